@@ -14,7 +14,12 @@ dropout 0.1, fp32-class (x6) arithmetic. `--config K` runs BASELINE.json configs
   5  32-block fully connected towers, 8,192 per GPU, S=10, forward only, hipGraph replay
 
 Contract: `python bench.py --gpus N --steps K --warmup W` (N>1 under torch.distributed.run, one
-rank per GPU). Prints ONE JSON line on rank 0. See DESIGN.md §7 for the roofline accounting.
+rank per GPU). Prints ONE JSON line on rank 0. A plain run does what the headline figure needs: set
+up, warm up, time the K steps, print the line. `--full` adds every other measurement, each in runs of
+its own outside the timed region: the per-kernel table and the dominant kernel's roofline, the same
+step in the other arithmetic modes, the CPU baseline (the --no-* options trim a full run).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy. See DESIGN.md §7 for
+the roofline accounting.
 """
 from __future__ import annotations
 
@@ -497,6 +502,33 @@ def timed_steps(trainer, step_in, kid, n_micro, steps, slots):
     return ms, len(ms) // steps, out3
 
 
+# ------------------------------------------------------------------------------ outputs
+DUMP_LIMIT = 64 << 20     # bytes over all dumped arrays
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """`--dump-outputs`: the arrays the timed path handed back in its last step, one float32/float64
+    `<name>.npy` each. An array larger than its share of DUMP_LIMIT is cut to a fixed sample (sorted
+    indices drawn from one seed over the flattened array), so two builds dump the same elements."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64 if a.dtype.itemsize > 4 else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(2024).choice(a.size, size=share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
+def train_outputs(trainer, out3, n_micro: int) -> dict:
+    """What a caller of Trainer.step holds after the step: its [loss, correct, n], the updated
+    parameters and Adam moments, and the step's (node-weighted, summed) flat gradient."""
+    grads = trainer.engine.grads if n_micro == 1 else trainer._acc
+    return {"out3": out3, "params": trainer.params, "adam_m": trainer.m, "adam_v": trainer.v, "grads": grads}
+
+
 # ------------------------------------------------------------------------------ main
 _JSON_OUT = None
 
@@ -526,11 +558,17 @@ def main():
     ap.add_argument("--math", default=None, choices=["x6", "f32", "bf16"],
                     help="matrix-product arithmetic (spwgnn.h SPWGNN_MATH_*), overrides the config")
     ap.add_argument("--dropout", type=float, default=0.1)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the per-kernel roofline table and the dominant kernel's "
+                         "roofline, the same step in the other arithmetic modes, the CPU baseline (each in "
+                         "runs of its own; trim with the --no-* options)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy")
     ap.add_argument("--roofline-kernel", default=None, choices=sorted(KERNELS))
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-f32-leg", action="store_true", help="skip the other-math reference measurements")
-    ap.add_argument("--no-kernel-table", action="store_true", help="skip the per-kernel roofline table")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-f32-leg", action="store_true", help="--full: skip the other-math reference measurements")
+    ap.add_argument("--no-kernel-table", action="store_true", help="--full: skip the per-kernel roofline table")
     ap.add_argument("--infer", action="store_true", help="alias of --config 5")
     ap.add_argument("--graph", action="store_true",
                     help="small-batch configs: replay each step as one captured hipGraph instead of issuing its "
@@ -544,6 +582,8 @@ def main():
                     help="N>1: all-reduce the whole gradient after the backward instead of the early range "
                          "[rmp.1.kernel, end) during it (Trainer.reduce_split)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.infer:
         args.config = 5
     cfg = dict(CONFIGS[args.config])
@@ -606,14 +646,15 @@ def run_train(args, cfg, world, rank, device):
 
     # every timed kernel's per-step time, before the timed region (untimed steps), so the roofline
     # can name the DOMINANT kernel (largest ms per step) and time it inside the timed region
+    # (--full; a plain run times one kernel only when --roofline-kernel names it)
     table = {}
-    if not args.no_kernel_table or not args.roofline_kernel:
+    if args.full and (not args.no_kernel_table or not args.roofline_kernel):
         table = kernel_table(trainer, step_in, n_micro, S, Ne, Nn, math, args.config, wl)
-    kname = args.roofline_kernel or dominant(table)
-    kid = KERNELS[kname][0]
+    kname = args.roofline_kernel or (dominant(table) if args.full else None)
+    kid = KERNELS[kname][0] if kname else 0
     if cfg.get("replay") and world == 1 and n_micro == 1 and not dp:
         return run_replay(args, cfg, trainer, rank, device, kname, table, wl)
-    ev = HipEvents(2 * MAX_LAUNCHES * n_micro * args.steps)
+    ev = HipEvents(2 * MAX_LAUNCHES * n_micro * args.steps) if kid else None
     per = 2 * MAX_LAUNCHES * n_micro
     # N>1: the gradient all-reduce of every timed step between two events on the step's stream, so
     # the line separates the collective (RCCL over xGMI) from the compute
@@ -628,12 +669,12 @@ def run_train(args, cfg, world, rank, device):
     t0 = time.perf_counter()
     for k in range(args.steps):
         # the library fills events in launch order: one slice of the array per step (and micro-batch)
-        evs = ev.ev[per * k: per * (k + 1)]
+        evs = ev.ev[per * k: per * (k + 1)] if ev else None
         if ar_ev:
             trainer.ar_events = ar_ev[k]
         if ar_early:
             trainer.ar_early_events = ar_early[k]
-        if n_micro == 1:
+        if n_micro == 1 or not ev:
             trainer.prof_kernel, trainer.prof_events = kid, evs
             out3 = trainer.step(*step_in)
         else:
@@ -673,13 +714,17 @@ def run_train(args, cfg, world, rank, device):
     if dp:
         dist.all_reduce(el_t, op=dist.ReduceOp.MAX)
     el = float(el_t.item())
-    kern_ms = recorded_ms(ev, MAX_LAUNCHES * n_micro * args.steps)
-    ev.close()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, train_outputs(trainer, out3, n_micro))
     loss = float(out3[0].item())     # node-weighted mean BCE over this rank's micro-batches
 
-    roof = roofline(kname, kern_ms, len(kern_ms) // args.steps, Ne, Nn, S, math, args.config, wl)
-    roof["selected"] = "--roofline-kernel" if args.roofline_kernel else \
-        "dominant: largest ms per step in this run's kernel table (measured before the timed region)"
+    roof = None
+    if ev:
+        kern_ms = recorded_ms(ev, MAX_LAUNCHES * n_micro * args.steps)
+        ev.close()
+        roof = roofline(kname, kern_ms, len(kern_ms) // args.steps, Ne, Nn, S, math, args.config, wl)
+        roof["selected"] = "--roofline-kernel" if args.roofline_kernel else \
+            "dominant: largest ms per step in this run's kernel table (measured before the timed region)"
     metric = METRIC if args.config == 0 else f"towers/sec fwd+bwd, BASELINE config {args.config}"
     out = {
         "metric": metric,
@@ -708,7 +753,7 @@ def run_train(args, cfg, world, rank, device):
     if allreduce:
         out["allreduce_ms"] = allreduce["allreduce_ms"]
         out["allreduce"] = allreduce
-    if world == 1 and args.config == 0 and math == "x6" and not args.no_f32_leg:
+    if args.full and world == 1 and args.config == 0 and math == "x6" and not args.no_f32_leg:
         # the same step in the other SPWGNN_MATH_* modes, for reference: f32 MFMA (fp32-class like
         # x6) and bf16 (operands rounded to bf16, one product — BASELINE configs 3-4's arithmetic)
         for m in ("f32", "bf16"):
@@ -728,7 +773,7 @@ def run_train(args, cfg, world, rank, device):
     out["hbm"] = step_hbm(args.config, out["ms_per_step"], math, wl)
     if table and not args.no_kernel_table:
         out["kernels"] = table
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
     if rank == 0:
         emit(out)
@@ -757,9 +802,14 @@ def run_replay(args, cfg, trainer, rank, device, kname, table, wl):
         trainer.replay_step(rs, plan, tgt)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        # the replayed step keeps its gradient to itself; its logits are the caller's (ReplayStep.z)
+        outs = train_outputs(trainer, rs.bce.out3, 1)
+        outs.pop("grads")
+        dump_outputs(args.dump_outputs, dict(outs, logits=rs.z))
     loss = float(rs.bce.out3[0].item())
     Ne, Nn = len(plan.src), plan.n_nodes
-    k = table.get(kname)
+    k = table.get(kname) if kname else None
     roof = None
     if k:
         roof = roofline(kname, [k["avg_launch_ms"]], k["launches_per_step"], Ne, Nn, S, math, args.config, wl)
@@ -780,7 +830,7 @@ def run_replay(args, cfg, trainer, rank, device, kname, table, wl):
         "loss": round(loss, 5), "roofline": roof, "kernels": table, "cpu_baseline": None,
     }
     out["hbm"] = step_hbm(args.config, out["ms_per_step"], math, wl)
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
     emit(out)
 
@@ -868,11 +918,12 @@ def run_infer(args, cfg, world, rank, device):
         graph.replay()
     torch.cuda.synchronize()
     # every forward kernel timed with HIP events on un-captured passes (same stream, same launches);
-    # the roofline names the dominant one (largest ms per forward)
+    # the roofline names the dominant one (largest ms per forward). --full; a plain run times one
+    # kernel only when --roofline-kernel names it
     Ne, Nn = batch.n_edges, batch.n_nodes
     wl = workload_name(cfg, world, 0.0)
     table, times = {}, {}
-    for name in INFER_KERNELS:
+    for name in INFER_KERNELS if args.full else [k for k in (args.roofline_kernel,) if k]:
         ev = HipEvents(2 * MAX_LAUNCHES * 3)
         for k in range(3):
             evs = ev.ev[2 * MAX_LAUNCHES * k: 2 * MAX_LAUNCHES * (k + 1)]
@@ -889,10 +940,10 @@ def run_infer(args, cfg, world, rank, device):
                        "ms_per_step": r["ms_per_step"], "tflops": r["mfma_achieved_tflops"], "frac": r["mfma_frac"],
                        "bound": r["bound"], "roof_frac": r["frac"], "alg_hbm_frac": r["alg_hbm_frac"],
                        "traffic": r["traffic"], "hbm_gbs": r["hbm_gbs"]}
-    kname = args.roofline_kernel or dominant(table)
-    if kname not in times:
+    kname = args.roofline_kernel or (dominant(table) if args.full else None)
+    if kname and kname not in times:
         raise SystemExit(f"kernel {kname} is not launched by the inference forward")
-    kern_ms = times[kname]
+    kern_ms = times.get(kname)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -907,6 +958,8 @@ def run_infer(args, cfg, world, rank, device):
     if world > 1:
         dist.all_reduce(el_t, op=dist.ReduceOp.MAX)
     el = float(el_t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": z})
     out = {
         "metric": INFER_METRIC, "value": round(world * B * args.steps / el, 1), "unit": "towers/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -918,12 +971,12 @@ def run_infer(args, cfg, world, rank, device):
         "step_tflops": round(fwd_flops(Ne, Nn, S) * world * args.steps / el / 1e12, 2),
         "roofline": dict(roofline(kname, kern_ms, len(kern_ms) // 3, Ne, Nn, S, math, 5, wl),
                          selected="--roofline-kernel" if args.roofline_kernel else
-                         "dominant: largest ms per forward in this run's kernel table"),
+                         "dominant: largest ms per forward in this run's kernel table") if kname else None,
         "kernels": table,
         "cpu_baseline": None,
     }
     out["hbm"] = step_hbm(5, out["ms_per_step"], math, wl)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
     if rank == 0:
         emit(out)

@@ -248,6 +248,29 @@ def test_bench_roofline_bound_follows_intensity():
     bench._FUSED[0] = False
 
 
+def test_bench_dump_outputs_float_arrays_within_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32/float64 .npy per array; an array over its share of the byte
+    limit is cut to the same sorted sample of its elements on every call."""
+    import importlib.util
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_LIMIT <= 64 << 20
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 3 * 400)
+    big = np.arange(1000, dtype=np.float32).reshape(10, 100)
+    arrays = {"out3": torch.tensor([0.5, 7.0, 9.0]), "count": np.arange(5, dtype=np.int64), "big": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert a["out3"].dtype == np.float32 and np.array_equal(a["out3"], [0.5, 7.0, 9.0])
+    assert a["count"].dtype == np.float64 and np.array_equal(a["count"], np.arange(5))
+    assert a["big"].dtype == np.float32 and a["big"].shape == (100,) and np.all(np.diff(a["big"]) > 0)
+    assert sum(v.nbytes for v in a.values()) <= 3 * 400
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+
+
 def test_plan_without_any_edge_and_empty_batch():
     """Single-box towers: no edge list at all (NULL src/dst through the C-ABI), one padding block
     per wave-tile; an empty batch is rejected before the library is called."""

@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT; T=${1:-x}
 cd $R
 for c in ${CONFIGS:-0}; do
   for L in ${LIBS:-A B A B}; do
-    SPWGNN_LIB=$R/${AB_DIR:-abl}/lib$L.so timeout -k 10 300 python3 bench.py --config $c --no-cpu-baseline --no-f32-leg \
+    SPWGNN_LIB=$R/${AB_DIR:-abl}/lib$L.so timeout -k 10 300 python3 bench.py --full --config $c --no-cpu-baseline --no-f32-leg \
       > gpurun_out/ab_${T}_c${c}_$L.json 2> gpurun_out/ab_${T}_c${c}_$L.err || { tail -20 gpurun_out/ab_${T}_c${c}_$L.err; exit 1; }
     echo "c$c $L $(KERNELS="${KERNELS:-wgrad_ws wgrad_w2 edge_fwd edge_bwd dA}" python3 -c "
 import json, os
