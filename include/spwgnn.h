@@ -129,6 +129,8 @@ typedef struct spwgnn_batch {
     int32_t flags;          /* SPWGNN_BATCH_* (0: a plan of spwgnn_plan_fill / _fill_cap)      */
     const float* pos;           /* [n_nodes][4]: objects (x, y, w)/170 + 0 pad (Networks.py:22)   */
     const float* prop;          /* [n_nodes][100] 'propagation' input (Networks.py:29); NULL = 0  */
+                                /* NULL is the fast case: the large-batch kernels skip the products with
+                                 * the zero state instead of multiplying it (an all-zero array is not detected) */
     const int32_t* node_tower;  /* [n_nodes] tower id (dropout key)                                */
     const int32_t* node_local; /* [n_nodes] node index inside its tower (dropout key)             */
     const int32_t* wtile;       /* [n_wtiles][4] first block, #blocks, first node, #nodes         */
@@ -229,7 +231,10 @@ int32_t spwgnn_forward(const float* params, const spwgnn_batch* batch, const spw
 
 /* Backward of the last spwgnn_forward on the same workspace (training == 1): dlogits [n_nodes]
  * → grads (flat, same layout as params; overwritten) and, if dprop != NULL, d/d propagation
- * [n_nodes][100]. Replaces TF autodiff of the graph (Networks.py:102 compile → fit). */
+ * [n_nodes][100]. Replaces TF autodiff of the graph (Networks.py:102 compile → fit).
+ * dprop == NULL is the fast case: step 0's gradient of the state is then not computed at all (with
+ * batch->prop == NULL too, the large-batch step loop also drops step 0's edge backward). The batch
+ * must be the forward's, its prop pointer null or non-null as it was there. */
 int32_t spwgnn_backward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
                         void* workspace, int64_t workspace_bytes, const float* dlogits,
                         float* grads, float* dprop, spwgnn_stream_t stream);

@@ -351,9 +351,20 @@ static bool bwd_fused_taken(const spwgnn_run* r, const spwgnn_batch* b) {
            !(b->flags & SPWGNN_BATCH_RECV_BLOCKS) && !store_b16_node(r, b) && !getenv_flag("SPWGNN_NO_BWD_FUSED");
 }
 
+// The loop-end shortcuts drop stores whose readers are all wide split-bf16 kernels
+// that know the rows are zero or unread: the node forward's step 0 (P0), the node backward's first
+// step (P_S) and, in training, the k_wgrad_ws jobs over P (step 0's stages). True when the run takes
+// exactly those kernels on the node side.
+static bool wide_node_side(const spwgnn_run* r, const spwgnn_batch* b) {
+    if (r->math == MATH_F32 || kmath(r, kX6NodeFwd) == MATH_F32 || team_blocks((b->n_nodes + 31) / 32)) return false;
+    return !r->training ||
+           (kmath(r, kX6NodeBwd) != MATH_F32 && kmath(r, kX6Wgrad) != MATH_F32 && !getenv_flag("SPWGNN_WG_OLD"));
+}
+
 static int32_t run_forward(const float* params, const spwgnn_batch* b, const spwgnn_run* r, const Ws& w,
                            char* base, float* logits, hipStream_t st) {
     Ctx c{w, base};
+    const bool zero_prop = b->prop == nullptr;   // 'propagation' = 0 (spwgnn.h): P0 = U0 = V0 = 0
     PrepArgs pa{};
     pa.params = params;
     pa.pk = c.f(w.pk);
@@ -421,6 +432,7 @@ static int32_t run_forward(const float* params, const spwgnn_batch* b, const spw
     en.U0 = c.f(w.U_at(0));
     en.V0 = c.f(w.V_at(0));
     en.uv16 = uv16;
+    en.store_p0 = !(zero_prop && wide_node_side(r, b));   // the zero P0 rows have no reader there (§3zh)
     en.dropout_on = drop;
     en.thresh = thresh;
     en.scale = scale;
@@ -489,6 +501,7 @@ static int32_t run_forward(const float* params, const spwgnn_batch* b, const spw
         ef.recv_blocks = (b->flags & SPWGNN_BATCH_RECV_BLOCKS) && kmath(r, kX6EdgeFwd) == MATH_X6 &&
                          b->n_eblocks == b->n_nodes && !getenv_flag("SPWGNN_RB_ONEHOT");
         ef.mask2 = r->training ? c.u(w.m2_at(s)) : nullptr;
+        ef.uv_zero = s == 0 && zero_prop;
         return ef;
     };
     auto node_args = [&](int s) {
@@ -530,6 +543,8 @@ static int32_t run_forward(const float* params, const spwgnn_batch* b, const spw
         }
         nf.n16 = store_b16_node(r, b);
         nf.uv16 = uv16;
+        nf.p_zero = s == 0 && zero_prop;
+        nf.last = s == S - 1 && wide_node_side(r, b);   // P_S unwritten: its one reader must know (§3zh)
         return nf;
     };
     if (fwd_fused_taken(r, b)) {
@@ -607,6 +622,7 @@ struct WgSpec {
     int tk = -1, tb = -1, k_rows = 0, k_row0 = 0, bias_row = -1, perm = 0;
     bool recompute = false;   // XM_H1 / YM_DH2 context below
     int b16 = 0;              // kB16X / kB16Y: bf16-stored operands (bf16 math, store_b16)
+    bool skip0 = false;       // k_wgrad_ws: step 0's X rows are exactly zero — its stages are left out
     const float2* xd = nullptr;          // z1 rebuilt from d (k_wgrad_ws XD 1)
     const float4* xp = nullptr;          // zo1 rebuilt from the node positions (XD 2)
     const float *w0 = nullptr, *b0 = nullptr;
@@ -684,6 +700,7 @@ static int32_t run_wgrad(const Ctx& c, const spwgnn_batch* b, const WgSpec& g, f
         wa.xp = g.xp;
         wa.w0 = g.w0;
         wa.b0 = g.b0;
+        wa.skip0 = g.skip0;   // the partition below is that of all S steps either way (same chunk sums)
         const int64_t nst = wa.nbs * wa.S;
         int64_t wgs = std::min<int64_t>(nst, kW2gWgs);
         if (wsb) {
@@ -799,6 +816,14 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
     const bool n16 = store_b16_node(r, b);
     const int64_t nN = b->n_nodes;
     const float scale = (r->dropout > 0.f) ? 1.0f / (1.0f - r->dropout) : 1.0f;
+    // Loop-end shortcuts. A null prop is P0 = 0: step 0's rows add nothing to the
+    // W1b / W1c / omp.0-P gradients, so their k_wgrad_ws jobs leave step 0's stages out (ws_skip0).
+    // dP_0, dU_0 and dV_0 then feed only the dprop pass: without a dprop request the wide node
+    // backward leaves dP_0 out and step 0's edge backward, which under the dA rebuild writes nothing
+    // but dU_0 / dV_0, is not launched.
+    const bool zero_prop = b->prop == nullptr, need_dP0 = dprop != nullptr;
+    const bool ws_skip0 = zero_prop && kmath(r, kX6Wgrad) != MATH_F32 && !getenv_flag("SPWGNN_WG_OLD");
+    const bool skip_eb0 = rebuild && ws_skip0 && !need_dP0 && !team_blocks(b->n_wtiles);
     // the reductions write the 22 Keras tensors' elements, not every float of the flat buffer: the
     // remaining ranges (alignment gaps; tensors no job of this batch writes) are zeroed by the same
     // reduction launch (tests/test_gpu_parity.py::test_backward_writes_every_gradient; a NaN-filled
@@ -849,6 +874,7 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
             nb.x_w3t = c.x6(X6_W3T);
         }
         nb.n16 = n16;
+        nb.no_dP = s == 0 && !need_dP0;
         return nb;
     };
     auto edge_args = [&](int s) {
@@ -1010,6 +1036,7 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
             SPW_CHECK(prof.before(SPWGNN_K_NODE_BWD));
             SPW_CHECK(launch_node_bwd(nb, kmath(r, kX6NodeBwd), st));
             SPW_CHECK(prof.after(SPWGNN_K_NODE_BWD));
+            if (s == 0 && skip_eb0) break;   // dU_0 / dV_0 stay unwritten: nothing reads them
             const EdgeBwdArgs eb = edge_args(s);
             SPW_CHECK(prof.before(SPWGNN_K_EDGE_BWD));
             SPW_CHECK(launch_edge_bwd(eb, kmath(r, kX6EdgeBwd), st));
@@ -1085,17 +1112,20 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
             WgSpec g; node_xy(g, w.P, kLdN, kFN, -1, RN, w.dU, kLdE, kFE, 128, 160);
             g.tk = T_RMP0K; g.k_rows = kFN; g.k_row0 = 150;
             g.b16 = n16 ? kB16Y : 0;
+            g.skip0 = ws_skip0;
             if ((e = wg(g))) return e;
         }
         {   // rmp.0 rows 250..349 (W1c)
             WgSpec g; node_xy(g, w.P, kLdN, kFN, -1, RN, w.dV, kLdE, kFE, 128, 160);
             g.tk = T_RMP0K; g.k_rows = kFN; g.k_row0 = 250;
             g.b16 = n16 ? kB16Y : 0;
+            g.skip0 = ws_skip0;
             if ((e = wg(g))) return e;
         }
         {   // omp.0 rows 200..299 (P part)
             WgSpec g; node_xy(g, w.P, kLdN, kFN, -1, RN, w.do1, kLdN, kFN, 128, 128);
             g.tk = T_OMP0K; g.k_rows = kFN; g.k_row0 = 200;
+            g.skip0 = ws_skip0;
             if ((e = wg(g))) return e;
         }
         {   // omp.0 rows 100..199 (effect part)

@@ -500,18 +500,27 @@ struct has_b16_words<T, std::void_t<decltype(std::declval<const std::decay_t<T>&
 // (k_prep) holds, per step u = kb·NT_OUT + T, the three matching A-operand parts of lane (i, h),
 // 16 bytes each: [u][part][lane] uint4. Steps stream through a D-deep ring of static slots (fully
 // unrolled; the loads of step u + D issue before step u's MFMAs).
-template <int NT_OUT, int NKB, int NC, int D = kX6Ring, int PARTS = 3, bool HT = false, class GetB>
+// INT, T0: the NT_OUT output tiles are tiles T0 .. T0 + NT_OUT − 1 of an image built for INT tiles
+// per k-block (a product of which only some output tiles are consumed; default: the whole image).
+template <int NT_OUT, int INT, int T0>
+__device__ __forceinline__ constexpr int x6_img_step(int u) {
+    return INT == NT_OUT && T0 == 0 ? u : (u / NT_OUT) * INT + T0 + u % NT_OUT;
+}
+template <int NT_OUT, int NKB, int NC, int D = kX6Ring, int PARTS = 3, bool HT = false, int INT = NT_OUT, int T0 = 0,
+          class GetB>
 __device__ __forceinline__ void tgemm_x6(GetB&& getb, f32x16 (&out)[NC][NT_OUT], const uint4* __restrict__ img,
                                          int lane) {
     static_assert(!HT || NT_OUT == 4, "half tile: 4-tile products");
+    static_assert(T0 + NT_OUT <= INT && (!HT || INT == NT_OUT), "output tiles within the image's");
     constexpr int NS = NKB * NT_OUT, NP = 4 * NC;   // pair-splits per k-block
+    static_assert(D <= NS, "ring deeper than the product");
     constexpr int SPD = HT ? 3 : 2;                 // split slots (HT: a pair's first k-block stays live)
     const uint4* wb = img + lane;
     uint4 ring[D][3];
 #pragma unroll
     for (int d = 0; d < D; ++d)
 #pragma unroll
-        for (int p = 0; p < 3; ++p) ring[d][p] = wb[(d * 3 + p) * 64];
+        for (int p = 0; p < 3; ++p) ring[d][p] = wb[(x6_img_step<NT_OUT, INT, T0>(d) * 3 + p) * 64];
     // split parts of k-block kb in slot kb % SPD; the next k-block's pair-splits are spread over
     // this k-block's steps, so the VALU work interleaves with the MFMAs
     uint32_t sp[SPD][NC][3][4];
@@ -544,7 +553,7 @@ __device__ __forceinline__ void tgemm_x6(GetB&& getb, f32x16 (&out)[NC][NT_OUT],
         for (int p = 0; p < 3; ++p) a[p] = as_bf16x8(ring[u % D][p]);
         if (u + D < NS) {
 #pragma unroll
-            for (int p = 0; p < 3; ++p) ring[u % D][p] = wb[((u + D) * 3 + p) * 64];
+            for (int p = 0; p < 3; ++p) ring[u % D][p] = wb[(x6_img_step<NT_OUT, INT, T0>(u + D) * 3 + p) * 64];
         }
         if (kb + 1 < NKB) {
 #pragma unroll
@@ -585,10 +594,11 @@ template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
-template <int NT_OUT, int NKB, int NC, int NW, int PARTS = 3, bool HT = false, class GetB>
+template <int NT_OUT, int NKB, int NC, int NW, int PARTS = 3, bool HT = false, int INT = NT_OUT, int T0 = 0, class GetB>
 __device__ __forceinline__ void tgemm_x6_wg(GetB&& getb, f32x16 (&out)[NC][NT_OUT], const uint4* __restrict__ img,
                                             int lane, const WgRing<NW>& wr) {
     static_assert(!HT || NT_OUT == 4, "half tile: 4-tile products");
+    static_assert(T0 + NT_OUT <= INT && (!HT || INT == NT_OUT), "output tiles within the image's");
     constexpr int SPD = HT ? 3 : 2;
     constexpr int LP = PARTS == 1 ? 1 : 3;    // parts held in LDS
     constexpr int KPS = PARTS == 1 ? 3 : 1;   // k-blocks per slice
@@ -602,7 +612,7 @@ __device__ __forceinline__ void tgemm_x6_wg(GetB&& getb, f32x16 (&out)[NC][NT_OU
         for (int q = 0; q < PPW; ++q) {
             const int i = min(wr.wid + NW * q, pc - 1);   // the last pieces may be loaded twice (same bytes)
             const int js = i / LP, p = i - js * LP;       // step within the slice, part
-            __builtin_amdgcn_global_load_lds(img + ((sl * SST + js) * 3 + p) * 64 + lane,
+            __builtin_amdgcn_global_load_lds(img + (x6_img_step<NT_OUT, INT, T0>(sl * SST + js) * 3 + p) * 64 + lane,
                                              wr.lds + ((sl % R) * kWgSlot + i * 64), 16, 0, 0);
         }
     };
@@ -719,6 +729,35 @@ __device__ __forceinline__ void tchain_x6s(const f32x16 (&in)[NC][NT_IN], f32x16
                                            const uint4* __restrict__ img, int lane, const WgRing<NW>& wr) {
     if constexpr (NW > 0) tchain_x6_wg<NT_OUT, NKB, NT_IN, NC, NW, PARTS, HT>(in, out, img, lane, wr);
     else tchain_x6<NT_OUT, NKB, NT_IN, NC, D, PARTS, HT>(in, out, img, lane);
+}
+// One k-block KB of a chain product, for an input whose other k-blocks are known to be zero (the node
+// backward's first step: dx' is the logit row alone). The skipped k-blocks would add ±0 to the
+// accumulators, so for KB the last k-block the sums are those of the whole chain. (HT: KB must be
+// the image's last k-block and even — its half-tile slot then holds that k-block alone.)
+template <int NT_OUT, int KB, int NT_IN, int NC, int D, int PARTS, int NW, bool HT = false>
+__device__ __forceinline__ void tchain_x6s_kb(const f32x16 (&in)[NC][NT_IN], f32x16 (&out)[NC][NT_OUT],
+                                              const uint4* __restrict__ img, int lane, const WgRing<NW>& wr) {
+    static_assert(KB < 2 * NT_IN, "k-block beyond the input tiles");
+    tgemm_x6s<NT_OUT, 1, NC, D, PARTS, NW, HT>(
+        [&](int c, int, float (&v)[8]) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = in[c][KB >> 1][8 * (KB & 1) + e];
+        },
+        out, img + KB * NT_OUT * 3 * 64, lane, wr);
+}
+// Output tile T0 alone of a chain product on an INT-tile image (the node forward's last step: only
+// the logit's tile of o1·Wo2' is consumed). The tile's accumulator takes the MFMAs it takes in the
+// whole product, in the same k order: bit-identical.
+template <int T0, int INT, int NKB, int NT_IN, int NC, int D, int PARTS, int NW>
+__device__ __forceinline__ void tchain_x6s_tile(const f32x16 (&in)[NC][NT_IN], f32x16 (&out)[NC][1],
+                                                const uint4* __restrict__ img, int lane, const WgRing<NW>& wr) {
+    static_assert(NKB <= 2 * NT_IN, "k-blocks beyond the input tiles");
+    auto getb = [&](int c, int kb, float (&v)[8]) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = in[c][kb >> 1][8 * (kb & 1) + e];
+    };
+    if constexpr (NW > 0) tgemm_x6_wg<1, NKB, NC, NW, PARTS, false, INT, T0>(getb, out, img, lane, wr);
+    else tgemm_x6<1, NKB, NC, D, PARTS, false, INT, T0>(getb, out, img, lane);
 }
 // the chain kernels' 4-tile products in the half-tile form: kHT (kernels.h, build flag SPWGNN_HT)
 

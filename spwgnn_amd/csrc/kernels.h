@@ -114,6 +114,9 @@ struct EncNodeArgs {
     const uint4* xh_om1;                  // its half-tile form (the chain kernel, §3w)
     float *zo1, *co, *P0, *U0, *V0;
     int uv16;                   // U0, V0 in bf16 math (training): kUvRound / kUvB16 (gemm_blocks.h store_cm_uv)
+    // prop null (P0 = 0, so U0 = V0 = 0) on the wide x6/bf16 kernel: the two products are not run, and
+    // the zero P0 rows are stored only with store_p0 (some later kernel reads them)
+    int store_p0;
     int dropout_on;
     uint32_t thresh;
     float scale;
@@ -159,6 +162,7 @@ struct EdgeFwdArgs {
     int n16;           // bf16 math (training, wide kernels): H2s stored as bf16 (§3g, node side)
     int uv16;          // how U, V were stored (store_cm_uv): kUvB16 exactly when n16 (the N16 kernel reads bf16)
     const uint4* x_w2; // x6 image of W2 (half rows, kh 76) — the LDS B operand (math == MATH_X6)
+    int uv_zero;       // step 0 of a null 'propagation': the U, V rows are all zero (§3zh)
 };
 
 struct NodeFwdArgs {
@@ -174,6 +178,10 @@ struct NodeFwdArgs {
     const uint4 *xh_w3a, *xh_wo1c, *xh_wo1a, *xh_wo1p, *xh_wo2;            // half-tile forms (chain kernel, §3w)
     int n16;        // bf16 math (training, wide kernels): H2s read and o1 stored as bf16 (§3g, node side)
     int uv16;       // U, V in bf16 math (training): kUvRound, or kUvB16 (exactly when n16)
+    // loop-end shortcuts of the wide x6/bf16 kernel; the other kernels ignore them
+    int p_zero;     // step 0 of a null 'propagation': P is zero and not read (no P·Wo1p, x' + 0)
+    int last;       // step S-1: only the logit (x' row 100, output tile 3 of o1·Wo2') is consumed —
+                    //   no other output tile, no residual tanh, no P_S store
 };
 
 struct NodeBwdArgs {
@@ -196,6 +204,9 @@ struct NodeBwdArgs {
     const float *bce_logits, *bce_targets;
     float* bce_dlogits;
     int64_t bce_n;
+    // step 0 without a dprop request (wide x6/bf16 kernel): dP_0 has no reader — no
+    // do1·Wo1pᵀ product, no dPout store; the other kernels ignore it
+    int no_dP;
 };
 
 struct EdgeBwdArgs {
@@ -299,7 +310,9 @@ struct WgWsArgs {          // k_wgrad_ws: stages (s, nb) of a [S][nbs] grid of 3
     const float *w0, *b0;  // XD: the first-layer pack [2][KXP] and its bias [KXP]
     float* slab;           // [wgs][kx_pad][ny_pad]
     int64_t nbs, S, x_sb, y_sb, count, stages_per_wg;
-    int x_ones, pad0;
+    int x_ones;
+    int skip0;             // 1: step 0's stages contribute nothing (X rows exactly zero) and are not run;
+                           //    the stage partition (workgroup ↔ chunk slab) stays as it is
 };
 // bf16 storage of the weight gradients' edge operands (bf16 math, §3g): bit 0 X, bit 1 Y
 enum : int { kB16X = 1, kB16Y = 2, kB16A = 4, kB16UV = 8 };   // kB16A / kB16UV: the W2 gradient's A / U, V rows

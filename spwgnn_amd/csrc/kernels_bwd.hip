@@ -180,20 +180,27 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_bwd_x6(NodeBwdArg
         }
         return;
     }
+    // Loop-end shortcuts, all workgroup-uniform. first: the incoming dP is zero, so
+    // P_S is not read (the last forward step does not store it), dpre = 0 is not stored and read
+    // back, and dx' is the logit row alone — Wo2'ᵀ runs over that row's k-block only. no_dP (step 0,
+    // no dprop request): dP_0 has no reader — no store, no do1·Wo1pᵀ.
+    const bool dp_rmw = !a.first && !a.no_dP;   // dP_s = dpre + do1·Wo1pᵀ through memory (D's registers are reused)
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        f32x16 Pn[4];
-        load_cm<4>(a.Pn + bN(c), Pn, lane);
+        if (!a.first) {
+            f32x16 Pn[4];
+            load_cm<4>(a.Pn + bN(c), Pn, lane);
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
+            for (int t = 0; t < 4; ++t)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int f = rho(r, 0) + 4 * h + 32 * t;
-                const float p = Pn[t][r];
-                D[c][t][r] = f < kFN ? D[c][t][r] * (1.f - p * p) : 0.f;  // tanh' (Networks.py:91)
-            }
+                for (int r = 0; r < 16; ++r) {
+                    const int f = rho(r, 0) + 4 * h + 32 * t;
+                    const float p = Pn[t][r];
+                    D[c][t][r] = f < kFN ? D[c][t][r] * (1.f - p * p) : 0.f;  // tanh' (Networks.py:91)
+                }
+        }
         // the residual path: dP_s gets dpre directly (Add()([prop_layer(x), prop]))
-        if (has[c]) store_cm<4>(a.dPout + bN(c), D[c], lane, valid[c]);
+        if (dp_rmw && has[c]) store_cm<4>(a.dPout + bN(c), D[c], lane, valid[c]);
         if (a.first && h == 1) D[c][3][0] = valid[c] ? a.dlogits[(nb0 + c) * 32 + j] : 0.f;  // x' row 100 = logit
         if (has[c]) {
             if constexpr (N16) store_cm_b16<4>(reinterpret_cast<uint16_t*>(a.dx) + bN(c), D[c], lane, valid[c]);
@@ -201,7 +208,10 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_bwd_x6(NodeBwdArg
         }
     }
     zero2(G);
-    tchain_x6s<4, 7, 4, NC, kX6Ring, NP, NW, kHT>(D, G, kHT ? a.xh_wo2t : a.x_wo2t, lane, wr);
+    if (a.first)   // row 100 = k-block 6 (k = 16·6 + 4h), the chain's last
+        tchain_x6s_kb<4, 6, 4, NC, kX6Ring, NP, NW, kHT>(D, G, kHT ? a.xh_wo2t : a.x_wo2t, lane, wr);
+    else
+        tchain_x6s<4, 7, 4, NC, kX6Ring, NP, NW, kHT>(D, G, kHT ? a.xh_wo2t : a.x_wo2t, lane, wr);
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         f32x16 O1[4];
@@ -214,15 +224,24 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_bwd_x6(NodeBwdArg
         if (has[c]) store_cm<4>(a.do1 + bN(c), G[c], lane, valid[c]);
     }
     // P part of omp's input → dP_s
-    zero2(D);
-    tchain_x6s<4, 7, 4, NC, kX6Ring, NP, NW, kHT>(G, D, kHT ? a.xh_wo1pt : a.x_wo1pt, lane, wr);
+    if (!a.no_dP) {
+        zero2(D);
+        tchain_x6s<4, 7, 4, NC, kX6Ring, NP, NW, kHT>(G, D, kHT ? a.xh_wo1pt : a.x_wo1pt, lane, wr);
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        f32x16 T[4];
-        load_cm<4>(a.dPout + bN(c), T, lane);
+        for (int c = 0; c < NC; ++c) {
+            if (dp_rmw) {
+                f32x16 T[4];
+                load_cm<4>(a.dPout + bN(c), T, lane);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) D[c][t] += T[t];
-        if (has[c]) store_cm<4>(a.dPout + bN(c), D[c], lane, valid[c]);
+                for (int t = 0; t < 4; ++t) D[c][t] += T[t];
+            } else {   // first: dpre = +0 (the sum a stored zero tile would give: −0 + 0 = +0)
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) D[c][t][r] += 0.f;
+            }
+            if (has[c]) store_cm<4>(a.dPout + bN(c), D[c], lane, valid[c]);
+        }
     }
     // c_o part → dc_o (accumulated over steps in step order S-1..0); with dco_sum the product with
     // Wo1cᵀ is linear in do1 and runs once on Σ_s do1_s (k_enc_node_bwd)

@@ -212,13 +212,19 @@ __global__ __launch_bounds__(256, 2) void k_enc_node_x6(EncNodeArgs a) {
             P[0][t][4 * q + 2] = v.z;
             P[0][t][4 * q + 3] = v.w;
         }
-    if (has) store_cm<4>(a.P0 + bN, P[0], lane, valid);
+    // a null prop (workgroup-uniform): P0 = 0, so U0 = V0 = 0 without the two products. The zero U0 /
+    // V0 rows are stored (the W2 gradient gathers them), the zero P0 rows only where a later kernel
+    // reads them (EncNodeArgs::store_p0)
+    const bool zp = a.prop == nullptr;
+    if (has && (!zp || a.store_p0)) store_cm<4>(a.P0 + bN, P[0], lane, valid);
     f32x16 U[1][5];
     zero_tiles(U[0]);
-    tchain_x6s<5, 7, 4, 1, kX6Ring, NP, NW>(P, U, a.x_w1b, lane, wr);
+    if (!zp) tchain_x6s<5, 7, 4, 1, kX6Ring, NP, NW>(P, U, a.x_w1b, lane, wr);
     if (has) store_cm_uv<5>(a.U0, bE, U[0], lane, valid, NP == 1 ? a.uv16 : kUvF32);
-    zero_tiles(U[0]);
-    tchain_x6s<5, 7, 4, 1, kX6Ring, NP, NW>(P, U, a.x_w1c, lane, wr);
+    if (!zp) {
+        zero_tiles(U[0]);
+        tchain_x6s<5, 7, 4, 1, kX6Ring, NP, NW>(P, U, a.x_w1c, lane, wr);
+    }
     if (has) store_cm_uv<5>(a.V0, bE, U[0], lane, valid, NP == 1 ? a.uv16 : kUvF32);
 }
 
@@ -764,7 +770,7 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_fwd_x6(NodeFwdArg
                 if (has[c]) store_cm<4>(a.cw_out + bN(c), O[c], lane, true);
     }
     tchain_x6s<4, 7, 4, NC, kX6Ring, NP, NW, kHT>(E, O, kHT ? a.xh_wo1a : a.x_wo1a, lane, wr);
-    {
+    if (!a.p_zero) {   // (workgroup-uniform) step 0 of a null prop: P = 0 adds nothing, and is not read
         HalfRows<kKhN, NC> hr;
         const float* blk[NC];
 #pragma unroll
@@ -780,6 +786,18 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_fwd_x6(NodeFwdArg
             else store_cm<4>(a.o1_out + bN(c), O[c], lane, valid[c]);
         }
     }
+    if constexpr (!kHT) {
+        if (a.last) {   // (workgroup-uniform) step S-1: nothing reads P_S — the logit's output tile alone
+            f32x16 X3[NC][1];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) X3[c][0] = zero16();
+            tchain_x6s_tile<3, 4, 7, 4, NC, kX6Ring, NP, NW>(O, X3, a.x_wo2, lane, wr);
+#pragma unroll
+            for (int c = 0; c < NC; ++c)   // x' row 100 = rho(0,1) + 96, + its bias (bias_act_rho's sum)
+                if (a.logits && h == 1 && valid[c]) a.logits[(nb0 + c) * 32 + j] = X3[c][0][0] + a.bo2p[100];
+            return;
+        }
+    }
     // X reuses E's registers: x' = o1·Wo2' + b, then P' = tanh(x' + P) into E
     f32x16 (&X)[NC][4] = E;
     zero2(X);
@@ -789,7 +807,8 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_fwd_x6(NodeFwdArg
         bias_act_rho<4, false>(X[c], a.bo2p, h);
         if (a.logits && h == 1 && valid[c]) a.logits[(nb0 + c) * 32 + j] = X[c][3][0];  // x' row 100 = rho(0,1) + 96
         f32x16 P[4];
-        load_cm<4>(a.P + bN(c), P, lane);
+        if (a.p_zero) zero_tiles(P);   // the sums the stored zero rows gave
+        else load_cm<4>(a.P + bN(c), P, lane);
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -988,7 +1007,9 @@ struct NodeSum16X6 {
 // W8 (≤ 32-node tiles): 8 waves at two per SIMD (256 registers: the 32-node sum and a short ring)
 // instead of 4 at one per SIMD with a 5-k-block ring
 // N16: H2s stored as bf16 (bf16 math, §3o)
-template <bool NW16, int DBG = 0, int NP = 3, bool AB16 = false, bool W8 = false, bool N16 = false>   // AB16: A stored as bf16 (§3g)
+// UV0 (step 0 of a null 'propagation', EdgeFwdArgs::uv_zero): U = V = 0 — h1 = relu(A + 0), no gathers
+template <bool NW16, int DBG = 0, int NP = 3, bool AB16 = false, bool W8 = false, bool N16 = false,   // AB16: A stored as bf16 (§3g)
+          bool UV0 = false>
 __global__ __launch_bounds__((NW16 || W8) ? 512 : 256, 1) __attribute__((amdgpu_waves_per_eu((NW16 || W8) ? 2 : 1, (NW16 || W8) ? 2 : 1)))
 void k_edge_fwd_x6(EdgeFwdArgs a) {
     // bf16 math (NP = 1): a k-block is 5 MFMAs, too short to cover a load one k-block ahead
@@ -1036,6 +1057,7 @@ void k_edge_fwd_x6(EdgeFwdArgs a) {
         }
     };
     auto ldUV = [&](const Src& sr, int kb, KU& r) {
+        if constexpr (UV0) return;
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const int q = min(2 * kb + c, kKhE / 4 - 1);
@@ -1084,7 +1106,10 @@ void k_edge_fwd_x6(EdgeFwdArgs a) {
             float xv[8];
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                const float4 av = unpack_uv(ca.a[c]), uv = unpack_uv(cu.u[c]), vv = unpack_uv(cu.v[c]);
+                const float4 av = unpack_uv(ca.a[c]);
+                // UV0: the sums the gathered zero rows gave (A + 0 + 0 = A + 0: −0 becomes +0 either way)
+                const float4 uv = UV0 ? make_float4(0.f, 0.f, 0.f, 0.f) : unpack_uv(cu.u[c]);
+                const float4 vv = UV0 ? make_float4(0.f, 0.f, 0.f, 0.f) : unpack_uv(cu.v[c]);
                 xv[4 * c + 0] = relu_valid(av.x + uv.x + vv.x, vcap);
                 xv[4 * c + 1] = relu_valid(av.y + uv.y + vv.y, vcap);
                 xv[4 * c + 2] = relu_valid(av.z + uv.z + vv.z, vcap);
@@ -1451,6 +1476,13 @@ hipError_t launch_enc_edge(const EncEdgeArgs& a, int math, hipStream_t st) {
         hipLaunchKernelGGL(k_enc_edge<false>, dim3((a.n_eblocks + 3) / 4), dim3(256), 0, st, a);
     return hipGetLastError();
 }
+// Step 0 of a null 'propagation' on the ≤ 16-node wide kernels without the U / V gathers (UV0): a
+// build option for A/B, default on (same box: edge forward −0.085 ms per step at the headline, −0.14
+// to −0.24 at config 3)
+#ifndef SPWGNN_EFWD_UV0
+#define SPWGNN_EFWD_UV0 1
+#endif
+constexpr bool kEfwdUv0 = SPWGNN_EFWD_UV0 != 0;
 hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
     if (a.nw_max > kNwMaxLimit) return hipErrorInvalidValue;  // one-hot rows: ≤ 32 nodes per wave-tile
     if ((a.uv16 == kUvB16) != (a.n16 != 0)) return hipErrorInvalidValue;   // bf16 U, V: the N16 kernel reads them
@@ -1470,7 +1502,10 @@ hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
             return hipGetLastError();
         }
 #endif
-        hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, 1, true, false, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
+        if (kEfwdUv0 && a.uv_zero)
+            hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, 1, true, false, true, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
+        else
+            hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, 1, true, false, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
         return hipGetLastError();
     }
     if (math == MATH_BF16) {
@@ -1485,7 +1520,9 @@ hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
             return hipGetLastError();
         }
 #endif
-        if (a.nw_max <= 16 && a.a_b16)
+        if (a.nw_max <= 16 && a.a_b16 && kEfwdUv0 && a.uv_zero)
+            hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, 1, true, false, false, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
+        else if (a.nw_max <= 16 && a.a_b16)
             hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, 1, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
         else if (a.a_b16)
             return hipErrorInvalidValue;
@@ -1517,6 +1554,8 @@ hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
         else if (a.nw_max <= 16 && dbg == 2)   // diagnosis: W2 image from L2 instead of LDS
             hipLaunchKernelGGL((k_edge_fwd_x6<true, 2>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
 #endif
+        else if (a.nw_max <= 16 && kEfwdUv0 && a.uv_zero)
+            hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, 3, false, false, false, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
         else if (a.nw_max <= 16)
             hipLaunchKernelGGL(k_edge_fwd_x6<true>, dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
         else   // ≤ 32-node tiles: two waves per SIMD (config 5: 37.5 -> 34.4 ms per forward, A/B on one box;

@@ -1096,9 +1096,12 @@ __device__ __forceinline__ void wgrad_ws_body(const WgWsArgs& a, int bid, char* 
     constexpr int MX = KXP / 32, MY = NYP / 32;
     auto buf = [&](int p) { return smem + p * W::BUF; };   // (offsets, not a pointer array: keeps the LDS address space)
     const int tid = threadIdx.x;
-    const int64_t t0 = (int64_t)bid * a.stages_per_wg;
+    // skip0: step 0's stages (t < nbs, a prefix of the workgroup's range) have zero X rows and are
+    // left out; the range's end and the slab (bid) stay, so every chunk sums what it summed before
     const int64_t nst = a.nbs * a.S;
-    const int T = t0 < nst ? (int)min<int64_t>(a.stages_per_wg, nst - t0) : 0;
+    const int64_t t1 = min<int64_t>((int64_t)bid * a.stages_per_wg + a.stages_per_wg, nst);
+    const int64_t t0 = max<int64_t>((int64_t)bid * a.stages_per_wg, a.skip0 ? a.nbs : 0);
+    const int T = t0 < t1 ? (int)(t1 - t0) : 0;
     if (tid < 256) {
         const int lane = tid & 63, c16 = lane & 15, kq = lane >> 4;
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
