@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 6   /* 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 7   /* 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
@@ -222,6 +222,15 @@ int32_t spwgnn_fused_path(const spwgnn_batch* batch, const spwgnn_run* run);
  * previous one; set < 0 only returns it. 0 puts every batch on the wide kernels (parity tests of the
  * large-batch path at oracle-sized batches). Read when a call plans its launches. */
 int32_t spwgnn_team_max_blocks(int32_t set);
+
+/* ABI 7. Stored steps of the dA sum on the wide x6 kernels: the edge backward of the
+ * last K propagation steps also keeps its dh1pre, and the dA kernel reads those K steps back instead
+ * of repeating their W2ᵀ products. Every K gives bitwise the same gradients; it trades matrix work for
+ * streamed bytes. The slabs are workspace arrays that are dead meanwhile: no larger workspace. K is
+ * clamped per call to min(4, mp_steps − 1) and is 0 for bf16 / fp32 math, small (team) batches and
+ * receiver-block plans. set >= 0 sets K for the process and returns the previous value; set < 0 only
+ * returns it. Read when a call plans its launches. */
+int32_t spwgnn_da_stored_steps(int32_t set);
 
 /* Forward: the whole graph of Networks.py:31-96 → per-node logits z (the model output is
  * sigmoid(z), Networks.py:94). logits: [n_nodes] device fp32. */

@@ -54,7 +54,7 @@ K_EDGE_FWD, K_NODE_FWD, K_EDGE_BWD, K_NODE_BWD, K_ENC_EDGE, K_ENC_EDGE_BWD, K_WG
 K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD = 9, 10, 11
 MATH_F32, MATH_X6, MATH_BF16 = 0, 1, 2
 STEP_KEY_COUNTER, STEP_KEY_SPLITMIX = 0, 1
-ABI_VERSION = 6        # SPWGNN_ABI_VERSION this binding's structs follow
+ABI_VERSION = 7        # SPWGNN_ABI_VERSION this binding's structs follow
 BATCH_RECV_BLOCKS = 1  # spwgnn_batch.flags: a receiver-block plan (spwgnn_plan_fill_recv)
 READOUT_SUM_PROB, READOUT_MEAN_PROB, READOUT_SUM_LOGIT, READOUT_MEAN_LOGIT = 0, 1, 2, 3
 
@@ -80,6 +80,7 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_workspace_bytes": (i64, [i32, i32, i32, i32]),
         "spwgnn_fused_path": (i32, [C.POINTER(BatchC), C.POINTER(RunC)]),
         "spwgnn_team_max_blocks": (i32, [i32]),
+        "spwgnn_da_stored_steps": (i32, [i32]),
         "spwgnn_host_device_ptr": (i32, [vp, C.POINTER(vp)]),
         "spwgnn_forward": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp]),
         "spwgnn_backward": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp, vp]),

@@ -1,4 +1,6 @@
 // C-ABI entry points of libspwgnn_hip.so: workspace layout and launch sequences.
+#include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
@@ -306,6 +308,30 @@ struct Prof {
 static bool rebuild_dA(const spwgnn_run* r, const spwgnn_batch* b) {
     const int m = kmath(r, kX6EdgeBwd);
     return b->nw_max <= 16 && m != MATH_F32 && !(m == MATH_X6 && !team_blocks(b->n_wtiles) && getenv_flag("SPWGNN_DA_RMW"));
+}
+
+// Stored dh1pre steps of that sum: on the wide x6 kernels the edge backward of steps
+// S−1 .. S−K also keeps its masked dh1pre_s, fragment-major, and k_dA_x6 reads those steps back instead
+// of repeating their dh2pre·W2ᵀ products (bitwise the same dA: same values, same order). The slabs are
+// dz4, dz3, dz2, dz1 — one chunk-major block (kCmBlk floats) per 32-edge block, exactly a stored
+// block's size — which nothing writes or reads between the previous backward's weight gradients and
+// this backward's relation-encoder pass, after k_dA_x6. K is spwgnn_da_stored_steps, clamped per call
+// to min(4, S−1): step 0 is always rebuilt (its edge backward may not run at all, §3zh).
+#ifndef SPWGNN_DA_STORED
+#define SPWGNN_DA_STORED 3   // same-box A/B at the headline batch: K = 3
+#endif
+static std::atomic<int> g_da_stored{SPWGNN_DA_STORED};
+int da_stored_steps(int set) {
+    return set >= 0 ? g_da_stored.exchange(set) : g_da_stored.load(std::memory_order_relaxed);
+}
+static bool bwd_fused_taken(const spwgnn_run* r, const spwgnn_batch* b);
+static int da_stored_planned(const spwgnn_run* r, const spwgnn_batch* b, const Ws& w) {
+    if (!rebuild_dA(r, b) || kmath(r, kX6EdgeBwd) != MATH_X6 || team_blocks(b->n_wtiles) || team_blocks(b->n_eblocks) ||
+        bwd_fused_taken(r, b))
+        return 0;
+    const int64_t step = w.dz3 - w.dz4;   // the four slabs at one stride, each a whole edge array
+    if (step < (int64_t)b->n_eblocks * kCmBlk || w.dz2 - w.dz3 != step || w.dz1 - w.dz2 != step) return 0;
+    return std::max(0, std::min({da_stored_steps(-1), 4, r->mp_steps - 1}));
 }
 
 // bf16 math (training) stores the encoder-side edge arrays that only ever feed MFMA operands — z2, z3,
@@ -814,6 +840,8 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
     const bool rebuild = rebuild_dA(r, b);
     const bool b16 = store_b16(r, b);
     const bool n16 = store_b16_node(r, b);
+    const int n_stored = da_stored_planned(r, b, w);   // steps S−1 .. S−n_stored keep their dh1pre (§3zi)
+    const int64_t slab_step = w.dz3 - w.dz4;
     const int64_t nN = b->n_nodes;
     const float scale = (r->dropout > 0.f) ? 1.0f / (1.0f - r->dropout) : 1.0f;
     // Loop-end shortcuts. A null prop is P0 = 0: step 0's rows add nothing to the
@@ -898,6 +926,7 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
         eb.dU = c.f(w.dU_at(s));
         eb.dV = c.f(w.dV_at(s));
         eb.n16 = n16;
+        eb.dh1_slab = S - 1 - s < n_stored ? c.f(w.dz4) + (S - 1 - s) * slab_step : nullptr;
         return eb;
     };
     NodeBwdArgs tl{};
@@ -933,6 +962,9 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
         da.dA = c.f(w.dA);
         da.x_w2t = c.x6(X6_W2T);
         da.b16 = b16;
+        da.n_stored = n_stored;
+        da.slab_step = slab_step;
+        da.slab = n_stored ? c.f(w.dz4) : nullptr;
     }
     EncEdgeBwdArgs eeb{};
     eeb.n_eblocks = b->n_eblocks;
@@ -1300,6 +1332,10 @@ int32_t spwgnn_host_device_ptr(const void* host, void** dev) {
 
 int32_t spwgnn_team_max_blocks(int32_t set) {
     return team_max_blocks(set);
+}
+
+int32_t spwgnn_da_stored_steps(int32_t set) {
+    return da_stored_steps(set);
 }
 
 int32_t spwgnn_forward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,

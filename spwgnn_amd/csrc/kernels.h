@@ -221,6 +221,8 @@ struct EdgeBwdArgs {
     float* dh2_out;    // dh2pre rows, chunk-major blocks (kCmBlk), for the W2 gradient
     const uint4* x_w2t; // x6 image of W2ᵀ (half rows, kh 76) — the LDS B operand (math == MATH_X6)
     int n16;           // bf16 math (training, wide kernels): dU, dV stored as bf16 (§3g, node side)
+    float* dh1_slab;   // x6, no_dA: this step's dh1pre kept for k_dA_x6, fragment-major (kCmBlk per block;
+                       // DESIGN.md §3zi); null = not kept
 };
 
 struct DaArgs {           // k_dA_x6: dA = Σ_s dh1pre_s, recomputed per 32-edge block
@@ -232,6 +234,11 @@ struct DaArgs {           // k_dA_x6: dA = Σ_s dh1pre_s, recomputed per 32-edge
     const float* G3;
     float* dA;                           // row-major [e][160]
     const uint4* x_w2t;
+    // x6 (k_dA_x6<3>): steps S−1 .. S−n_stored are not rebuilt but read back from the slabs their edge
+    // backward wrote (EdgeBwdArgs::dh1_slab): step S−1−k at slab + k·slab_step
+    int n_stored;
+    int64_t slab_step;
+    const float* slab;
 };
 
 struct EncEdgeBwdArgs {
@@ -447,6 +454,7 @@ hipError_t launch_tower_readout(const float* z, const int32_t* off, int n_towers
 constexpr int kTeamMaxBlocks = SPWGNN_TEAM_MAX_BLOCKS;
 bool team_blocks(int n_blocks);   // 32-row blocks of the launch (edge or node blocks)
 int team_max_blocks(int set);      // set >= 0: the new limit (returns the previous one); < 0: query
+int da_stored_steps(int set);      // stored dh1pre steps of the x6 dA sum (spwgnn_da_stored_steps), same form
 hipError_t launch_enc_node_team(const EncNodeArgs& a, int math, hipStream_t st);
 hipError_t launch_edge_fwd_team(const EdgeFwdArgs& a, int math, hipStream_t st);
 hipError_t launch_edge_bwd_team(const EdgeBwdArgs& a, int math, hipStream_t st);

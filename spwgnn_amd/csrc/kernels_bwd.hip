@@ -767,9 +767,38 @@ hipError_t launch_node_bwd(const NodeBwdArgs& a, int math, hipStream_t st) {
 #ifndef SPWGNN_DA_DBG
 #define SPWGNN_DA_DBG 0
 #endif
+// tile 4 of a stored dh1pre block: 24 lanes per half (features 128..151) at float4 1024 + (2·(r/4) + h)·24 + i
+constexpr int kSlabT4 = (2 * kKhE - 128), kSlabT4Base = 4 * 4 * 64;
+static_assert(kSlabT4Base + 8 * kSlabT4 == kCmBlk / 4, "a stored dh1pre block fills a chunk-major block exactly");
+// A stored block is written once and read once, 2.6 GB per stored step at the headline batch:
+// SPWGNN_SLAB_NT marks those accesses non-temporal (no L2 residency wanted beside the G3 gathers)
+#ifndef SPWGNN_SLAB_NT
+#define SPWGNN_SLAB_NT 1
+#endif
+typedef float slab_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void slab_store(float4* p, const float4& v) {
+#if SPWGNN_SLAB_NT
+    __builtin_nontemporal_store(slab_f4{v.x, v.y, v.z, v.w}, reinterpret_cast<slab_f4*>(p));
+#else
+    *p = v;
+#endif
+}
+__device__ __forceinline__ float4 slab_load(const float4* p) {
+#if SPWGNN_SLAB_NT
+    const slab_f4 v = __builtin_nontemporal_load(reinterpret_cast<const slab_f4*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+#else
+    return *p;
+#endif
+}
 // N16 (bf16 math, §3g node side): dU, dV stored as bf16
-template <bool ACCUM, bool NODA = false, int NP = 3, int DBG = 0, bool N16 = false>   // DBG 3 (diagnosis): G3 rows of the tile's first node
+// SLAB (x6, NODA): the step's masked dh1pre is also kept for k_dA_x6, which then reads
+// it back instead of repeating this step's product — plain float4 stores of the C fragments as they
+// lie in the registers (fragment-major: float4 (4t + r/4)·64 + lane of the block's kCmBlk floats, tile
+// 4's lanes i ≥ 24 — features past 151, always zero — left out), beside the one-hot MFMAs.
+template <bool ACCUM, bool NODA = false, int NP = 3, int DBG = 0, bool N16 = false, bool SLAB = false>   // DBG 3 (diagnosis): G3 rows of the tile's first node
 __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_edge_bwd_x6(EdgeBwdArgs a) {
+    static_assert(!SLAB || (NODA && NP == 3 && !N16), "stored dh1pre steps: the x6 rebuild form only");
     constexpr int PF = NP == 1 ? SPWGNN_EBWD_PF_B16 : SPWGNN_EBWD_PF, kWaves = 8;   // bf16: see k_dA_x6
     __shared__ uint4 wl[50 * 3 * 64];   // W2ᵀ x6 image: [kb·5 + T][part][lane]
     for (int idx = threadIdx.x; idx < 50 * 3 * 64; idx += blockDim.x) wl[idx] = a.x_w2t[idx];
@@ -908,6 +937,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             for (int r = 0; r < 16; ++r) acc[t][r] = mask_bit(acc[t][r], mh, rho(r, 0));
         }
         float* dArow = a.dA + (int64_t)blk * 32 * kLdE + i;
+        float4* slab4 = SLAB ? reinterpret_cast<float4*>(a.dh1_slab) + (int64_t)blk * (kCmBlk / 4) : nullptr;
 #if SPWGNN_ONEHOT_BPERM && SPWGNN_OH_KB >= 10
         build_oh();
 #endif
@@ -952,6 +982,14 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                     } else if (ACCUM) *p += acc[t][r];   // the wave owns the block: plain read-add-write
                     else *p = acc[t][r];
                 }
+                if constexpr (SLAB) {   // the same 8 registers as two fragment quads, 1 KiB per wave store
+#pragma unroll
+                    for (int q = 2 * s; q < 2 * s + 2; ++q) {
+                        const float4 v = make_float4(acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]);
+                        if (t < 4) slab_store(slab4 + (4 * t + q) * 64 + lane, v);
+                        else if (i < kSlabT4) slab_store(slab4 + kSlabT4Base + (q * 2 + h) * kSlabT4 + i, v);
+                    }
+                }
             }
         }
         cur = nxt;
@@ -977,6 +1015,8 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 }
 
 hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st) {
+    // a stored dh1pre step: the wide x6 rebuild form only (k_dA_x6<3> is its one reader)
+    if (a.dh1_slab && (math != MATH_X6 || a.nw_max > 16 || !a.no_dA || team_blocks(a.n_wtiles))) return hipErrorInvalidValue;
     if (math != MATH_F32 && a.nw_max <= 16 && a.no_dA && team_blocks(a.n_wtiles))   // small batches
         return a.n16 ? hipErrorInvalidValue : launch_edge_bwd_team(a, math, st);   // team kernels: fp32 dU/dV
     if (a.n16 && (math != MATH_BF16 || a.nw_max > 16 || !a.no_dA)) return hipErrorInvalidValue;
@@ -993,6 +1033,7 @@ hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st) {
 #endif
             if (math == MATH_BF16 && a.n16) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 1, 0, true>), g, b, 0, st, a);
             else if (math == MATH_BF16) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 1>), g, b, 0, st, a);
+            else if (a.dh1_slab) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 3, 0, false, true>), g, b, 0, st, a);
             else hipLaunchKernelGGL((k_edge_bwd_x6<false, true>), g, b, 0, st, a);
             return hipGetLastError();
         }
@@ -1032,8 +1073,16 @@ hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st) {
 // values), sums the steps in registers in the order the atomics did (S-1 first, then S-2 .. 0: the
 // same fp32 sums, bit-identical dA) and stores dA once with plain stores.
 // W2ᵀ (x6 image) is the LDS B operand; blocks are independent (no tile structure needed).
-template <int NP = 3, bool B16 = false>
+// SLAB (x6): the first n_stored steps of that order, S−1 .. S−n_stored, are not
+// rebuilt: their edge backward kept the masked dh1pre_s (k_edge_bwd_x6<SLAB>, same lane mapping), and a
+// block's sum starts with those values, read back 20 float4 per step and added in the same order to
+// the zeroed accumulators — the same fp32 sums, bit-identical dA. The (block, step) pairs of the
+// rebuild loop are then steps S−1−n_stored .. 0 of every block (step 0 is never stored: n_stored < S),
+// and the G3 ring carries over between those pairs as before; a block's stored steps are read ahead
+// of its first rebuilt pair, where the accumulators are zero and acc is free.
+template <int NP = 3, bool B16 = false, bool SLAB = false>
 __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_dA_x6(DaArgs a) {
+    static_assert(!SLAB || (NP == 3 && !B16), "stored dh1pre steps: x6 only");
     // bf16 math (NP = 1): a k-block is 5 MFMAs, so the G3 rows run further ahead to cover HBM latency
     constexpr int kWaves = 8, PF = NP == 1 ? SPWGNN_DA_PF_B16 : 2;
     static_assert(10 % PF == 0, "ring slots carry over between (block, step) pairs");
@@ -1100,7 +1149,8 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
         for (int c = 0; c < 2; ++c) r.g[c] = G4[64 * min(2 * kb + c, kKhE / 4 - 1)];
     };
-    int blk = b0, s = a.S - 1;
+    const int s_top = SLAB ? a.S - 1 - a.n_stored : a.S - 1;   // a block's first rebuilt step
+    int blk = b0, s = s_top;
     int d = a.edst[(int64_t)blk * 32 + i];
     Pair cur = load_pair(blk, s, d);
     KB ring[PF];
@@ -1108,12 +1158,44 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     for (int k = 0; k < PF; ++k) ld(cur.G4, k, ring[k]);
     f32x16 dacc[5];
     zero_tiles(dacc);
+    // dacc += the block's stored steps, S−1 first (tile 4's lanes i ≥ 24 are not stored: zeros)
+    auto slab_sum = [&](int sblk) {
+        const float4* sp = reinterpret_cast<const float4*>(a.slab) + (int64_t)sblk * (kCmBlk / 4);
+        for (int k = 0; k < a.n_stored; ++k, sp += a.slab_step / 4) {
+            // two groups of tiles (12 + 8 float4 in flight): all 20 at once spill beside dacc and the ring
+            auto part = [&](auto T0c, auto T1c) {
+                constexpr int T0 = decltype(T0c)::value, T1 = decltype(T1c)::value;
+                float4 v[T1 - T0][4];
+#pragma unroll
+                for (int t = T0; t < T1; ++t)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        if (t < 4) v[t - T0][q] = slab_load(sp + (4 * t + q) * 64 + lane);
+                        else v[t - T0][q] = i < kSlabT4 ? slab_load(sp + kSlabT4Base + (q * 2 + h) * kSlabT4 + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
+#pragma unroll
+                for (int t = T0; t < T1; ++t)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        dacc[t][4 * q + 0] += v[t - T0][q].x;
+                        dacc[t][4 * q + 1] += v[t - T0][q].y;
+                        dacc[t][4 * q + 2] += v[t - T0][q].z;
+                        dacc[t][4 * q + 3] += v[t - T0][q].w;
+                    }
+            };
+            part(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
+            part(std::integral_constant<int, 3>{}, std::integral_constant<int, 5>{});
+        }
+    };
     for (;;) {
+        if constexpr (SLAB) {
+            if (s == s_top) slab_sum(blk);   // a block's first pair: dacc is zero here
+        }
         // the next pair (steps S-1 .. 0 of a block, then the next block; clamped at the range end)
         const bool last_step = s == 0;
         const bool has_next = !last_step || blk + kStride < b1;
         const int nblk = last_step ? (blk + kStride < b1 ? blk + kStride : blk) : blk;
-        const int ns = last_step ? a.S - 1 : s - 1;
+        const int ns = last_step ? s_top : s - 1;
         const int nd = last_step ? a.edst[(int64_t)nblk * 32 + i] : d;
         const Pair nxt = load_pair(nblk, max(ns, 0), nd);
         const uint64_t mlo = h == 0 ? ((uint64_t)cur.w[1] << 32 | cur.w[0])
@@ -1196,11 +1278,15 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 }
 
 hipError_t launch_dA(const DaArgs& a, int math, hipStream_t st) {
+    if (a.n_stored > 0 && (math != MATH_X6 || team_blocks(a.n_eblocks))) return hipErrorInvalidValue;
     if ((math == MATH_X6 || math == MATH_BF16) && team_blocks(a.n_eblocks)) return launch_dA_team(a, math, st);
     const dim3 g(edge_grid(a.n_eblocks, 8)), b(512);
     if (math == MATH_BF16 && a.b16) hipLaunchKernelGGL((k_dA_x6<1, true>), g, b, 0, st, a);
     else if (math == MATH_BF16) hipLaunchKernelGGL((k_dA_x6<1>), g, b, 0, st, a);
-    else hipLaunchKernelGGL((k_dA_x6<3>), g, b, 0, st, a);
+    else if (a.n_stored > 0) {
+        if (a.n_stored >= a.S || !a.slab || a.b16) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_dA_x6<3, false, true>), g, b, 0, st, a);
+    } else hipLaunchKernelGGL((k_dA_x6<3>), g, b, 0, st, a);
     return hipGetLastError();
 }
 hipError_t launch_enc_edge_bwd(const EncEdgeBwdArgs& a, int math, hipStream_t st) {

@@ -195,6 +195,33 @@ class wide_kernels:
         return False
 
 
+DA_STORED_DEFAULT = 3   # the library's compile-time SPWGNN_DA_STORED
+
+
+def da_stored_steps(set_to: Optional[int] = None) -> int:
+    """The stored steps K of the dA sum on the wide x6 kernels (spwgnn_da_stored_steps): the edge backward
+    of the last K steps keeps its dh1pre and the dA kernel reads it back instead of repeating the product
+    (bitwise the same gradients at every K; clamped per call to min(4, mp_steps - 1)). With ``set_to``
+    (>= 0) it is changed for the process and the previous value is returned."""
+    return int(_lib.lib().spwgnn_da_stored_steps(-1 if set_to is None else int(set_to)))
+
+
+class da_stored:
+    """``with da_stored(k): ...`` — every backward planned inside keeps k dh1pre steps (see
+    da_stored_steps), then the previous value is restored."""
+
+    def __init__(self, k: int):
+        self._k = int(k)
+
+    def __enter__(self):
+        self._prev = da_stored_steps(self._k)
+        return self
+
+    def __exit__(self, *exc):
+        da_stored_steps(self._prev)
+        return False
+
+
 def forward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
             logits: Optional[torch.Tensor] = None) -> torch.Tensor:
     _require_gpu(flat_params, "params")
