@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 7   /* 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs; 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
@@ -206,6 +206,7 @@ typedef struct spwgnn_run {
 #define SPWGNN_K_WGRAD_WS 9    /* every stored-operand weight gradient (k_wgrad_ws family, split-bf16 maths) */
 #define SPWGNN_K_ENC_NODE 10
 #define SPWGNN_K_ENC_NODE_BWD 11
+#define SPWGNN_K_INPUT_BWD 12  /* spwgnn_backward_inputs' one launch */
 
 /* Workspace bytes for (n_nodes, n_eblocks, mp_steps, training). */
 int64_t spwgnn_workspace_bytes(int32_t n_nodes, int32_t n_eblocks, int32_t mp_steps, int32_t training);
@@ -247,6 +248,18 @@ int32_t spwgnn_forward(const float* params, const spwgnn_batch* batch, const spw
 int32_t spwgnn_backward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
                         void* workspace, int64_t workspace_bytes, const float* dlogits,
                         float* grads, float* dprop, spwgnn_stream_t stream);
+
+/* ABI 8. d(loss)/d(batch->pos) of the last spwgnn_backward / spwgnn_bce_backward on this workspace
+ * (same batch, same run; before the next forward on it): dpos [n_nodes][4] device fp32 (16-byte
+ * aligned), column 3 = 0, every row written, rows in the plan's node order. The gradient with respect
+ * to the objects rows (x, y, width)/170 of Networks.py:22: x and y through the relation encoder's
+ * input pos[receiver].xy - pos[sender].xy (Networks.py:58-62), y and width through the object
+ * encoder's (Networks.py:65-71). The relation set (a thresholded one included, main.py:71-81) is a
+ * constant of the graph and is NOT differentiated. One launch that streams the first encoder layers'
+ * pre-activation gradients the backward left in the workspace; sums in plan order without atomics
+ * (the same bits on every run). `params` is the flat buffer the forward ran with. */
+int32_t spwgnn_backward_inputs(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                               void* workspace, int64_t workspace_bytes, float* dpos, spwgnn_stream_t stream);
 
 /* Keras binary_crossentropy on sigmoid(logits) (Networks.py:102), mean over n:
  * out3 = {loss, sum of correct (binary_accuracy numerator), n}; dlogits = dloss/dlogit.

@@ -51,10 +51,11 @@ class RunC(C.Structure):
 
 
 K_EDGE_FWD, K_NODE_FWD, K_EDGE_BWD, K_NODE_BWD, K_ENC_EDGE, K_ENC_EDGE_BWD, K_WGRAD_W2, K_DA = 1, 2, 3, 4, 5, 6, 7, 8
-K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD = 9, 10, 11
+K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD, K_INPUT_BWD = 9, 10, 11, 12
 MATH_F32, MATH_X6, MATH_BF16 = 0, 1, 2
+E_ARG, E_WORKSPACE, E_NOTRAIN = -1, -4, -6   # SPWGNN_E_* statuses the bindings name
 STEP_KEY_COUNTER, STEP_KEY_SPLITMIX = 0, 1
-ABI_VERSION = 7        # SPWGNN_ABI_VERSION this binding's structs follow
+ABI_VERSION = 8        # SPWGNN_ABI_VERSION this binding's structs follow
 BATCH_RECV_BLOCKS = 1  # spwgnn_batch.flags: a receiver-block plan (spwgnn_plan_fill_recv)
 READOUT_SUM_PROB, READOUT_MEAN_PROB, READOUT_SUM_LOGIT, READOUT_MEAN_LOGIT = 0, 1, 2, 3
 
@@ -84,6 +85,7 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_host_device_ptr": (i32, [vp, C.POINTER(vp)]),
         "spwgnn_forward": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp]),
         "spwgnn_backward": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp, vp]),
+        "spwgnn_backward_inputs": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp]),
         "spwgnn_bce_scratch_bytes": (i64, [i64]),
         "spwgnn_bce": (i32, [vp, vp, i64, vp, vp, vp, vp]),
         "spwgnn_bce_accumulate": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp]),

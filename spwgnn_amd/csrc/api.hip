@@ -1362,6 +1362,37 @@ int32_t spwgnn_backward(const float* params, const spwgnn_batch* batch, const sp
                         static_cast<hipStream_t>(stream));
 }
 
+int32_t spwgnn_backward_inputs(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                               int64_t workspace_bytes, float* dpos, spwgnn_stream_t stream) {
+    int32_t stt = validate(batch, run);
+    if (stt) return stt;
+    if (!run->training) return SPWGNN_E_NOTRAIN;
+    if (!params || !workspace || !dpos || reinterpret_cast<uintptr_t>(dpos) % 16) return SPWGNN_E_ARG;
+    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, 1);
+    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const Ctx c{w, static_cast<char*>(workspace)};
+    const ParamTable& pt = param_table();
+    InputBwdArgs a{};
+    a.n_wtiles = batch->n_wtiles;
+    a.n_eblocks = batch->n_eblocks;
+    a.n_nodes = batch->n_nodes;
+    a.wtile = batch->wtile;
+    a.esrc = batch->edge_src;
+    a.edst = batch->edge_dst;
+    a.dz1 = c.f(w.dz1);     // the Y operands of the rm.0 / om.0 weight gradients (run_backward g_rm0, g_om0),
+    a.dzo1 = c.f(w.dzo1);   // as the backward left them
+    a.b16 = store_b16(run, batch);   // g_rm0's kB16Y
+    a.w_rm0 = params + pt.t[T_RM0K].offset;
+    a.w_om0 = params + pt.t[T_OM0K].offset;
+    a.dpos = reinterpret_cast<float4*>(dpos);
+    const Prof prof{run, st};
+    SPW_CHECK(prof.before(SPWGNN_K_INPUT_BWD));
+    SPW_CHECK(launch_input_bwd(a, st));
+    SPW_CHECK(prof.after(SPWGNN_K_INPUT_BWD));
+    return SPWGNN_OK;
+}
+
 int32_t spwgnn_bce_backward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
                             int64_t workspace_bytes, const float* logits, const float* targets, int64_t n,
                             float* out3, float* dlogits, void* bce_scratch, const double* weights3, double* total3,

@@ -445,6 +445,18 @@ hipError_t launch_sigmoid(const float* z, float* p, int64_t n, hipStream_t st);
 hipError_t launch_accumulate_out3(const float* out3, const double* w, double* tot, hipStream_t st);
 hipError_t launch_copy_in(const void* src, void* dst, int64_t n16, hipStream_t st);
 hipError_t launch_tower_readout(const float* z, const int32_t* off, int n_towers, int mode, float* out, hipStream_t st);
+// k_input_bwd (kernels_input.hip): d/d(pos) from the first encoder layers' pre-activation gradients
+struct InputBwdArgs {
+    int n_wtiles, n_eblocks, n_nodes;
+    const int32_t* wtile;            // [n_wtiles][4] first block, #blocks, first node, #nodes
+    const int32_t *esrc, *edst;      // [n_eblocks*32] global sender / receiver, -1 = padding
+    const float* dz1;                // chunk-major edge rows (kCmBlk per block); bf16 in that element order: b16
+    const float* dzo1;               // chunk-major node rows (kCmBlkN per 32-node block), fp32
+    const float *w_rm0, *w_om0;      // rm.0.kernel [2][150], om.0.kernel [2][100] in the flat parameters
+    float4* dpos;                    // [n_nodes] (d/dx, d/dy, d/dw, 0)
+    int b16;
+};
+hipError_t launch_input_bwd(const InputBwdArgs& a, hipStream_t st);
 
 // Team kernels (kernels_team.hip): one block per workgroup of waves that split each layer's output
 // tiles — the latency-bound small batches (the reference's batch 32) up to kTeamMaxBlocks blocks

@@ -54,6 +54,41 @@ def stability_sums(net: Net, towers_raw: np.ndarray, mode: str = "sum_prob") -> 
         return E.tower_readout(z, batch, mode)
 
 
+def stability_gradients(net: Net, towers_raw: np.ndarray, mode: str = "sum_prob") -> Tuple[torch.Tensor, torch.Tensor]:
+    """`stability_sums` plus its derivative: (sums (C,), grads (C, N, 3)) with grads[c, n] =
+    d sums[c] / d towers_raw[c, n] in raw-pixel units — which way to move (x, y) or resize (width) each
+    box to raise the readout, and which box's position the prediction hangs on. The continuous form of
+    the candidate searches above (`drop_to_demolish` refined by a gradient step).
+
+    One training forward with dropout 0 (the inference forward's values, with the activations kept),
+    one backward from d readout / d logit (σ'(z) for the "prob" modes, 1 for the "logit" modes, the
+    "mean" modes divided by N) and `engine.backward_inputs`; the chain rule through the /170
+    normalisation. The relation set is a constant: fully connected at inference, so nothing is lost."""
+    if mode not in E.READOUT_MODES:
+        raise ValueError(f"readout mode must be one of {sorted(E.READOUT_MODES)}")
+    g = _graph_net(net)
+    towers_raw = np.asarray(towers_raw, np.float64)
+    C_, N = towers_raw.shape[:2]
+    objects = (towers_raw / RELATION_THRESHOLD).astype(np.float32)
+    batch = TowerBatch.fully_connected(objects, device=g.device)
+    flat = g.flat.detach()
+    run = E.RunConfig(g.mp_steps, training=True, dropout=0.0)
+    ws = E.Workspace(g.device)
+    with torch.no_grad():
+        z = E.forward(flat, batch, run, ws)
+        sums = E.tower_readout(z, batch, mode)
+        if mode.endswith("prob"):
+            p = E.sigmoid(z)
+            dz = p * (1.0 - p)
+        else:
+            dz = torch.ones_like(z)
+        if mode.startswith("mean"):
+            dz = dz / N
+        E.backward(flat, batch, run, ws, dz)
+        dobj = E.backward_inputs(flat, batch, run, ws)
+        return sums, (dobj / RELATION_THRESHOLD).reshape(C_, N, 3)
+
+
 def remove_to_demolish(net: Net, boxes_raw: np.ndarray) -> Tuple[np.ndarray, int]:
     """Batched `JengaBuilder.remove_to_demolish` decision: (box_stabilities (n,), remove_index)."""
     sums = stability_sums(net, removal_candidates(boxes_raw)).cpu().numpy().astype(np.float64)

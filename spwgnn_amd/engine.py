@@ -113,7 +113,7 @@ class Prologue:
 
 
 # SPWGNN_POISON_WORKSPACE=1: fill every newly allocated workspace with 0xFF bytes (and the logits,
-# gradient and d/d'propagation' outputs with NaN), so a kernel that reads workspace it did not write,
+# gradient, d/d'propagation' and d/d'objects' outputs with NaN), so a kernel that reads workspace it did not write,
 # or leaves part of an output unwritten, turns results into NaN (run the GPU suite with it;
 # tests/test_gpu_determinism.py does the same per case)
 POISON_WORKSPACE = os.environ.get("SPWGNN_POISON_WORKSPACE", "0") not in ("", "0")
@@ -134,6 +134,7 @@ class Workspace:
         self.buf: Optional[torch.Tensor] = None
         self.fwd_key: Optional[tuple] = None   # what the last forward on this workspace stored
         self.fwd_batch = None                  # weakref to the batch that forward ran on
+        self.bwd_key: Optional[tuple] = None   # fwd_key once a backward of that forward has run (backward_inputs)
 
     @staticmethod
     def key(batch: TowerBatch, run: "RunConfig") -> tuple:
@@ -237,6 +238,7 @@ def forward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Wo
                                    logits.data_ptr(), _stream(batch.device))
     ws.fwd_key = Workspace.key(batch, run) if st == 0 else None
     ws.fwd_batch = weakref.ref(batch) if st == 0 else None
+    ws.bwd_key = None
     _lib.check(st, "spwgnn_forward")
     return logits
 
@@ -261,8 +263,31 @@ def backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: W
     st = _lib.lib().spwgnn_backward(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
                                     dlogits.data_ptr(), grads.data_ptr(), dprop.data_ptr() if dprop is not None else None,
                                     _stream(batch.device))
+    ws.bwd_key = ws.fwd_key if st == 0 else None
     _lib.check(st, "spwgnn_backward")
     return grads, dprop
+
+
+def backward_inputs(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace) -> torch.Tensor:
+    """d(loss)/d(objects) of the last `backward` / `bce_backward` on this workspace (spwgnn_backward_inputs,
+    ABI 8): (n_nodes, 3) fp32 — d/d(x, y, width) of the objects rows as the batch holds them (already
+    /170) — in the plan's node order (`TowerBatch.to_input_order` for packed plans), a view of the
+    library's (n_nodes, 4) output. One extra launch; the gradients `backward` returned are untouched.
+    The relation set (a thresholded one included) is a constant of the graph and is not differentiated."""
+    if not run.training:
+        _lib.check(_lib.E_NOTRAIN, "spwgnn_backward_inputs")
+    if not ws.holds(batch, run) or ws.bwd_key != ws.fwd_key:
+        raise _lib.SpwgnnError("backward_inputs needs the backward of the same batch and RunConfig on this workspace "
+                               "(it reads what that backward left there; a new forward discards it)")
+    _require_gpu(flat_params, "params")
+    dpos = _poison(torch.empty(batch.n_nodes, 4, dtype=torch.float32, device=batch.device))
+    b = batch.cstruct()
+    r = run.cstruct()
+    buf = ws.buf
+    st = _lib.lib().spwgnn_backward_inputs(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
+                                           dpos.data_ptr(), _stream(batch.device))
+    _lib.check(st, "spwgnn_backward_inputs")
+    return dpos[:, :3]
 
 
 def bce_backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace, logits: torch.Tensor,
@@ -296,6 +321,7 @@ def bce_backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, w
         targets.data_ptr(), logits.numel(), scratch.out3.data_ptr(), dlogits.data_ptr(), scratch.scratch.data_ptr(),
         weights3.data_ptr() if weights3 is not None else None, total3.data_ptr() if total3 is not None else None,
         grads.data_ptr(), dprop.data_ptr() if dprop is not None else None, _stream(batch.device))
+    ws.bwd_key = ws.fwd_key if st == 0 else None
     _lib.check(st, "spwgnn_bce_backward")
     return scratch.out3, dlogits, grads, dprop
 

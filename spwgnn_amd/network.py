@@ -18,22 +18,25 @@ from .batch import TowerBatch
 
 
 class _PropagationFn(torch.autograd.Function):
-    """Forward/backward of the whole graph through the C-ABI; gradients w.r.t. the flat
-    parameter buffer and the propagation input."""
+    """Forward/backward of the whole graph through the C-ABI; gradients w.r.t. the flat parameter
+    buffer, the propagation input and the objects (the (n_nodes, 3) rows in the plan's node order;
+    the relation set is a constant of the graph and is not differentiated)."""
 
     @staticmethod
-    def forward(ctx, flat, prop_dummy, batch: TowerBatch, run: E.RunConfig, ws: E.Workspace):
+    def forward(ctx, flat, prop_dummy, obj_dummy, batch: TowerBatch, run: E.RunConfig, ws: E.Workspace):
         logits = E.forward(flat, batch, run, ws)
         ctx.batch, ctx.run, ctx.ws = batch, run, ws
         ctx.save_for_backward(flat)
         ctx.want_prop = prop_dummy.requires_grad
+        ctx.want_obj = obj_dummy.requires_grad
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         (flat,) = ctx.saved_tensors
         grads, dprop = E.backward(flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop)
-        return grads, dprop, None, None, None
+        dobj = E.backward_inputs(flat, ctx.batch, ctx.run, ctx.ws) if ctx.want_obj else None
+        return grads, dprop, dobj, None, None, None
 
 
 class GraphNetwork(nn.Module):
@@ -63,8 +66,8 @@ class GraphNetwork(nn.Module):
         with torch.no_grad():
             self.flat.copy_(P.to_flat(params, device=self.flat.device))
 
-    def _run(self) -> E.RunConfig:
-        need_grad = torch.is_grad_enabled() and self.flat.requires_grad
+    def _run(self, input_grad: bool = False) -> E.RunConfig:
+        need_grad = torch.is_grad_enabled() and (self.flat.requires_grad or input_grad)
         drop = self.training and self.dropout > 0 and need_grad
         seed = 0
         if drop:
@@ -72,9 +75,17 @@ class GraphNetwork(nn.Module):
             seed = self._step_seed
         return E.RunConfig(self.mp_steps, training=need_grad, dropout=self.dropout if drop else 0.0, seed=seed)
 
-    def forward_batch(self, batch: TowerBatch, prop: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Logits (n_nodes,) for a compact batch (the reference returns sigmoid of these)."""
-        run = self._run()
+    def forward_batch(self, batch: TowerBatch, prop: Optional[torch.Tensor] = None,
+                      objects: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Logits (n_nodes,) for a compact batch (the reference returns sigmoid of these).
+
+        ``objects``: the torch tensor the batch's node rows were built from (n_nodes·3 elements, the
+        input's node order, any device / float dtype). The forward reads the batch's own copy; when
+        the tensor requires grad, backward also returns d/d objects into it (one extra launch,
+        `engine.backward_inputs`), in its own shape, device and dtype. The relation set — a
+        thresholded one included — is held constant: it is not differentiated."""
+        want_obj = objects is not None and torch.is_grad_enabled() and objects.requires_grad
+        run = self._run(want_obj)
         ws = E.Workspace(self.device)
         if prop is not None:
             batch = batch.with_prop(prop)
@@ -83,28 +94,38 @@ class GraphNetwork(nn.Module):
             dummy = prop.reshape(batch.n_nodes, 100)
         else:
             dummy = torch.zeros(0, device=self.device)
+        if want_obj:
+            # d/d objects arrives as (n_nodes, 3) in plan order: autograd maps it back through the
+            # gather (TowerBatch.to_input_order for packed plans), the device / dtype move and the reshape
+            odummy = batch.to_plan_order(objects.reshape(batch.n_nodes, 3).to(self.device, torch.float32))
+        else:
+            odummy = dummy.new_zeros(0)
         if not run.training:
             with torch.no_grad():
                 return E.forward(self.flat.detach(), batch, run, ws)
-        return _PropagationFn.apply(self.flat, dummy, batch, run, ws)
+        return _PropagationFn.apply(self.flat, dummy, odummy, batch, run, ws)
 
     def forward_logits(self, objects, sender_relations, receiver_relations, propagation=None) -> torch.Tensor:
+        """(B, N) logits. A torch ``objects`` that requires grad receives d/d objects (B, N, 3) on
+        backward (see `forward_batch`; the relations are constants)."""
         batch = TowerBatch.from_dense(objects, sender_relations, receiver_relations, None, device=self.device)
         prop = None
         if propagation is not None:
             prop = torch.as_tensor(propagation, dtype=torch.float32, device=self.device).reshape(batch.n_nodes, 100)
-        z = self.forward_batch(batch, prop)
+        z = self.forward_batch(batch, prop, objects if isinstance(objects, torch.Tensor) else None)
         return z.reshape(batch.node_shape)
 
     def forward(self, objects, sender_relations, receiver_relations, propagation=None) -> torch.Tensor:
-        """(B, N, 1) probabilities: sigmoid(x[:, :, :1]) of the last step (Networks.py:93-96)."""
+        """(B, N, 1) probabilities: sigmoid(x[:, :, :1]) of the last step (Networks.py:93-96);
+        differentiable in a torch ``objects`` like `forward_logits`."""
         return torch.sigmoid(self.forward_logits(objects, sender_relations, receiver_relations, propagation))[..., None]
 
     def forward_pooled(self, objects, sender_relations, receiver_relations, propagation=None,
                        mode: str = "mean_prob") -> torch.Tensor:
         """(B,) per-tower pooled output — the optional GlobalBlock-style readout (not in the
         reference): "mean_prob" / "sum_prob" (Σŷ of JengaBuilder.py:252-256) /
-        "mean_logit" / "sum_logit", reduced on device. Inference only (no autograd)."""
+        "mean_logit" / "sum_logit", reduced on device. Inference only (no autograd, a torch
+        ``objects`` included; `demolish.stability_gradients` gives d(readout)/d objects)."""
         batch = TowerBatch.from_dense(objects, sender_relations, receiver_relations, propagation, device=self.device)
         with torch.no_grad():
             z = E.forward(self.flat.detach(), batch, E.RunConfig(self.mp_steps, training=False), E.Workspace(self.device))
