@@ -73,7 +73,7 @@ static constexpr int kWsMinWgs = 32;
 #endif
 static constexpr int kWsSmallStages = SPWGNN_WS_SMALL_STAGES;
 // Diagnosis switches (A/B of superseded kernels, per-kernel math) exist only in -DSPWGNN_DIAG builds;
-// the shipping library has no environment-dependent code path.
+// the shipping library's one environment-dependent choice is SPWGNN_GATHER_PTR (gather_desc_ok below).
 static bool getenv_flag(const char* name) {
 #ifdef SPWGNN_DIAG
     const char* e = getenv(name);
@@ -165,6 +165,20 @@ static Ws make_ws(int64_t n_nodes, int64_t n_eblocks, int S, int training) {
     }
     w.total = cur * 4;
     return w;
+}
+
+// Range guard of the buffer-descriptor gathers: the edge-side kernels address a node
+// row by a 32-bit byte offset into one step's chunk-major array (U, V, G3: RN rows of kRowE floats), so
+// that array must stay below 2^31 bytes; larger batches take the 64-bit pointer form of the same
+// kernels. SPWGNN_GATHER_PTR (read per call: same-library A/B, tests) is a mask of kernels that take
+// the pointer form anyway: 1 the W2 gradient, 2 the edge forward, 4 the edge backward (7: all).
+enum : int { kGdW2 = 1, kGdEdgeFwd = 2, kGdEdgeBwd = 4 };
+static bool gather_desc_fits(int64_t rows_padded) {
+    return rows_padded * kRowE * (int64_t)sizeof(float) < (int64_t(1) << 31);
+}
+static bool gather_desc_ok(const Ws& w, int kernel) {
+    const char* e = getenv("SPWGNN_GATHER_PTR");
+    return gather_desc_fits(w.RN) && !((e ? atoi(e) : 0) & kernel);
 }
 
 // ---------------------------------------------------------------- weight packs ---------------
@@ -528,6 +542,8 @@ static int32_t run_forward(const float* params, const spwgnn_batch* b, const spw
                          b->n_eblocks == b->n_nodes && !getenv_flag("SPWGNN_RB_ONEHOT");
         ef.mask2 = r->training ? c.u(w.m2_at(s)) : nullptr;
         ef.uv_zero = s == 0 && zero_prop;
+        ef.gather_desc = gather_desc_ok(w, kGdEdgeFwd);
+        ef.node_bytes = (uint32_t)(ef.gather_desc ? w.RN * kRowE * 4 : 0);
         return ef;
     };
     auto node_args = [&](int s) {
@@ -649,6 +665,7 @@ struct WgSpec {
     bool recompute = false;   // XM_H1 / YM_DH2 context below
     int b16 = 0;              // kB16X / kB16Y: bf16-stored operands (bf16 math, store_b16)
     bool skip0 = false;       // k_wgrad_ws: step 0's X rows are exactly zero — its stages are left out
+    bool uv_zero = false;     // recompute: a null 'propagation' (U_0 = V_0 = 0)
     const float2* xd = nullptr;          // z1 rebuilt from d (k_wgrad_ws XD 1)
     const float4* xp = nullptr;          // zo1 rebuilt from the node positions (XD 2)
     const float *w0 = nullptr, *b0 = nullptr;
@@ -708,6 +725,8 @@ static int32_t run_wgrad(const Ctx& c, const spwgnn_batch* b, const WgSpec& g, f
         a.n_wtiles = b->n_wtiles;
         a.nw_max = b->nw_max;
         a.w2_tile = !getenv_flag("SPWGNN_W2G_GATHER");   // A/B switch: the per-edge gather kernel
+        a.gather_desc = gather_desc_ok(w, kGdW2);
+        a.uv_zero = g.uv_zero;
     }
     // stored chunk-major operands in x6 math: the warp-specialized kernel, one workgroup per CU
     if (math != MATH_F32 && g.xmode == XM_CM && (g.ymode == YM_CM || g.ymode == YM_ROW) &&
@@ -779,7 +798,9 @@ static int32_t run_wgrad(const Ctx& c, const spwgnn_batch* b, const WgSpec& g, f
         chunks = (nblk + bpw - 1) / bpw;
     }
     // a small x6 batch: the W2 gradient runs inside the batched weight-gradient launch
-    const bool w2_in_batch = ws && math == MATH_X6 && wsb && team_blocks(b->n_eblocks) && !getenv_flag("SPWGNN_NO_W2_MERGE");
+    // (the copy in the batched launch is the descriptor form: the pointer form runs as its own launch)
+    const bool w2_in_batch = ws && math == MATH_X6 && wsb && team_blocks(b->n_eblocks) && a.gather_desc &&
+                             !getenv_flag("SPWGNN_NO_W2_MERGE");
     if (prof && g.recompute && !w2_in_batch) SPW_CHECK(prof->before(SPWGNN_K_WGRAD_W2));
     if (w2_in_batch) {
         wsb->w2 = a;
@@ -927,6 +948,8 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
         eb.dV = c.f(w.dV_at(s));
         eb.n16 = n16;
         eb.dh1_slab = S - 1 - s < n_stored ? c.f(w.dz4) + (S - 1 - s) * slab_step : nullptr;
+        eb.gather_desc = gather_desc_ok(w, kGdEdgeBwd);
+        eb.node_bytes = (uint32_t)(eb.gather_desc ? w.RN * kRowE * 4 : 0);
         return eb;
     };
     NodeBwdArgs tl{};
@@ -1129,6 +1152,7 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
         g.x_count = g.y_count = g.rows = RE * S;
         g.recompute = true;
         g.b16 = (b16 ? kB16A : 0) | (n16 ? kB16UV : 0);   // U, V rows as the forward stored them (uv_storage)
+        g.uv_zero = zero_prop;
         return wg(g);
     };
     auto node_xy = [&](WgSpec& g, int64_t xoff, int xld, int xw, int xones, int64_t xstride, int64_t yoff, int yld,

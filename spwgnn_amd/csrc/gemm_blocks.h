@@ -197,6 +197,38 @@ __device__ __forceinline__ int64_t cm_index(int64_t row, int f) {
     return (row >> 5) * (KH * 64) + cm_offk<KH>((int)(row & 31), f);
 }
 
+// ---- node rows through buffer descriptors. The per-edge gathers of U_s[src],
+// V_s[dst] and G3_s[dst] read 16-byte (bf16 storage: 8-byte) pieces of a chunk-major row. A descriptor
+// over one step's array (wave-uniform: array + s·step) takes the lane's 32-bit byte offset of the row's
+// first piece; the chunk walked by the loop goes into the load's scalar offset, so a piece costs no
+// vector address arithmetic where a 64-bit pointer costs an add with carry. The host keeps the array
+// below 2^31 bytes (api.hip: gather_desc_ok) or selects the pointer form.
+// bytes = 0: every load returns zeros without touching memory (rows known to be zero).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t node_rows_rsrc(const void* step_base, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(step_base), (short)0, (int)bytes, 0x00020000);
+}
+// byte offset of feature 76h + c (c < 4) of node n's row; EB = bytes per stored element
+template <int EB>
+__device__ __forceinline__ int node_row_vo(int n, int h) {
+    return ((n >> 5) * kCmBlk + h * 128 + (n & 31) * 4) * EB;
+}
+// aux: the load's cache-policy bits (kBufNt: non-temporal, as ld_nt_*)
+#ifdef SPWGNN_NO_NT
+constexpr int kBufNt = 0;
+#else
+constexpr int kBufNt = 2;
+#endif
+template <int AUX = 0>
+__device__ __forceinline__ float4 buf_ld_f4(__amdgpu_buffer_rsrc_t r, int vo, int so) {
+    const auto u = __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, AUX);
+    return make_float4(__uint_as_float(u[0]), __uint_as_float(u[1]), __uint_as_float(u[2]), __uint_as_float(u[3]));
+}
+template <int AUX = 0>
+__device__ __forceinline__ uint2 buf_ld_u2(__amdgpu_buffer_rsrc_t r, int vo, int so) {
+    const auto u = __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, AUX);
+    return make_uint2(u[0], u[1]);
+}
+
 // ---- per-lane activation-sign bits of NT C-layout tiles (bit 16t + r of the lane's words), so a
 // backward pass in the same orientation reads 3 words per lane instead of the activations.
 // X must be ≥ +0 (post-relu): then X > 0 ⟺ its bit pattern is non-zero, min(bits, 1) is the bit.

@@ -163,6 +163,8 @@ struct EdgeFwdArgs {
     int uv16;          // how U, V were stored (store_cm_uv): kUvB16 exactly when n16 (the N16 kernel reads bf16)
     const uint4* x_w2; // x6 image of W2 (half rows, kh 76) — the LDS B operand (math == MATH_X6)
     int uv_zero;       // step 0 of a null 'propagation': the U, V rows are all zero (§3zh)
+    int gather_desc;   // 1: A, U, V rows through buffer descriptors (§3zk; the ≤ 16-node wide kernels)
+    uint32_t node_bytes;   // gather_desc: bytes of one step's fp32 node array (RN · kRowE · 4 < 2^31)
 };
 
 struct NodeFwdArgs {
@@ -223,6 +225,8 @@ struct EdgeBwdArgs {
     int n16;           // bf16 math (training, wide kernels): dU, dV stored as bf16 (§3g, node side)
     float* dh1_slab;   // x6, no_dA: this step's dh1pre kept for k_dA_x6, fragment-major (kCmBlk per block;
                        // DESIGN.md §3zi); null = not kept
+    int gather_desc;   // 1: G3 rows through a buffer descriptor (§3zk; the wide x6 / bf16 kernels)
+    uint32_t node_bytes;   // gather_desc: bytes of one step's G3 array (RN · kRowE · 4 < 2^31)
 };
 
 struct DaArgs {           // k_dA_x6: dA = Σ_s dh1pre_s, recomputed per 32-edge block
@@ -307,6 +311,8 @@ struct WgradArgs {
     const int32_t* wtile;          // the batch plan's wave-tiles (k_w2grad_tile walks whole tiles)
     int n_wtiles, nw_max;
     int w2_tile;                   // 1: the W2 gradient with LDS-staged node rows (bf16 math)
+    int gather_desc;               // 1: U, V, G3 rows through buffer descriptors (each step's array < 2^31 bytes)
+    int uv_zero;                   // 1: a null 'propagation' — U_0 = V_0 = 0, step 0's stages need not read them
     float* slab;           // [chunks][kx_pad][ny_pad]
 };
 struct WgWsArgs {          // k_wgrad_ws: stages (s, nb) of a [S][nbs] grid of 32-row blocks

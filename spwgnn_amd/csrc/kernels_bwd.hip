@@ -796,7 +796,10 @@ __device__ __forceinline__ float4 slab_load(const float4* p) {
 // it back instead of repeating this step's product — plain float4 stores of the C fragments as they
 // lie in the registers (fragment-major: float4 (4t + r/4)·64 + lane of the block's kCmBlk floats, tile
 // 4's lanes i ≥ 24 — features past 151, always zero — left out), beside the one-hot MFMAs.
-template <bool ACCUM, bool NODA = false, int NP = 3, int DBG = 0, bool N16 = false, bool SLAB = false>   // DBG 3 (diagnosis): G3 rows of the tile's first node
+// DESC (§3zk): the G3 rows through a buffer descriptor — a lane keeps the 32-bit byte offset of its
+// receiver's row and the chunk goes into the load's scalar offset (no 64-bit add per piece)
+template <bool ACCUM, bool NODA = false, int NP = 3, int DBG = 0, bool N16 = false, bool SLAB = false,   // DBG 3 (diagnosis): G3 rows of the tile's first node
+          bool DESC = false>
 __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_edge_bwd_x6(EdgeBwdArgs a) {
     static_assert(!SLAB || (NODA && NP == 3 && !N16), "stored dh1pre steps: the x6 rebuild form only");
     constexpr int PF = NP == 1 ? SPWGNN_EBWD_PF_B16 : SPWGNN_EBWD_PF, kWaves = 8;   // bf16: see k_dA_x6
@@ -817,19 +820,27 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         load_m2(a.mask2 + (int64_t)blk * kM2Blk, i, p.w);
         return p;
     };
+    struct GRow { const float4* p; int vo; };   // a receiver's G3 row: pointer, or (DESC) byte offset
+    const auto rG = node_rows_rsrc(a.G3, a.node_bytes);
     auto g_of = [&](int d, int n0) {
-        return reinterpret_cast<const float4*>(a.G3 + cm_index<kKhE>(DBG == 3 ? n0 : (d >= 0 ? d : n0), 0) + h * 128);
+        const int n = DBG == 3 ? n0 : (d >= 0 ? d : n0);
+        if constexpr (DESC) return GRow{nullptr, node_row_vo<4>(n, h)};
+        else return GRow{reinterpret_cast<const float4*>(a.G3 + cm_index<kKhE>(n, 0) + h * 128), 0};
     };
     struct KB { float4 g[2]; };
-    auto ld = [&](const float4* G4, int kb, KB& r) {
+    auto ld = [&](const GRow& G4, int kb, KB& r) {
 #pragma unroll
-        for (int c = 0; c < 2; ++c) r.g[c] = G4[64 * min(2 * kb + c, kKhE / 4 - 1)];
+        for (int c = 0; c < 2; ++c) {
+            const int q = min(2 * kb + c, kKhE / 4 - 1);
+            if constexpr (DESC) r.g[c] = buf_ld_f4(rG, G4.vo, 1024 * q);
+            else r.g[c] = G4.p[64 * q];
+        }
     };
     int wt = blockIdx.x * kWaves + wave;
     if (wt >= a.n_wtiles) return;
     int4 info = wtiles[wt];
     Pre cur = load_pre(info.x);
-    const float4* G4 = g_of(cur.d, info.z);
+    GRow G4 = g_of(cur.d, info.z);
     KB ring[PF];
 #pragma unroll
     for (int k = 0; k < PF; ++k) ld(G4, k, ring[k]);
@@ -856,7 +867,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         const uint64_t mlo = h == 0 ? ((uint64_t)w[1] << 32 | w[0])
                                     : ((uint64_t)w[4] << 52 | (uint64_t)w[3] << 20 | (w[2] >> 12));
         const uint32_t mhi = h == 0 ? (w[2] & 0xfffu) : (w[4] >> 12);
-        const float4* NG4 = nullptr;
+        GRow NG4{nullptr, 0};
         // one-hot [node row][edge]: element e of half h ↔ edge rho(8s + e, h)
         const int s_ = cur.s;
         uint32_t oh2[2][4];
@@ -1031,6 +1042,13 @@ hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st) {
                 return hipGetLastError();
             }
 #endif
+            if (a.gather_desc) {   // G3 rows through a buffer descriptor (§3zk)
+                if (math == MATH_BF16 && a.n16) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 1, 0, true, false, true>), g, b, 0, st, a);
+                else if (math == MATH_BF16) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 1, 0, false, false, true>), g, b, 0, st, a);
+                else if (a.dh1_slab) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 3, 0, false, true, true>), g, b, 0, st, a);
+                else hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 3, 0, false, false, true>), g, b, 0, st, a);
+                return hipGetLastError();
+            }
             if (math == MATH_BF16 && a.n16) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 1, 0, true>), g, b, 0, st, a);
             else if (math == MATH_BF16) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 1>), g, b, 0, st, a);
             else if (a.dh1_slab) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 3, 0, false, true>), g, b, 0, st, a);

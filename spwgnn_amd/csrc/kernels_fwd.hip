@@ -1008,8 +1008,11 @@ struct NodeSum16X6 {
 // instead of 4 at one per SIMD with a 5-k-block ring
 // N16: H2s stored as bf16 (bf16 math, §3o)
 // UV0 (step 0 of a null 'propagation', EdgeFwdArgs::uv_zero): U = V = 0 — h1 = relu(A + 0), no gathers
+// DESC (§3zk): the A rows and the gathered U, V rows through buffer descriptors — the block's A base
+// and the node arrays are wave-uniform, a lane keeps one 32-bit offset per row and the chunk goes
+// into the load's scalar offset (the pointer form adds 64·q·16 bytes to a 64-bit pointer per piece)
 template <bool NW16, int DBG = 0, int NP = 3, bool AB16 = false, bool W8 = false, bool N16 = false,   // AB16: A stored as bf16 (§3g)
-          bool UV0 = false>
+          bool UV0 = false, bool DESC = false>
 __global__ __launch_bounds__((NW16 || W8) ? 512 : 256, 1) __attribute__((amdgpu_waves_per_eu((NW16 || W8) ? 2 : 1, (NW16 || W8) ? 2 : 1)))
 void k_edge_fwd_x6(EdgeFwdArgs a) {
     // bf16 math (NP = 1): a k-block is 5 MFMAs, too short to cover a load one k-block ahead
@@ -1031,7 +1034,10 @@ void k_edge_fwd_x6(EdgeFwdArgs a) {
     // a block's h1 operand sources: A rows and the gathered U[s], V[r] rows (chunk q at +256q / +64q)
     // N16: U, V stored as bf16 (kUvB16, §3ze) — 8-byte pieces at the fp32 element index, unpacked at use
     using UVT = typename std::conditional<N16, uint2, float4>::type;
-    struct Src { int64_t ai; const UVT *U, *V; };   // ai: element index of the A rows
+    struct Src { int64_t ai; const UVT *U, *V; int ab, vu, vv; };   // ai: element index of the A rows
+    constexpr int EBA = AB16 ? 2 : 4, EBU = N16 ? 2 : 4;            // DESC: ab the A block, vu / vv the rows' byte offsets
+    const auto rU = node_rows_rsrc(a.U, a.node_bytes / (4 / EBU)), rV = node_rows_rsrc(a.V, a.node_bytes / (4 / EBU));
+    const int voA = (h * 128 + i * 4) * EBA;
     auto uv_at = [&](const float* base, int node) {
         const int64_t e = cm_index<kKhE>(node, 0) + h * 128;
         if constexpr (N16) return reinterpret_cast<const UVT*>(reinterpret_cast<const uint16_t*>(base) + e);
@@ -1039,18 +1045,24 @@ void k_edge_fwd_x6(EdgeFwdArgs a) {
     };
     auto src_of = [&](int blk, int2 sd, int n0) {
         const int sc = DBG == 3 ? n0 : (sd.x >= 0 ? sd.x : n0), dc = DBG == 3 ? n0 : (sd.x >= 0 ? sd.y : n0);
-        return Src{(int64_t)(DBG == 1 ? (blk & 7) : blk) * kCmBlk + h * 128 + i * 4, uv_at(a.U, sc), uv_at(a.V, dc)};
+        if constexpr (DESC) return Src{0, nullptr, nullptr, DBG == 1 ? (blk & 7) : blk, node_row_vo<EBU>(sc, h), node_row_vo<EBU>(dc, h)};
+        else return Src{(int64_t)(DBG == 1 ? (blk & 7) : blk) * kCmBlk + h * 128 + i * 4, uv_at(a.U, sc), uv_at(a.V, dc), 0, 0, 0};
     };
     // k-block kb = chunks 2kb, 2kb+1 (chunk 19 does not exist: clamped, its W2 rows are zero)
     // (bf16 pieces stay packed in the ring and are unpacked where they are used)
     using AT = typename std::conditional<AB16, uint2, float4>::type;
     struct KA { AT a[2]; };
     struct KU { UVT u[2], v[2]; };
-    auto ldA = [&](int64_t ai, int kb, KA& r) {
+    auto ldA = [&](int64_t ai, int ab, int kb, KA& r) {
+        const auto rA = node_rows_rsrc(reinterpret_cast<const char*>(a.A) + (int64_t)ab * (kCmBlk * EBA), kCmBlk * EBA);
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const int q = min(2 * kb + c, kKhE / 4 - 1);
-            if constexpr (AB16)
+            if constexpr (DESC && AB16)
+                r.a[c] = buf_ld_u2<kBufNt>(rA, voA, 256 * q * EBA);
+            else if constexpr (DESC)
+                r.a[c] = buf_ld_f4<kBufNt>(rA, voA, 256 * q * EBA);
+            else if constexpr (AB16)
                 r.a[c] = ld_nt_u2(reinterpret_cast<const uint16_t*>(a.A) + ai + 256 * q);
             else
                 r.a[c] = ld_nt_f4(a.A + ai + 256 * q);
@@ -1061,8 +1073,16 @@ void k_edge_fwd_x6(EdgeFwdArgs a) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const int q = min(2 * kb + c, kKhE / 4 - 1);
-            r.u[c] = sr.U[64 * q];
-            r.v[c] = sr.V[64 * q];
+            if constexpr (DESC && N16) {
+                r.u[c] = buf_ld_u2(rU, sr.vu, 256 * q * EBU);
+                r.v[c] = buf_ld_u2(rV, sr.vv, 256 * q * EBU);
+            } else if constexpr (DESC) {
+                r.u[c] = buf_ld_f4(rU, sr.vu, 256 * q * EBU);
+                r.v[c] = buf_ld_f4(rV, sr.vv, 256 * q * EBU);
+            } else {
+                r.u[c] = sr.U[64 * q];
+                r.v[c] = sr.V[64 * q];
+            }
         }
     };
     int wt = blockIdx.x * kWaves + wave;
@@ -1076,7 +1096,7 @@ void k_edge_fwd_x6(EdgeFwdArgs a) {
     KU ringU[kX6Pf];
 #pragma unroll
     for (int k = 0; k < kPfA; ++k) {
-        ldA(cur.ai, k, ringA[k]);
+        ldA(cur.ai, cur.ab, k, ringA[k]);
         if (k < kX6Pf) ldUV(cur, k, ringU[k]);
     }
     for (; wt < a.n_wtiles; wt += wstep) {
@@ -1118,8 +1138,8 @@ void k_edge_fwd_x6(EdgeFwdArgs a) {
             uint32_t hw[4], mw[4], lw[4];
 #pragma unroll
             for (int m = 0; m < 4; ++m) split2(xv[2 * m], xv[2 * m + 1], hw[m], mw[m], lw[m]);
-            if (kb + kPfA < 10) ldA(cur.ai, kb + kPfA, ca);
-            else ldA(nai, kb + kPfA - 10, ca);
+            if (kb + kPfA < 10) ldA(cur.ai, cur.ab, kb + kPfA, ca);
+            else ldA(nai, DBG == 1 ? (nblk & 7) : nblk, kb + kPfA - 10, ca);
             if (kb + kX6Pf < 10) {
                 ldUV(cur, kb + kX6Pf, cu);
             } else {
@@ -1483,6 +1503,13 @@ hipError_t launch_enc_edge(const EncEdgeArgs& a, int math, hipStream_t st) {
 #define SPWGNN_EFWD_UV0 1
 #endif
 constexpr bool kEfwdUv0 = SPWGNN_EFWD_UV0 != 0;
+// the ≤ 16-node wide forms: buffer-descriptor loads (EdgeFwdArgs::gather_desc) or 64-bit pointers
+template <int NP, bool AB16, bool N16, bool UV0>
+static void launch_edge_fwd16(const EdgeFwdArgs& a, hipStream_t st) {
+    const dim3 g(edge_grid(a.n_wtiles, 8)), b(512);
+    if (a.gather_desc) hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, NP, AB16, false, N16, UV0, true>), g, b, 0, st, a);
+    else hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, NP, AB16, false, N16, UV0, false>), g, b, 0, st, a);
+}
 hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
     if (a.nw_max > kNwMaxLimit) return hipErrorInvalidValue;  // one-hot rows: ≤ 32 nodes per wave-tile
     if ((a.uv16 == kUvB16) != (a.n16 != 0)) return hipErrorInvalidValue;   // bf16 U, V: the N16 kernel reads them
@@ -1502,10 +1529,8 @@ hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
             return hipGetLastError();
         }
 #endif
-        if (kEfwdUv0 && a.uv_zero)
-            hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, 1, true, false, true, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
-        else
-            hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, 1, true, false, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
+        if (kEfwdUv0 && a.uv_zero) launch_edge_fwd16<1, true, true, true>(a, st);
+        else launch_edge_fwd16<1, true, true, false>(a, st);
         return hipGetLastError();
     }
     if (math == MATH_BF16) {
@@ -1521,13 +1546,13 @@ hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
         }
 #endif
         if (a.nw_max <= 16 && a.a_b16 && kEfwdUv0 && a.uv_zero)
-            hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, 1, true, false, false, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
+            launch_edge_fwd16<1, true, false, true>(a, st);
         else if (a.nw_max <= 16 && a.a_b16)
-            hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, 1, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
+            launch_edge_fwd16<1, true, false, false>(a, st);
         else if (a.a_b16)
             return hipErrorInvalidValue;
         else if (a.nw_max <= 16)
-            hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, 1>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
+            launch_edge_fwd16<1, false, false, false>(a, st);
         else
             hipLaunchKernelGGL((k_edge_fwd_x6<false, 0, 1>), dim3(edge_grid(a.n_wtiles, 4)), dim3(256), 0, st, a);
         return hipGetLastError();
@@ -1555,9 +1580,9 @@ hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
             hipLaunchKernelGGL((k_edge_fwd_x6<true, 2>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
 #endif
         else if (a.nw_max <= 16 && kEfwdUv0 && a.uv_zero)
-            hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, 3, false, false, false, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
+            launch_edge_fwd16<3, false, false, true>(a, st);
         else if (a.nw_max <= 16)
-            hipLaunchKernelGGL(k_edge_fwd_x6<true>, dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
+            launch_edge_fwd16<3, false, false, false>(a, st);
         else   // ≤ 32-node tiles: two waves per SIMD (config 5: 37.5 -> 34.4 ms per forward, A/B on one box;
                // 36 spilled registers, an inference-only instantiation without the mask code spills 612)
             hipLaunchKernelGGL((k_edge_fwd_x6<false, 0, 3, false, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);

@@ -542,6 +542,10 @@ __global__ __launch_bounds__(kWgThreads, OCC) void k_wgrad_x6(WgradArgs a) {
 // other LDS buffer, so the matrix pipe runs while the staging VALU work issues in its gaps.
 // One barrier per stage; deterministic (fixed ranges and order).
 constexpr int kW2gThreads = 512;
+// descriptor form: the gather's loads spread between the build's column groups (A/B build option)
+#ifndef SPWGNN_W2G_SPREAD
+#define SPWGNN_W2G_SPREAD 1
+#endif
 constexpr int kW2gImg = 3 * X6Img<160>::PART;   // one operand's split image (30 KB)
 
 // A rows of 32-edge block b (fp32, or bf16 at the fp32 element index) through a buffer descriptor
@@ -572,7 +576,9 @@ struct W2gSet {
 
 // DBG (diagnosis builds, SPWGNN_W2G_DBG): 1 no MFMAs, 2 gathers from stage 0, 4 no staging
 // arithmetic, 8 matrix waves at s_setprio 1, 32 no gathers
-template <int dbg, int NP = 3, bool AB16 = false>   // AB16: A stored as bf16 (bf16 math, §3g)
+// DESC: U, V, G3 rows through per-step buffer descriptors, the lane's node offsets and the block's
+// src / dst read once per 32-edge block (§3zk); false: per-stage 64-bit pointers (arrays ≥ 2^31 bytes)
+template <int dbg, int NP = 3, bool AB16 = false, bool DESC = true>   // AB16: A stored as bf16 (bf16 math, §3g)
 __device__ __forceinline__ void w2grad_ws_body(const WgradArgs& a, int64_t blk_per_wg, int bid,
                                                char (*buf)[2 * kW2gImg]) {   // [stage parity][X | Y]
     using IM = X6Img<160>;
@@ -684,12 +690,11 @@ __device__ __forceinline__ void w2grad_ws_body(const WgradArgs& a, int64_t blk_p
             R.m[k] = mw[k];
         }
     };
-    auto build = [&](const W2gSet& R, char* Xs) {
+    auto build_k = [&](const W2gSet& R, char* Xs, int k) {   // column group k of a stage
         if constexpr ((dbg & 4) != 0) return;
         char* Ys = Xs + kW2gImg;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            if (k == 4 && !k4ok) break;
+        {
+            if (k == 4 && !k4ok) return;
             float4 x = f4relu(f4add3(AB16 ? unpack4_bf16(R.ah[k]) : R.a[k], R.u[k], R.v[k]));
             if (k == 4 && c0 == 5) x.z = 1.f;   // feature 150: the b2 ones column
             // dh2pre = G3 ⊙ [h2 > 0]: sign-extended single-bit fields as AND masks
@@ -704,6 +709,10 @@ __device__ __forceinline__ void w2grad_ws_body(const WgradArgs& a, int64_t blk_p
             IM::template put<NP>(Ys, rr, c0 + 8 * k, y);
         }
     };
+    auto build = [&](const W2gSet& R, char* Xs) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) build_k(R, Xs, k);
+    };
     if (T == 0) {
         __syncthreads();
         return;
@@ -716,6 +725,110 @@ __device__ __forceinline__ void w2grad_ws_body(const WgradArgs& a, int64_t blk_p
         }
     }
     W2gSet R0, R1;
+    if constexpr (DESC) {
+        // chunk c0 + 8k of a row sits at a wave-uniform distance from chunk c0 for k = 1, 3, 4 (scalar
+        // offsets); chunk c0 + 16 straddles the row's two halves within staging wave 1 (a lane offset)
+        static_assert(cm_offk<kKhE>(0, 4 * 8) == 2048 && cm_offk<kKhE>(0, 4 * (7 + 8)) - cm_offk<kKhE>(0, 4 * 7) == 2048 &&
+                      cm_offk<kKhE>(0, 4 * 24) == 1408 && cm_offk<kKhE>(0, 4 * (7 + 24)) - cm_offk<kKhE>(0, 4 * 7) == 1408 &&
+                      cm_offk<kKhE>(0, 4 * 32) == 3456 && cm_offk<kKhE>(0, 4 * (5 + 32)) - cm_offk<kKhE>(0, 4 * 5) == 3456,
+                      "chunk-major distances of a staging lane's column groups");
+        const int so1 = 2048 * 4, so3 = 1408 * 4, so4 = k4ok ? 3456 * 4 : 0;
+        const int d2 = (off[2] - off[0]) * 4;
+        const uint32_t step_bytes = (uint32_t)(nstep_n * 4);
+        // the block whose stages are being gathered: the lane's offsets of chunk c0 (and c0 + 16) of
+        // U_s[src] (vs) and V_s[dst], G3_s[dst] (vd) within a step's array; padding edges read row 0
+        int vs = 0, vs2 = 0, vd = 0, vd2 = 0, vin = 0;
+        int64_t fb = b0;      // block and step of the next gather; nidx: the indices of block fb + 1
+        int fs = 0, ft = 0;   //   (of block fb while fs == 0 has not been gathered yet)
+        int2 nidx = make_int2(a.esrc[32 * b0 + rr], a.edst[32 * b0 + rr]);
+        struct Desc { __amdgpu_buffer_rsrc_t rU, rV, rG, rA; };
+        auto gather_head = [&](W2gSet& R) {   // the stage's descriptors; its h2 > 0 words
+            if (fs == 0) {   // wave-uniform: a new block, once per S stages
+                vin = nidx.x >= 0;
+                const int sn = vin ? nidx.x : 0, dn = vin ? nidx.y : 0;
+                vs = node_row_vo<4>(sn, 0) + off[0] * 4;
+                vd = node_row_vo<4>(dn, 0) + off[0] * 4;
+                vs2 = vs + d2;
+                vd2 = vd + d2;
+                const int64_t nb = min(fb + 1, b1 - 1);
+                nidx = make_int2(a.esrc[32 * nb + rr], a.edst[32 * nb + rr]);
+            }
+            const int64_t ns = (int64_t)fs * nstep_n;
+            // a null 'propagation': U_0 = V_0 = 0 — zero-length descriptors return the zeros unread
+            const uint32_t uvb = (a.uv_zero && fs == 0) ? 0u : step_bytes;
+            const auto rU = node_rows_rsrc(a.U + ns, uvb), rV = node_rows_rsrc(a.V + ns, uvb);
+            const auto rG = node_rows_rsrc(a.G3 + ns, step_bytes);
+            const auto rA = w2_rows_rsrc<AB16>(a.A, fb);
+            load_m2(a.mask2 + ((int64_t)fs * nblk + fb) * kM2Blk, rr, R.m);
+            R.in = vin;
+            return Desc{rU, rV, rG, rA};
+        };
+        auto gather_k = [&](const Desc& d, W2gSet& R, int k) {   // column group k: A, U, V, G3 pieces
+            const int so = k == 1 ? so1 : (k == 3 ? so3 : (k == 4 ? so4 : 0));
+            w2_row_load<AB16>(d.rA, voa[k], R.ah[k], R.a[k]);   // re-read by the block's next steps
+            R.u[k] = buf_ld_f4(d.rU, k == 2 ? vs2 : vs, so);
+            R.v[k] = buf_ld_f4(d.rV, k == 2 ? vd2 : vd, so);
+            R.g[k] = buf_ld_f4(d.rG, k == 2 ? vd2 : vd, so);
+        };
+        auto gather_tail = [&]() {
+            if constexpr ((dbg & 2) != 0) return;   // every gather from stage 0
+            if (++ft < T && ++fs == S) {             // past the end: the last stage again (unused)
+                fs = 0;
+                ++fb;
+            }
+        };
+        auto gather = [&](W2gSet& R) {
+            if constexpr ((dbg & 32) != 0) return;
+            const Desc d = gather_head(R);
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                gather_k(d, R, k);
+#if SPWGNN_W2G_SPREAD   // the loop's load order, so that its waits count the same loads on every path into it
+                __builtin_amdgcn_sched_barrier(0);
+#endif
+            }
+            gather_tail();
+        };
+        // one loop half: gather the stage two ahead into Rg while stage one ahead is built from Rb,
+        // the gather's loads issued a column group at a time between the build's groups (issued in one
+        // burst after the barrier they queue behind the other staging waves' and stall the wave)
+        auto gather_build = [&](W2gSet& Rg, const W2gSet& Rb, char* Xs) {
+#if SPWGNN_W2G_SPREAD
+            if constexpr ((dbg & 32) != 0) { build(Rb, Xs); return; }
+            const Desc d = gather_head(Rg);
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                gather_k(d, Rg, k);
+                __builtin_amdgcn_sched_barrier(0);
+                build_k(Rb, Xs, k);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            gather_tail();
+#else
+            gather(Rg);
+            build(Rb, Xs);
+#endif
+        };
+        gather(R0);
+        gather(R1);
+        build(R0, buf[0]);
+        __syncthreads();   // stage 0 staged
+        // iteration t: gather stage t+2 (set t&1), build stage t+1 (set (t+1)&1) into buffer (t+1)&1,
+        // barrier. A block's indices were loaded S gathers before the gather that turns them into offsets.
+        int t = 0;
+        for (; t + 2 < T; t += 2) {
+            gather_build(R0, R1, buf[1]);
+            __syncthreads();
+            gather_build(R1, R0, buf[0]);
+            __syncthreads();
+        }
+        if (t + 1 < T) {   // t even: build stage t+1 from set 1
+            build(R1, buf[1]);
+            __syncthreads();
+        }
+        __syncthreads();   // the matrix waves' last stage
+        return;
+    }
     int2 i0, i1;
     load_idx(0, i0);
     load_idx(1, i1);
@@ -745,11 +858,11 @@ __device__ __forceinline__ void w2grad_ws_body(const WgradArgs& a, int64_t blk_p
     }
     __syncthreads();   // the matrix waves' last stage
 }
-template <int dbg, int NP = 3, bool AB16 = false>
+template <int dbg, int NP = 3, bool AB16 = false, bool DESC = true>
 __global__ __launch_bounds__(kW2gThreads, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_w2grad_ws(WgradArgs a, int64_t blk_per_wg) {
     __shared__ __attribute__((aligned(16))) char buf[2][2 * kW2gImg];
-    w2grad_ws_body<dbg, NP, AB16>(a, blk_per_wg, blockIdx.x, buf);
+    w2grad_ws_body<dbg, NP, AB16, DESC>(a, blk_per_wg, blockIdx.x, buf);
 }
 
 // W2 gradient with the node rows staged in LDS per (wave-tile, step) — bf16 math. The per-edge
@@ -1869,13 +1982,16 @@ hipError_t launch_w2grad_ws(const WgradArgs& a, int wgs, int64_t blk_per_wg, int
             return hipGetLastError();
         }
         if (a.uv16) return hipErrorInvalidValue;   // bf16 U, V rows: the tile kernel only
-        if (a.a_b16) hipLaunchKernelGGL((k_w2grad_ws<0, 1, true>), g, b, 0, st, a, blk_per_wg);
-        else hipLaunchKernelGGL((k_w2grad_ws<0, 1>), g, b, 0, st, a, blk_per_wg);
+        if (a.a_b16 && a.gather_desc) hipLaunchKernelGGL((k_w2grad_ws<0, 1, true>), g, b, 0, st, a, blk_per_wg);
+        else if (a.a_b16) hipLaunchKernelGGL((k_w2grad_ws<0, 1, true, false>), g, b, 0, st, a, blk_per_wg);
+        else if (a.gather_desc) hipLaunchKernelGGL((k_w2grad_ws<0, 1>), g, b, 0, st, a, blk_per_wg);
+        else hipLaunchKernelGGL((k_w2grad_ws<0, 1, false, false>), g, b, 0, st, a, blk_per_wg);
         return hipGetLastError();
     }
     if (a.a_b16) return hipErrorInvalidValue;
     if (dbg == 0) {
-        hipLaunchKernelGGL(k_w2grad_ws<0>, g, b, 0, st, a, blk_per_wg);
+        if (a.gather_desc) hipLaunchKernelGGL(k_w2grad_ws<0>, g, b, 0, st, a, blk_per_wg);
+        else hipLaunchKernelGGL((k_w2grad_ws<0, 3, false, false>), g, b, 0, st, a, blk_per_wg);
         return hipGetLastError();
     }
 #ifdef SPWGNN_DIAG
