@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs; 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
@@ -46,7 +46,8 @@ typedef struct spwgnn_param_info {
 
 int32_t spwgnn_version(void);
 /* sizeof the ABI structs as this library was compiled (bindings check their own layouts against it):
- * which = 0 spwgnn_batch, 1 spwgnn_run, 2 spwgnn_plan_sizes, 3 spwgnn_param_info; -1 otherwise. */
+ * which = 0 spwgnn_batch, 1 spwgnn_run, 2 spwgnn_plan_sizes, 3 spwgnn_param_info,
+ * 4 spwgnn_loss_weights; -1 otherwise. */
 int32_t spwgnn_struct_size(int32_t which);
 const char* spwgnn_strerror(int32_t status);
 int32_t spwgnn_param_tensor_count(void);
@@ -283,6 +284,41 @@ int32_t spwgnn_bce_backward(const float* params, const spwgnn_batch* batch, cons
                             const float* targets, int64_t n, float* out3, float* dlogits, void* bce_scratch,
                             const double* weights3, double* total3, float* grads, float* dprop,
                             spwgnn_stream_t stream);
+
+/* Per-node loss weights (added within ABI 8: new symbols only, no existing struct or signature
+ * changed). Keras 2.x weighted_masked_objective with the divisor supplied by the caller:
+ *   loss = Σ_i w_i·bce_i / norm,   dlogits_i = w_i·(σ(z_i) − t_i) / norm  (0 where |z_i| >= the clip)
+ * with norm = #{i : w_i != 0} for Keras's sample_weight / class_weight (model.fit, main.py:92-98); a
+ * per-tower weight is that weight repeated over the tower's nodes. A zero weight is a MASK: the node
+ * adds exactly 0 to the loss, gets dlogits_i = 0 and is not counted, whatever its logit and target hold
+ * (NaN included). Weights are any finite floats; nothing validates them on the device. The caller gives
+ * norm because the gradient needs it before any reduction is done: by value, or in a device float a
+ * replayed step refills without recapture. (Keras divides by the count itself and gives NaN for an
+ * all-zero batch; a caller passing max(count, 1) gets loss 0 and zero gradients there.)
+ * out3 = {loss, correct predictions among the nodes with w != 0, number of nodes with w != 0}: with
+ * every weight non-zero that is spwgnn_bce's out3 (Keras's metrics= are unweighted too); with zeros it
+ * is the accuracy over the nodes that count — a deviation from Keras's unweighted metric.
+ * With w ≡ 1 and norm = n (n < 2^24) every output equals the unweighted call's bit for bit.
+ * scratch: >= spwgnn_bce_scratch_bytes(n), as for spwgnn_bce. */
+typedef struct spwgnn_loss_weights {
+    const float* w;         /* [n] device fp32 per-node weights, in the targets' order */
+    const float* norm_dev;  /* device float holding the divisor; NULL = use norm         */
+    double norm;            /* the divisor when norm_dev == NULL; must be > 0           */
+} spwgnn_loss_weights;
+/* spwgnn_bce (weights3 = total3 = NULL) / spwgnn_bce_accumulate with weights. SPWGNN_E_ARG: lw or
+ * lw->w NULL, norm <= 0 with norm_dev == NULL, weights3 / total3 not both set or both NULL. */
+int32_t spwgnn_bce_weighted(const float* logits, const float* targets, int64_t n, const spwgnn_loss_weights* lw,
+                            float* out3, float* dlogits, void* scratch, const double* weights3, double* total3,
+                            spwgnn_stream_t stream);
+/* spwgnn_bce_backward with weights: spwgnn_bce_weighted then spwgnn_backward in one call, bit for bit.
+ * The weighted loss launch runs first on every path — it is not folded into the fused small-batch
+ * loop, whose kernel would pay scratch and scalar spills for the extra arguments.
+ * Also SPWGNN_E_ARG unless n == batch->n_nodes. */
+int32_t spwgnn_bce_backward_weighted(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                                     void* workspace, int64_t workspace_bytes, const float* logits,
+                                     const float* targets, int64_t n, float* out3, float* dlogits, void* bce_scratch,
+                                     const double* weights3, double* total3, float* grads, float* dprop,
+                                     const spwgnn_loss_weights* lw, spwgnn_stream_t stream);
 
 /* Keras-2.x Adam (Networks.py:101: lr=5e-4, decay=0): in-place on the flat buffer.
  * g' = grad_scale*grad + 2*l2*param; lr_t = lr*sqrt(1-b2^t)/(1-b1^t);

@@ -50,6 +50,11 @@ class RunC(C.Structure):
                 ("grads_early_event", C.c_void_p)]
 
 
+class LossWeightsC(C.Structure):
+    """spwgnn_loss_weights: per-node loss weights and their divisor (added within ABI 8)."""
+    _fields_ = [("w", C.c_void_p), ("norm_dev", C.c_void_p), ("norm", C.c_double)]
+
+
 K_EDGE_FWD, K_NODE_FWD, K_EDGE_BWD, K_NODE_BWD, K_ENC_EDGE, K_ENC_EDGE_BWD, K_WGRAD_W2, K_DA = 1, 2, 3, 4, 5, 6, 7, 8
 K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD, K_INPUT_BWD = 9, 10, 11, 12
 MATH_F32, MATH_X6, MATH_BF16 = 0, 1, 2
@@ -90,6 +95,9 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_bce": (i32, [vp, vp, i64, vp, vp, vp, vp]),
         "spwgnn_bce_accumulate": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp]),
         "spwgnn_bce_backward": (i32, [vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "spwgnn_bce_weighted": (i32, [vp, vp, i64, C.POINTER(LossWeightsC), vp, vp, vp, vp, vp, vp]),
+        "spwgnn_bce_backward_weighted": (i32, [vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp,
+                                               C.POINTER(LossWeightsC), vp]),
         "spwgnn_adam": (i32, [vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, f32, f32, vp]),
         "spwgnn_adam_dev": (i32, [vp, vp, vp, vp, i64, vp, vp, i32, f32, f32, f32, f32, f32, vp]),
         "spwgnn_adam_lr_table": (i32, [f32, f32, f32, i32, vp]),
@@ -118,7 +126,7 @@ def lib() -> C.CDLL:
         if lib_.spwgnn_version() != ABI_VERSION:
             raise SpwgnnError(f"{path} implements ABI {lib_.spwgnn_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild with `python -m spwgnn_amd.build`")
-        for which, st in enumerate((BatchC, RunC, PlanSizes, ParamInfo)):
+        for which, st in enumerate((BatchC, RunC, PlanSizes, ParamInfo, LossWeightsC)):
             if lib_.spwgnn_struct_size(which) != C.sizeof(st):
                 raise SpwgnnError(f"{path} was built with a different {st.__name__} layout "
                                   f"({lib_.spwgnn_struct_size(which)} vs {C.sizeof(st)} bytes): rebuild it")

@@ -1038,8 +1038,10 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
     int32_t e = SPWGNN_OK;
     const bool fused = bwd_fused_taken(r, b);
     // spwgnn_bce_backward: on the fused loop (one loss workgroup) the loop computes dlogits itself and
-    // the loss sums ride in the last reduction launch; anywhere else the loss launch runs first
-    const bool bce_inline = bce && fused && bce->blocks == 1;
+    // the loss sums ride in the last reduction launch; anywhere else the loss launch runs first. A
+    // weighted loss (bce->w) is never folded: its three more kernel arguments cost the fused loop
+    // scratch and scalar spills, so its loss launch runs first on every path
+    const bool bce_inline = bce && fused && bce->blocks == 1 && !bce->w;
     if (bce && !bce_inline) SPW_CHECK(launch_bce(*bce, st));
     auto edge_encoder_bwd = [&]() -> int32_t {   // dA rebuild + relation encoder backward (wide kernels)
         if (rebuild) {
@@ -1445,7 +1447,7 @@ int32_t spwgnn_bce_backward(const float* params, const spwgnn_batch* batch, cons
 
 int64_t spwgnn_bce_scratch_bytes(int64_t n) {
     (void)n;
-    return 256 * 2 * sizeof(float);
+    return 256 * 3 * sizeof(float);   // [blocks][3] for the weighted loss; the unweighted one uses [blocks][2]
 }
 
 static int32_t bce_launch(const float* logits, const float* targets, int64_t n, float* out3, float* dlogits,
@@ -1474,6 +1476,57 @@ int32_t spwgnn_bce_accumulate(const float* logits, const float* targets, int64_t
                               void* scratch, const double* weights3, double* total3, spwgnn_stream_t stream) {
     if (!weights3 || !total3) return SPWGNN_E_ARG;
     return bce_launch(logits, targets, n, out3, dlogits, scratch, weights3, total3, stream);
+}
+
+// spwgnn_loss_weights' own checks (no pointer followed past lw itself)
+static bool loss_weights_ok(const spwgnn_loss_weights* lw) {
+    return lw && lw->w && (lw->norm_dev || lw->norm > 0.0);
+}
+static BceArgs weighted_bce_args(const float* logits, const float* targets, int64_t n, float* out3, float* dlogits,
+                                 void* scratch, const double* weights3, double* total3, const spwgnn_loss_weights* lw) {
+    BceArgs a{};   // as bce_launch builds it, plus the weights
+    a.w3 = weights3;
+    a.tot3 = total3;
+    a.logits = logits;
+    a.targets = targets;
+    a.n = n;
+    a.dlogits = dlogits;
+    a.partial = static_cast<float*>(scratch);
+    a.out3 = out3;
+    a.blocks = (int)std::min<int64_t>(256, (n + 255) / 256);
+    a.w = lw->w;
+    a.norm_dev = lw->norm_dev;
+    a.norm = lw->norm_dev ? 0.f : (float)lw->norm;
+    return a;
+}
+
+int32_t spwgnn_bce_weighted(const float* logits, const float* targets, int64_t n, const spwgnn_loss_weights* lw,
+                            float* out3, float* dlogits, void* scratch, const double* weights3, double* total3,
+                            spwgnn_stream_t stream) {
+    if (!loss_weights_ok(lw) || (!weights3) != (!total3)) return SPWGNN_E_ARG;
+    if (!logits || !targets || !out3 || !scratch || n < 1) return SPWGNN_E_ARG;
+    const BceArgs a = weighted_bce_args(logits, targets, n, out3, dlogits, scratch, weights3, total3, lw);
+    hipError_t e = launch_bce(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+}
+
+int32_t spwgnn_bce_backward_weighted(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                                     void* workspace, int64_t workspace_bytes, const float* logits,
+                                     const float* targets, int64_t n, float* out3, float* dlogits, void* bce_scratch,
+                                     const double* weights3, double* total3, float* grads, float* dprop,
+                                     const spwgnn_loss_weights* lw, spwgnn_stream_t stream) {
+    int32_t stt = validate(batch, run);
+    if (stt) return stt;
+    if (!run->training) return SPWGNN_E_NOTRAIN;
+    if (!loss_weights_ok(lw) || n != batch->n_nodes) return SPWGNN_E_ARG;
+    if (!params || !workspace || !grads || !logits || !targets || !out3 || !dlogits || !bce_scratch || n < 1 ||
+        (!weights3) != (!total3))
+        return SPWGNN_E_ARG;
+    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, 1);
+    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
+    const BceArgs a = weighted_bce_args(logits, targets, n, out3, dlogits, bce_scratch, weights3, total3, lw);
+    return run_backward(params, batch, run, w, static_cast<char*>(workspace), dlogits, grads, dprop,
+                        static_cast<hipStream_t>(stream), &a);
 }
 
 static float adam_lr_t(float lr, float beta1, float beta2, double t) {

@@ -62,6 +62,7 @@ int32_t spwgnn_struct_size(int32_t which) {
         case 1: return (int32_t)sizeof(spwgnn_run);
         case 2: return (int32_t)sizeof(spwgnn_plan_sizes);
         case 3: return (int32_t)sizeof(spwgnn_param_info);
+        case 4: return (int32_t)sizeof(spwgnn_loss_weights);
         default: return -1;
     }
 }

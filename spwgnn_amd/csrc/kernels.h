@@ -373,13 +373,24 @@ struct BceArgs {
     int blocks;
     const double* w3;   // non-null: tot3[k] += (double)out3[k] * w3[k] by the thread that writes out3
     double* tot3;
+    // per-node loss weights (spwgnn_bce_weighted; null w: the unweighted kernels, `partial` [blocks][2]).
+    // loss = Σ w_i·bce_i / norm, dlogits_i = w_i ≠ 0 ? w_i·bce_dlogit(z_i, t_i, 1/norm) : 0, out3 =
+    // {loss, correct among w ≠ 0, #{w ≠ 0}}; `partial` is [blocks][3]. norm = *norm_dev when set.
+    const float* w;
+    const float* norm_dev;
+    float norm;
 };
+__device__ __forceinline__ float bce_norm(const BceArgs& a) { return a.norm_dev ? *a.norm_dev : a.norm; }
 // Keras binary_crossentropy (Networks.py:102): clip(ŷ, 1e-7, 1-1e-7) ≡ clamp(z, ±ln((1-ε)/ε)).
 constexpr float kLogitClip = 16.11809565f;
 // dL/dz of one node (k_bce_partial's expression; the fused backward's inline form uses it too)
 __device__ __forceinline__ float bce_dlogit(float z0, float t, float inv_n) {
     const float p = 1.f / (1.f + expf(-z0));
     return fabsf(z0) < kLogitClip ? (p - t) * inv_n : 0.f;
+}
+// the weighted form: a zero weight is a mask (a select — a NaN target or logit under it stays out)
+__device__ __forceinline__ float bce_dlogit_w(float z0, float t, float w, float inv_norm) {
+    return w != 0.f ? w * bce_dlogit(z0, t, inv_norm) : 0.f;
 }
 struct ReduceBatch {       // the weight gradients of one backward, reduced in one launch (blockIdx.y)
     ReduceArgs r[kMaxReduce];

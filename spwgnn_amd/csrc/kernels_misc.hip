@@ -1756,6 +1756,74 @@ __global__ void k_bce_final(BceArgs a) {
     bce_store_out3(a, (float)(ls / (double)a.n), (float)cs);
 }
 
+// Per-node loss weights (a.w set; Keras 2.x weighted_masked_objective with the caller's divisor):
+// bce_block's sums with each term times w_i, the correct count over the nodes with w_i ≠ 0 and their
+// number as a third sum; a zero weight is a select, so whatever its logit and target hold stays out.
+// With w ≡ 1 and norm = n every value below is the unweighted kernels' (1.0f·x and the selects are
+// exact; 1/norm is bce_block's expression for 1/n). Kernels of their own: the unweighted ones keep
+// their registers and LDS.
+__device__ inline void bce_store_out3_w(const BceArgs& a, float loss, float correct, float count) {
+    const float o[3] = {loss, correct, count};
+    for (int k = 0; k < 3; ++k) {
+        a.out3[k] = o[k];
+        if (a.tot3) a.tot3[k] += (double)o[k] * a.w3[k];
+    }
+}
+template <bool FINAL>
+__device__ __forceinline__ void bce_block_w(const BceArgs& a, int blk) {
+    __shared__ float sl[256], sc[256], sn[256];
+    float ls = 0.f, cs = 0.f, ns = 0.f;
+    const float norm = bce_norm(a);
+    const float inv_n = 1.0f / (float)norm;
+    for (int64_t i = (int64_t)blk * 256 + threadIdx.x; i < a.n; i += (int64_t)a.blocks * 256) {
+        const float z0 = a.logits[i], t = a.targets[i], w = a.w[i];
+        const bool on = w != 0.f;
+        const float z = fminf(fmaxf(z0, -kLogitClip), kLogitClip);
+        const float l = fmaxf(z, 0.f) - z * t + log1pf(expf(-fabsf(z)));
+        ls += on ? w * l : 0.f;
+        const float p = 1.f / (1.f + expf(-z0));
+        cs += (on && (p > 0.5f ? 1.f : 0.f) == t) ? 1.f : 0.f;
+        ns += on ? 1.f : 0.f;
+        if (a.dlogits) a.dlogits[i] = bce_dlogit_w(z0, t, w, inv_n);
+    }
+    sl[threadIdx.x] = ls;
+    sc[threadIdx.x] = cs;
+    sn[threadIdx.x] = ns;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            sl[threadIdx.x] += sl[threadIdx.x + o];
+            sc[threadIdx.x] += sc[threadIdx.x + o];
+            sn[threadIdx.x] += sn[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if constexpr (FINAL) {
+            bce_store_out3_w(a, (float)((double)sl[0] / (double)norm), (float)(double)sc[0], (float)(double)sn[0]);
+        } else {
+            a.partial[3 * blk] = sl[0];
+            a.partial[3 * blk + 1] = sc[0];
+            a.partial[3 * blk + 2] = sn[0];
+        }
+    }
+}
+template <bool FINAL>
+__global__ __launch_bounds__(256) void k_bce_partial_w(BceArgs a) {
+    bce_block_w<FINAL>(a, blockIdx.x);
+}
+
+__global__ void k_bce_final_w(BceArgs a) {
+    if (threadIdx.x != 0) return;
+    double ls = 0.0, cs = 0.0, ns = 0.0;
+    for (int b = 0; b < a.blocks; ++b) {
+        ls += a.partial[3 * b];
+        cs += a.partial[3 * b + 1];
+        ns += a.partial[3 * b + 2];
+    }
+    bce_store_out3_w(a, (float)(ls / (double)bce_norm(a)), (float)cs, (float)ns);
+}
+
 __global__ void k_adam(AdamArgs a) {
     // replayable steps: the step count lives on the device; lr_t comes from the host-built table
     // (spwgnn_adam_lr_table: the same expression spwgnn_adam evaluates, so both paths agree bitwise)
@@ -2122,7 +2190,8 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce_small(ReduceBatch rb) {
     if (bias) a.out[a.bias_off + col] = s;
 }
 hipError_t launch_wgrad_reduce_all(const ReduceBatch& rb, hipStream_t st) {
-    if (rb.bce_row && (rb.bce.blocks != 1 || rb.bce.dlogits)) return hipErrorInvalidValue;   // one FINAL workgroup
+    // one FINAL workgroup of the unweighted loss (a weighted loss always has its own launch)
+    if (rb.bce_row && (rb.bce.blocks != 1 || rb.bce.dlogits || rb.bce.w)) return hipErrorInvalidValue;
     if (rb.n <= 0 && rb.nzero > 0) return hipErrorInvalidValue;   // the zero row writes through r[0].out
     if (rb.n <= 0 && !rb.bce_row) return hipSuccess;
     int maxc = 0;
@@ -2135,6 +2204,15 @@ hipError_t launch_wgrad_reduce_all(const ReduceBatch& rb, hipStream_t st) {
     return hipGetLastError();
 }
 hipError_t launch_bce(const BceArgs& a, hipStream_t st) {
+    if (a.w) {   // per-node weights: partial is [blocks][3]
+        if (a.blocks == 1) {
+            hipLaunchKernelGGL(k_bce_partial_w<true>, dim3(1), dim3(256), 0, st, a);
+            return hipGetLastError();
+        }
+        hipLaunchKernelGGL(k_bce_partial_w<false>, dim3(a.blocks), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_bce_final_w, dim3(1), dim3(64), 0, st, a);
+        return hipGetLastError();
+    }
     if (a.blocks == 1) {
         hipLaunchKernelGGL(k_bce_partial<true>, dim3(1), dim3(256), 0, st, a);
         return hipGetLastError();

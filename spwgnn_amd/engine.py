@@ -293,10 +293,12 @@ def backward_inputs(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig
 def bce_backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace, logits: torch.Tensor,
                  targets: torch.Tensor, scratch: "BceScratch", dlogits: Optional[torch.Tensor] = None,
                  total3: Optional[torch.Tensor] = None, weights3: Optional[torch.Tensor] = None,
-                 grads: Optional[torch.Tensor] = None, want_dprop: bool = False):
+                 grads: Optional[torch.Tensor] = None, want_dprop: bool = False,
+                 node_weights: Optional[torch.Tensor] = None, norm=None):
     """bce (or its accumulating form) then backward in one library call (spwgnn_bce_backward, ABI 6):
     bit-identical to the two calls; on the fused small-batch loop the loss needs no launch of its own.
-    Returns (out3, dlogits, grads, dprop)."""
+    With `node_weights` / `norm` (see `bce`) the weighted loss (spwgnn_bce_backward_weighted), whose
+    loss launch always runs first. Returns (out3, dlogits, grads, dprop)."""
     if not run.training:
         raise _lib.SpwgnnError("backward needs a training forward on the same workspace")
     if not ws.holds(batch, run):
@@ -316,14 +318,49 @@ def bce_backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, w
     b = batch.cstruct()
     r = run.cstruct()
     buf = ws.buf
-    st = _lib.lib().spwgnn_bce_backward(
-        flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(), logits.data_ptr(),
-        targets.data_ptr(), logits.numel(), scratch.out3.data_ptr(), dlogits.data_ptr(), scratch.scratch.data_ptr(),
-        weights3.data_ptr() if weights3 is not None else None, total3.data_ptr() if total3 is not None else None,
-        grads.data_ptr(), dprop.data_ptr() if dprop is not None else None, _stream(batch.device))
+    args = (flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(), logits.data_ptr(),
+            targets.data_ptr(), logits.numel(), scratch.out3.data_ptr(), dlogits.data_ptr(), scratch.scratch.data_ptr(),
+            weights3.data_ptr() if weights3 is not None else None, total3.data_ptr() if total3 is not None else None,
+            grads.data_ptr(), dprop.data_ptr() if dprop is not None else None)
+    if node_weights is None:
+        if norm is not None:
+            raise ValueError("norm goes with node_weights")
+        st = _lib.lib().spwgnn_bce_backward(*args, _stream(batch.device))
+        what = "spwgnn_bce_backward"
+    else:
+        lw, _keep = _loss_weights(node_weights, norm, logits)
+        st = _lib.lib().spwgnn_bce_backward_weighted(*args, C.byref(lw), _stream(batch.device))
+        what = "spwgnn_bce_backward_weighted"
     ws.bwd_key = ws.fwd_key if st == 0 else None
-    _lib.check(st, "spwgnn_bce_backward")
+    _lib.check(st, what)
     return scratch.out3, dlogits, grads, dprop
+
+
+def _loss_weights(node_weights: torch.Tensor, norm, logits: torch.Tensor):
+    """spwgnn_loss_weights of `node_weights` (one fp32 per logit, on the logits' device) and `norm`: a
+    number, a one-element device fp32 tensor (read on the device: a replayed step refills it), or None =
+    max(#non-zero weights, 1), counted here. Returns the struct and what it points into."""
+    _require_gpu(node_weights, "node_weights")
+    w = node_weights.reshape(-1)
+    if w.dtype != torch.float32 or not w.is_contiguous():
+        w = w.to(torch.float32).contiguous()
+    if w.numel() != logits.numel() or w.device != logits.device:
+        raise ValueError(f"node_weights must hold one weight per logit on {logits.device} "
+                         f"(got {w.numel()} on {w.device} for {logits.numel()} logits)")
+    lw = _lib.LossWeightsC()
+    lw.w = w.data_ptr()
+    if norm is None:
+        norm = max(int(torch.count_nonzero(w).item()), 1)   # one host sync
+    if isinstance(norm, torch.Tensor):
+        _require_gpu(norm, "norm")
+        if norm.dtype != torch.float32 or norm.numel() != 1 or norm.device != logits.device:
+            raise ValueError("a device norm is one fp32 element on the logits' device")
+        lw.norm_dev = norm.data_ptr()
+    else:
+        if not float(norm) > 0:
+            raise ValueError(f"norm must be > 0 (got {norm}); pass max(count of non-zero weights, 1)")
+        lw.norm = float(norm)
+    return lw, (w, norm)
 
 
 class BceScratch:
@@ -334,13 +371,38 @@ class BceScratch:
 
 
 def bce(logits: torch.Tensor, targets: torch.Tensor, scratch: BceScratch, dlogits: Optional[torch.Tensor] = None,
-        total3: Optional[torch.Tensor] = None, weights3: Optional[torch.Tensor] = None):
+        total3: Optional[torch.Tensor] = None, weights3: Optional[torch.Tensor] = None,
+        node_weights: Optional[torch.Tensor] = None, norm=None):
     """Keras binary_crossentropy (+ binary_accuracy numerator) and d loss / d logit on device.
     Returns out3 = [loss, n_correct, n] (device) and dlogits. With total3/weights3 (float64) the
-    same launch also does total3 += out3.double() * weights3 (spwgnn_bce_accumulate)."""
+    same launch also does total3 += out3.double() * weights3 (spwgnn_bce_accumulate).
+
+    `node_weights` (device fp32, one per logit, in the targets' order): the per-node weighted loss of
+    Keras 2.x (spwgnn_bce_weighted) — loss = Σ w·bce / norm, dlogits = w·(σ(z) − t) / norm. A zero weight
+    masks its node: it adds 0 to the loss, gets dlogit 0 and is not counted, whatever its logit and
+    target hold (NaN included). out3 is then [loss, correct among the nodes with w ≠ 0, their number] —
+    with zeros an accuracy over the nodes that count, where Keras's `metrics=` stay unweighted.
+    `norm`: a number, a one-element device fp32 tensor (read on the device), or None = the number of
+    non-zero weights, at least 1, counted here with one host sync. Keras divides by that count itself
+    and gives NaN (0/0) for an all-zero batch; here such a batch gives loss 0 and zero gradients.
+    `weights3` stays the epoch-sum weights of the accumulating form."""
     targets = targets.reshape(-1).to(torch.float32).contiguous()
     if dlogits is None:
         dlogits = _poison(torch.empty_like(logits))
+    if node_weights is not None:
+        if (total3 is None) != (weights3 is None):
+            raise ValueError("total3 and weights3 go together")
+        if total3 is not None:
+            assert total3.dtype == torch.float64 and weights3.dtype == torch.float64
+        lw, _keep = _loss_weights(node_weights, norm, logits)
+        st = _lib.lib().spwgnn_bce_weighted(
+            logits.data_ptr(), targets.data_ptr(), logits.numel(), C.byref(lw), scratch.out3.data_ptr(),
+            dlogits.data_ptr(), scratch.scratch.data_ptr(), weights3.data_ptr() if weights3 is not None else None,
+            total3.data_ptr() if total3 is not None else None, _stream(logits.device))
+        _lib.check(st, "spwgnn_bce_weighted")
+        return scratch.out3, dlogits
+    if norm is not None:
+        raise ValueError("norm goes with node_weights")
     args = (logits.data_ptr(), targets.data_ptr(), logits.numel(), scratch.out3.data_ptr(), dlogits.data_ptr(),
             scratch.scratch.data_ptr())
     if total3 is None:

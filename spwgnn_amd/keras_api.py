@@ -24,6 +24,34 @@ from .network import GraphNetwork
 from .replay import DeviceCounters, ReplayCache
 
 
+def node_weights(target, sample_weight=None, class_weight=None) -> np.ndarray:
+    """Per-node loss weights (B, N) float32 of Keras's `sample_weight` / `class_weight` for a (B, N[, 1])
+    0/1 target (pure numpy; model.fit's arguments, main.py:92-98).
+
+    `sample_weight`: (B,) — one weight per tower, repeated over its N nodes (with Keras 2.x's
+    weighted_masked_objective that is the same loss) — or (B, N), Keras's sample_weight_mode='temporal'.
+    `class_weight`: {0: a, 1: b}, applied per node by its target: an extension, Keras refuses
+    class_weight for 3-D targets. Both given: their product. A weight of 0 masks the node."""
+    t = np.asarray(target)
+    if t.ndim == 3 and t.shape[-1] == 1:
+        t = t[..., 0]
+    if t.ndim != 2:
+        raise ValueError("target must be (B, N) or (B, N, 1)")
+    w = np.ones(t.shape, np.float64)
+    if sample_weight is not None:
+        sw = np.asarray(sample_weight, np.float64)
+        if sw.shape == t.shape[:1]:
+            sw = sw[:, None]
+        elif sw.shape != t.shape:
+            raise ValueError(f"sample_weight must be (B,) or (B, N) = {t.shape} (got {sw.shape})")
+        w = w * sw
+    if class_weight is not None:
+        if set(class_weight) != {0, 1}:
+            raise ValueError("class_weight must be {0: a, 1: b}")
+        w = w * np.where(t == 1, float(class_weight[1]), float(class_weight[0]))
+    return w.astype(np.float32)
+
+
 class CompactDataset:
     """Host-side compact copy of a dense dataset: per-tower node rows and active edges."""
 
@@ -101,7 +129,7 @@ class KerasModel:
         # replayed fit steps (spwgnn_amd/replay.py): device step words, per-geometry graphs, epoch sums
         self._ctr: Optional[DeviceCounters] = None
         self._replays: Optional[ReplayCache] = None
-        self._replay_graph: Optional[bool] = None
+        self._replay_graph: Optional[tuple] = None   # (graph, weighted) of the cache in _replays
         self._tot = torch.zeros(3, dtype=torch.float64, device=dev)
         self._w3: Dict[int, torch.Tensor] = {}
 
@@ -124,18 +152,25 @@ class KerasModel:
         return out
 
     # ---------------------------------------------------------------- training
-    def train_on_batch(self, batch: TowerBatch, target: torch.Tensor):
-        """One Keras step: forward (dropout on), BCE, backward, Adam. Returns (loss, accuracy) tensors."""
+    def train_on_batch(self, batch: TowerBatch, target: torch.Tensor, node_weights=None):
+        """One Keras step: forward (dropout on), BCE, backward, Adam. Returns out3 = [loss, correct, n]
+        (device). `node_weights` (one per node, in the targets' order): the weighted loss of engine.bce
+        with the divisor max(#non-zero weights, 1) (one host sync to count them)."""
         net = self.net
         net._step_seed += 1
         run = E.RunConfig(net.mp_steps, training=True, dropout=net.dropout, seed=net._step_seed)
         z = E.forward(net.flat.data, batch, run, self._ws)
-        out3, dz = E.bce(z, target, self._bce)
+        out3, dz = E.bce(z, target, self._bce, node_weights=self._dev_weights(node_weights))
         E.backward(net.flat.data, batch, run, self._ws, dz, grads=self._grads)
         self.iterations += 1
         E.adam(net.flat.data, self._grads, self.m, self.v, self.iterations, self.lr, self.beta1, self.beta2,
                self.eps, self.l2)
         return out3
+
+    def _dev_weights(self, node_weights) -> Optional[torch.Tensor]:
+        if node_weights is None:
+            return None
+        return torch.as_tensor(node_weights, dtype=torch.float32, device=self.net.device).reshape(-1).contiguous()
 
     def _replay_body(self):
         """One fit step's launches for a replayed geometry: the same sequence as train_on_batch
@@ -143,7 +178,7 @@ class KerasModel:
         read from the device, and the epoch sums accumulated on the device."""
         net, ctr = self.net, self._ctr
 
-        def body(batch, target, ws, bce, z, dz, pre=None):
+        def body(batch, target, ws, bce, z, dz, pre=None, weights=None, norm=None):
             w3 = self._w3[batch.n_towers]        # created before the first (eager) run of a geometry
             # the key/step advance (and the replayed batch upload, `pre`) ride in the forward's first launch
             pro = None
@@ -155,31 +190,45 @@ class KerasModel:
             run = E.RunConfig(net.mp_steps, training=True, dropout=net.dropout, seed_dev=ctr.key, prologue=pro)
             E.forward(net.flat.data, batch, run, ws, logits=z)
             # loss + epoch sums and the backward in one call: on the fused small-batch loop the loss
-            # needs no launch of its own (spwgnn_bce_backward)
+            # needs no launch of its own (spwgnn_bce_backward); weights / norm: a weighted fit's per-node
+            # loss weights and their divisor, views of the step's static buffer
             E.bce_backward(net.flat.data, batch, run, ws, z, target, bce, dlogits=dz, total3=self._tot, weights3=w3,
-                           grads=self._grads)
+                           grads=self._grads, node_weights=weights, norm=norm)
             E.adam_dev(net.flat.data, self._grads, self.m, self.v, ctr.step, ctr.lr_table, self.beta1, self.beta2,
                        self.eps, self.l2)
         return body
 
-    def evaluate_batch(self, batch: TowerBatch, target: torch.Tensor):
+    def evaluate_batch(self, batch: TowerBatch, target: torch.Tensor, node_weights=None, norm=None):
+        """out3 = [loss, correct, n] of an inference forward; `node_weights` / `norm` as engine.bce takes
+        them (norm None: the non-zero weights are counted, one host sync)."""
         run = E.RunConfig(self.net.mp_steps, training=False)
         z = E.forward(self.net.flat.data, batch, run, self._ws)
-        out3, _ = E.bce(z, target, self._bce)
+        out3, _ = E.bce(z, target, self._bce, node_weights=self._dev_weights(node_weights), norm=norm)
         return out3
 
     def fit(self, x: Dict[str, np.ndarray], y: Dict[str, np.ndarray], batch_size: int = 32, epochs: int = 10,
             validation_split: float = 0.0, shuffle: bool = True, verbose: int = 1, seed: int = 0,
-            graph: bool = False):
+            graph: bool = False, sample_weight=None, class_weight=None):
         """Keras fit (main.py:92-98). Each training step is the replayable step of
         spwgnn_amd/replay.py — forward, BCE, backward and Adam per batch geometry on static buffers
         refilled by the step's first launch — issued eagerly (`graph=True`: the same step captured
         once and replayed as a hipGraph; bit-identical results; on the MI355X host eager issue is the
         faster, 0.270 vs 0.277 ms per step at batch 32); batches are planned with
-        N(N−1) relation slots per tower."""
+        N(N−1) relation slots per tower.
+
+        `sample_weight` ((B,) per tower or (B, N) per node) and `class_weight` ({0: a, 1: b}, per node by
+        its target — an extension, Keras refuses it for 3-D targets) weight the loss as Keras 2.x does
+        (`node_weights`): each batch's loss is Σ w·bce / #{w ≠ 0}. They are computed before the validation
+        split and split with it, and weight val_loss too. A zero weight masks its node; a batch whose
+        weights are all zero gives loss 0 and no gradient, where Keras gives NaN (0/0). The accuracies
+        count the nodes with w ≠ 0 only — with zero weights a deviation from Keras, whose `metrics=` stay
+        unweighted; with none it is Keras's. With neither argument the steps are exactly the unweighted
+        ones."""
         objects = np.asarray(x["objects"], np.float32)
         target = np.asarray(y["target"], np.float32).reshape(objects.shape[0], -1)
         B = objects.shape[0]
+        weighted = sample_weight is not None or class_weight is not None
+        W = node_weights(target, sample_weight, class_weight) if weighted else None
         n_tr = keras_split_at(B, validation_split)
         n_val = B - n_tr
         ds = CompactDataset(objects, x["sender_relations"], x["receiver_relations"], x.get("propagation"))
@@ -190,6 +239,8 @@ class KerasModel:
             hist.update({"val_loss": [], "val_binary_accuracy": []})
             vbatch = ds.subset(np.arange(n_tr, B), dev)
             vtgt = torch.as_tensor(target[n_tr:], device=dev).reshape(-1).contiguous()
+            vw = self._dev_weights(W[n_tr:]) if weighted else None
+            vnorm = max(int(np.count_nonzero(W[n_tr:])), 1) if weighted else None   # counted once, on the host
         # every step runs as a replayed hipGraph per batch geometry (graph=False: the same launches
         # eagerly); the device words start from the host counters and the host mirrors each step
         if self._ctr is None:
@@ -198,9 +249,9 @@ class KerasModel:
         else:
             self._ctr.set(key=self.net._step_seed, step=self.iterations, lr=self.lr, beta1=self.beta1,
                           beta2=self.beta2)
-        if self._replays is None or self._replay_graph != graph:
-            self._replays = ReplayCache(dev, self._replay_body, graph=graph)
-            self._replay_graph = graph
+        if self._replays is None or self._replay_graph != (graph, weighted):
+            self._replays = ReplayCache(dev, self._replay_body, graph=graph, weighted=weighted)
+            self._replay_graph = (graph, weighted)
         # per-epoch sums stay on the device (stream-ordered copies) and are read once after the last
         # epoch — with verbose=0 the host never waits for the GPU between epochs (a sync per epoch
         # drained the pipeline: ≈ 8 µs per step at batch 32); verbose > 0 reads them per epoch to print
@@ -214,7 +265,7 @@ class KerasModel:
             if n_val:
                 vl, vc, vn = ep_val[ep].tolist()
                 hist["val_loss"].append(vl)
-                hist["val_binary_accuracy"].append(vc / vn)
+                hist["val_binary_accuracy"].append(vc / max(vn, 1))
 
         for ep in range(epochs):
             order = rng.permutation(n_tr) if shuffle else np.arange(n_tr)
@@ -225,12 +276,12 @@ class KerasModel:
                 idx = order[b0:b0 + batch_size]
                 if len(idx) not in self._w3:
                     self._w3[len(idx)] = torch.tensor([float(len(idx)), 1.0, 1.0], dtype=torch.float64, device=dev)
-                self._replays(ds.subset_plan(idx, edge_cap=True), target[idx])
+                self._replays(ds.subset_plan(idx, edge_cap=True), target[idx], W[idx] if weighted else None)
                 self.net._step_seed += 1
                 self.iterations += 1
             ep_tot[ep].copy_(self._tot)
             if n_val:
-                ep_val[ep].copy_(self.evaluate_batch(vbatch, vtgt))
+                ep_val[ep].copy_(self.evaluate_batch(vbatch, vtgt, vw, vnorm))
             if verbose:
                 record(ep)
                 msg = f"Epoch {ep + 1}/{epochs} - loss: {hist['loss'][-1]:.4f} - binary_accuracy: {hist['binary_accuracy'][-1]:.4f}"

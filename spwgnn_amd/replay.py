@@ -83,11 +83,15 @@ class StaticBatch:
     Two pinned (device-mapped) staging slots: the host writes the next step's arrays into one while
     the step that reads the other runs; `copy_in(slot)` moves a slot into the device buffer with one
     kernel (spwgnn_copy_in) on the current stream — inside a captured step it is the graph's first
-    kernel node, so no copy sits between two replays."""
+    kernel node, so no copy sits between two replays.
+
+    `weighted`: the block also carries per-node loss weights (n_nodes floats) and their divisor (one
+    float) after the targets, each padded to 16 bytes and moved by the same copy: `weights` and
+    `norm` are the device views a weighted loss reads (engine.bce's node_weights / norm)."""
 
     SLOTS = 2
 
-    def __init__(self, plan: HostPlan, device):
+    def __init__(self, plan: HostPlan, device, weighted: bool = False):
         self.device = torch.device(device)
         self.geometry = plan.geometry
         self.offsets, total = [], 0
@@ -97,6 +101,12 @@ class StaticBatch:
         self.n_target = plan.n_nodes
         self.t_off = total
         total += (plan.n_nodes * 4 + 15) // 16 * 16
+        self.weighted = bool(weighted)
+        if self.weighted:
+            self.w_off = total
+            total += (plan.n_nodes * 4 + 15) // 16 * 16
+            self.norm_off = total
+            total += 16
         self.total = max(total, 16)
         self.buf = torch.zeros(self.total, dtype=torch.uint8, device=self.device)
         views = []
@@ -104,14 +114,19 @@ class StaticBatch:
             dt = torch.from_numpy(a[:0].reshape(-1)).dtype
             views.append(self.buf[o:o + a.nbytes].view(dt).view(a.shape))
         self.target = self.buf[self.t_off:self.t_off + 4 * plan.n_nodes].view(torch.float32)
+        self.weights = self.norm = None
+        if self.weighted:
+            self.weights = self.buf[self.w_off:self.w_off + 4 * plan.n_nodes].view(torch.float32)
+            self.norm = self.buf[self.norm_off:self.norm_off + 4].view(torch.float32)
         self.batch = TowerBatch.from_plan(plan, self.device, dev_arrays=views)
         self.ring = [torch.zeros(self.total, dtype=torch.uint8, pin_memory=True) for _ in range(self.SLOTS)]
         self.ring_dev = [_mapped_device_ptr(r) for r in self.ring]
         self.loads = 0
 
-    def fill(self, plan: HostPlan, target: np.ndarray, slot: int):
+    def fill(self, plan: HostPlan, target: np.ndarray, slot: int, weights: Optional[np.ndarray] = None):
         """This step's plan arrays and targets → pinned staging slot `slot` (host writes only: the
-        caller has made sure no step still reads that slot)."""
+        caller has made sure no step still reads that slot). A weighted block also takes the per-node
+        `weights` (None = all ones) and stores their divisor max(#non-zero, 1) beside them."""
         if plan.geometry != self.geometry:
             raise ValueError("batch geometry differs from the captured one")
         hv = self.ring[slot].numpy()
@@ -121,19 +136,30 @@ class StaticBatch:
         if t.size != self.n_target:
             raise ValueError("one target per node")
         hv[self.t_off:self.t_off + t.nbytes] = t.view(np.uint8)
+        if self.weighted:
+            w = (np.ones(self.n_target, np.float32) if weights is None
+                 else np.ascontiguousarray(weights, np.float32).reshape(-1))
+            if w.size != self.n_target:
+                raise ValueError("one weight per node")
+            hv[self.w_off:self.w_off + w.nbytes] = w.view(np.uint8)
+            norm = np.array([max(int(np.count_nonzero(w)), 1)], np.float32)
+            hv[self.norm_off:self.norm_off + 4] = norm.view(np.uint8)
+        elif weights is not None:
+            raise ValueError("weights need a StaticBatch built with weighted=True")
         self.loads += 1
         # host-side copies the wrappers keep for reporting (edge ids, counts) follow the new batch
         b = self.batch
         b.tower_edges, b.src, b.dst, b.edge_id = plan.tower_edges, plan.src, plan.dst, plan.edge_id
         b.tower_nodes, b.node_shape = plan.tower_nodes, plan.node_shape
+        b.node_perm = plan.node_perm
 
     def copy_in(self, slot: int):
         E.copy_in(self.ring[slot], self.buf, self.total, src_dev_ptr=self.ring_dev[slot])
 
-    def load(self, plan: HostPlan, target: np.ndarray):
+    def load(self, plan: HostPlan, target: np.ndarray, weights: Optional[np.ndarray] = None):
         """fill + copy_in through slot 0, synchronously ordered on the current stream (tools/tests)."""
         torch.cuda.current_stream(self.device).synchronize()
-        self.fill(plan, target, 0)
+        self.fill(plan, target, 0, weights)
         self.copy_in(0)
 
 
@@ -176,7 +202,9 @@ class ReplayStep:
     """One batch geometry's training step (forward, BCE, backward, Adam) as a replayed hipGraph.
 
     `body(batch, target, ws, bce, z, dz)` issues the step's launches on the current stream; it is
-    run eagerly on the first call (a real step) and captured right after, then replayed.
+    run eagerly on the first call (a real step) and captured right after, then replayed. A `weighted`
+    step uploads per-node loss weights and their divisor with the batch and passes them (views of the
+    static buffer) as `weights=` and `norm=` to a body whose signature names them.
 
     The batch upload is part of the step: its first kernel copies a pinned staging slot into the
     static device buffer (StaticBatch.copy_in). Two slots, one graph each: step i reads slot i mod 2,
@@ -185,8 +213,8 @@ class ReplayStep:
     replays (that copy left it idle ≈ 26 µs per Keras-fit step at batch 32,
     profiles/r04_fit_step_gaps.txt)."""
 
-    def __init__(self, plan: HostPlan, device, body: Callable, graph: bool = True):
-        self.static = StaticBatch(plan, device)
+    def __init__(self, plan: HostPlan, device, body: Callable, graph: bool = True, weighted: bool = False):
+        self.static = StaticBatch(plan, device, weighted=weighted)
         self.device = self.static.device
         self.ws = E.Workspace(self.device)
         self.bce = E.BceScratch(self.device)
@@ -195,7 +223,10 @@ class ReplayStep:
         self.dz = torch.empty(n, dtype=torch.float32, device=self.device)
         self.body = body
         # a body taking `pre` gets the upload as a prologue of its forward's first launch
-        self.fold = E.FOLD_PROLOGUE and "pre" in inspect.signature(body).parameters
+        names = inspect.signature(body).parameters
+        self.fold = E.FOLD_PROLOGUE and "pre" in names
+        if weighted and not ("weights" in names and "norm" in names):
+            raise ValueError("a weighted step needs a body that takes weights= and norm=")
         self.use_graph = graph
         self.graphs: list = [None] * StaticBatch.SLOTS
         self.done: list = [None] * StaticBatch.SLOTS   # per slot: SlotEvent after the last step that read it
@@ -208,19 +239,20 @@ class ReplayStep:
 
     def _issue(self, k: int):
         st = self.static
+        kw = {"weights": st.weights, "norm": st.norm} if st.weighted else {}
         if self.fold:   # the body's forward runs the upload in its first launch (spwgnn_run.prologue)
             pre = E.Prologue(dst=st.buf, src_dev_ptr=st.ring_dev[k], nbytes=st.total)
-            self.body(st.batch, st.target, self.ws, self.bce, self.z, self.dz, pre=pre)
+            self.body(st.batch, st.target, self.ws, self.bce, self.z, self.dz, pre=pre, **kw)
         else:
             st.copy_in(k)
-            self.body(st.batch, st.target, self.ws, self.bce, self.z, self.dz)
+            self.body(st.batch, st.target, self.ws, self.bce, self.z, self.dz, **kw)
 
-    def __call__(self, plan: HostPlan, target: np.ndarray):
+    def __call__(self, plan: HostPlan, target: np.ndarray, weights: Optional[np.ndarray] = None):
         k = self.calls % StaticBatch.SLOTS
         self.calls += 1
         if self.done[k] is not None:
             self.done[k].synchronize()
-        self.static.fill(plan, target, k)
+        self.static.fill(plan, target, k, weights)
         cur = torch.cuda.current_stream(self.device)
         if self.graphs[k] is not None:
             self.graphs[k].replay()
@@ -244,18 +276,20 @@ class ReplayStep:
 class ReplayCache:
     """ReplaySteps keyed by batch geometry (full batches and the epoch's last partial batch)."""
 
-    def __init__(self, device, make_body: Callable[[], Callable], graph: bool = True, max_entries: int = 8):
+    def __init__(self, device, make_body: Callable[[], Callable], graph: bool = True, max_entries: int = 8,
+                 weighted: bool = False):
         self.device, self.make_body, self.graph, self.max_entries = device, make_body, graph, max_entries
+        self.weighted = weighted
         self.steps: Dict[tuple, ReplayStep] = {}
 
-    def __call__(self, plan: HostPlan, target: np.ndarray):
+    def __call__(self, plan: HostPlan, target: np.ndarray, weights: Optional[np.ndarray] = None):
         key = plan.geometry
         st = self.steps.get(key)
         if st is None:
             if len(self.steps) >= self.max_entries:       # bounded: drop the oldest geometry
                 self.steps.pop(next(iter(self.steps)))
-            st = self.steps[key] = ReplayStep(plan, self.device, self.make_body(), self.graph)
-        st(plan, target)
+            st = self.steps[key] = ReplayStep(plan, self.device, self.make_body(), self.graph, self.weighted)
+        st(plan, target, weights)
         return st
 
 

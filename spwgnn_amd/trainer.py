@@ -15,6 +15,11 @@ from the shard plan (`spwgnn_amd/shard.py`) or, when not given, from one 8-byte 
 Micro-batches (`step` with lists) accumulate their node-weighted gradients before the one
 all-reduce and the one Adam update.
 
+Per-node loss weights (`step(..., weights=)`, Keras's sample_weight / class_weight): the loss is
+Σ w·bce over the nodes of the global batch divided by the number of its nodes with w ≠ 0
+(`norm_global`). Each micro-batch's loss divides by its own non-zero count nnz_i, and its gradient is
+scaled by nnz_i / norm_global instead of n_i / n_global: the same sum.
+
 The arithmetic engine is pluggable only so the CPU test-suite can drive this control flow under
 gloo with the oracle; the product engine is HipEngine and has no CPU fallback.
 """
@@ -62,6 +67,9 @@ class HipEngine:
 
     def loss(self, logits, target):
         return E.bce(logits, target, self.bce_scratch)
+
+    def loss_weighted(self, logits, target, weights, norm):
+        return E.bce(logits, target, self.bce_scratch, node_weights=weights, norm=norm)
 
     def backward(self, params, batch, run, dlogits):
         if self.grads is None or self.grads.numel() != params.numel():
@@ -144,24 +152,31 @@ class Trainer:
             self._ctr.set(step=self.iterations, lr=self.lr, beta1=self.b1, beta2=self.b2)
         self._ctr_at = self.iterations
 
-    def replay_body(self, n_nodes: int, n_global: Optional[int] = None):
+    def replay_body(self, n_nodes: int, n_global: Optional[int] = None, weighted: bool = False):
         """The launches of one single-batch `step` for spwgnn_amd.replay.ReplayStep (hipGraph
         replay): the dropout key and Adam step are device words (spwgnn_step_advance in the
         Trainer's splitmix key mode, spwgnn_adam_dev), so every replay is the next optimizer step
         with the masks `step` would draw. Single process only (no all-reduce inside a graph).
 
         Run each step through `replay_step(rs, plan, target)`: a replay advances the device words
-        only, and replay_step keeps `iterations` (the host counter `step` reads) in step with them."""
+        only, and replay_step keeps `iterations` (the host counter `step` reads) in step with them.
+
+        `weighted`: a body for ReplayStep(..., weighted=True) — it takes the step's per-node loss
+        weights and their divisor (the batch's own non-zero count, a device float) as `weights=` and
+        `norm=`; `replay_step(rs, plan, target, weights)` uploads them. Whole-batch steps only (no
+        n_global: the gradient scale nnz / norm_global would be a per-step host value)."""
         if self.world > 1:
             raise ValueError("replayed steps are single-process; DP steps use step()")
         if not isinstance(self.engine, HipEngine):
             raise ValueError("replayed steps need the HIP engine")
         self._sync_counters()
         ctr = self._ctr
+        if weighted and n_global not in (None, n_nodes):
+            raise ValueError("weighted replayed steps cover the whole batch (no n_global)")
         w = n_nodes / (n_global or n_nodes)
         grads = torch.empty_like(self.params)
 
-        def body(batch, target, ws, bce, z, dz, pre=None):
+        def body(batch, target, ws, bce, z, dz, pre=None, weights=None, norm=None):
             # the key/step advance (and the replayed batch upload, `pre`) ride in the forward's first launch
             pro = None
             if E.FOLD_PROLOGUE:
@@ -174,7 +189,8 @@ class Trainer:
             E.forward(self.params, batch, run, ws, logits=z)
             # the loss and the backward in one call (spwgnn_bce_backward: no loss launch of its own on
             # the fused small-batch loop; bit-identical to bce then backward)
-            E.bce_backward(self.params, batch, run, ws, z, target, bce, dlogits=dz, grads=grads)
+            E.bce_backward(self.params, batch, run, ws, z, target, bce, dlogits=dz, grads=grads,
+                           node_weights=weights, norm=norm)
             if w != 1.0:
                 grads.mul_(w)
             E.adam_dev(self.params, grads, self.m, self.v, ctr.step, ctr.lr_table, self.b1, self.b2, self.eps,
@@ -256,33 +272,50 @@ class Trainer:
         if self.ar_events is not None:
             self.ar_events[1].record()
 
-    def replay_step(self, rs, plan, target):
+    def replay_step(self, rs, plan, target, weights=None):
         """One replayed optimizer step (rs: a ReplayStep/ReplayCache over `replay_body`): the
         device words are first brought to the host's counters (a `step()` may have run in
-        between), the step runs, and the host counter advances with the device one."""
+        between), the step runs, and the host counter advances with the device one. `weights`: the
+        per-node loss weights of a weighted step (host array, one per node)."""
         self._sync_counters()
-        out = rs(plan, target)
+        out = rs(plan, target) if weights is None else rs(plan, target, weights)
         self.iterations += 1
         self._ctr_at = self.iterations
         return out
 
-    def step(self, batch, target, n_global: Optional[int] = None):
+    def _count_global(self, n_local: float) -> int:
+        """Σ over ranks of a per-rank count (one 8-byte all-reduce)."""
+        if self.world <= 1:
+            return int(n_local)
+        t = torch.tensor([float(n_local)], dtype=torch.float64,
+                         device=self.params.device if dist.get_backend(self.group) != "gloo" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return int(t.item())
+
+    def step(self, batch, target, n_global: Optional[int] = None, weights=None, norm_global: Optional[int] = None):
         """One optimizer step. `batch`/`target` may be lists (micro-batches of this rank's shard);
         `n_global` = nodes in the whole global batch (all ranks, all micro-batches). Returns one
         [loss, correct, n] device tensor for this rank's shard: the node-weighted mean BCE over its
-        micro-batches, the binary_accuracy numerator and the node count."""
+        micro-batches, the binary_accuracy numerator and the node count.
+
+        `weights` (one tensor per micro-batch, a weight per node in the targets' order): the weighted
+        loss of engine.bce — Σ w·bce over the global batch / `norm_global`, the number of nodes with
+        w ≠ 0 in the whole global batch (all-reduced when None, as n_global is; at least 1). Zero
+        weights mask their nodes. Counting each micro-batch's non-zero weights is one host sync. The
+        result is then [loss over this rank's counted nodes, correct among them, their number]. The
+        engine needs `loss_weighted(logits, target, weights, norm)`."""
         batches = batch if isinstance(batch, (list, tuple)) else [batch]
         targets = target if isinstance(target, (list, tuple)) else [target]
         if len(batches) != len(targets) or not batches:
             raise ValueError("one target per micro-batch")
+        if weights is not None:
+            return self._step_weighted(batches, targets, weights if isinstance(weights, (list, tuple)) else [weights],
+                                       norm_global)
+        if norm_global is not None:
+            raise ValueError("norm_global goes with weights")
         n_local = sum(b.n_nodes for b in batches)
         if n_global is None:
-            n_global = n_local
-            if self.world > 1:
-                t = torch.tensor([float(n_local)], dtype=torch.float64,
-                                 device=self.params.device if dist.get_backend(self.group) != "gloo" else "cpu")
-                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
-                n_global = int(t.item())
+            n_global = self._count_global(n_local)
         run = self.run_config()
         acc = None
         tot3 = None
@@ -349,3 +382,45 @@ class Trainer:
                          self.l2, 1.0)
         # node-weighted mean loss of this rank's shard, total correct, total nodes (device, fp32)
         return torch.stack([tot3[0] / tot3[2], tot3[1], tot3[2]]).float()
+
+    def _step_weighted(self, batches, targets, weights, norm_global):
+        """`step` with per-node loss weights: micro-batch i's loss divides by its own non-zero count
+        nnz_i (at least 1) and its gradient is scaled by nnz_i / norm_global."""
+        if len(weights) != len(batches):
+            raise ValueError("one weight tensor per micro-batch")
+        nnz = [int(torch.count_nonzero(torch.as_tensor(w)).item()) for w in weights]
+        if norm_global is None:
+            norm_global = self._count_global(sum(nnz))
+        norm_global = max(int(norm_global), 1)
+        acc = None
+        tot3 = None
+        for i, (b, tg, wt, k) in enumerate(zip(batches, targets, weights, nnz)):
+            run = self.run_config(micro=i)
+            z = self.engine.forward(self.params, b, run)
+            out3, dz = self.engine.loss_weighted(z, tg, wt, max(k, 1))
+            w3 = out3.double() * out3.new_tensor([float(k), 1.0, 1.0], dtype=torch.float64)
+            tot3 = w3 if tot3 is None else tot3 + w3   # before the engine reuses its out3 buffer
+            last = i == len(batches) - 1
+            ev = self._early(run) if last else None
+            g = self.engine.backward(self.params, b, run, dz)
+            w = k / norm_global
+            if acc is None:
+                if len(batches) == 1:
+                    acc = g
+                else:   # the engine writes every backward into one buffer: the sum lives in the Trainer's
+                    if getattr(self, "_acc", None) is None or self._acc.shape != g.shape or self._acc.device != g.device:
+                        self._acc = torch.empty_like(g)
+                    acc = self._acc
+                first = True
+            else:
+                first = False
+            if ev is not None:
+                self.reduce_split(acc, g, w, first, ev)
+            else:
+                self._combine(acc, g, w, slice(0, g.numel()), first)
+        if self.distributed and not self._split():
+            self.allreduce(acc)
+        self.iterations += 1
+        self.engine.adam(self.params, acc, self.m, self.v, self.iterations, self.lr, self.b1, self.b2, self.eps,
+                         self.l2, 1.0)
+        return torch.stack([tot3[0] / tot3[2].clamp(min=1.0), tot3[1], tot3[2]]).float()
