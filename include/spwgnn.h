@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
@@ -184,16 +184,32 @@ typedef struct spwgnn_run {
     void* grads_early_event;
 } spwgnn_run;
 
-/* Matrix-product arithmetic. F32 and X6 give fp32-class results:
+/* Matrix-product arithmetic. F32 and X6 give fp32-class results; X3 and BF16 do not:
  *   F32  v_mfma_f32_*_f32: one fp32 fma chain per output (the f32 MFMA rate, 157 TF)
  *   X6   each fp32 operand split into three bf16 parts, six bf16 MFMA products per fp32 product,
  *        fp32 accumulation (6/16 of the f32 MFMA cost; error O(2^-24) per product)
  *   BF16 operands rounded to bf16, one bf16 MFMA product, fp32 accumulation; in training the
  *        stored A, U, V (the three terms of h1) rounded to bf16 once (BASELINE configs 3-4 are
- *        quoted in bf16; error O(2^-9) per product — not the fp32 parity path)                */
+ *        quoted in bf16; error O(2^-9) per product — not the fp32 parity path)
+ *   X3   (added within ABI 8) each fp32 operand x split into two bf16 parts,
+ *        h = bf16_rne(x), m = bf16_rne(x − h) — the first two parts of X6's split, the third is not
+ *        formed — and three bf16 MFMA products per fp32 product, acc += a_m·b_h, then a_h·b_m, then
+ *        a_h·b_h, with fp32 accumulation: X6's order without the terms that hold a third part and
+ *        without m·m. Operands carry a 16-bit mantissa over the whole fp32 exponent range (no
+ *        scaling); error O(2^-17) per product. One-hot sums (the receiver sum of h2, the sender /
+ *        receiver sums of dh1pre) and bias gradients sum the two-part roundings of their values.
+ *        Everything X6 keeps in fp32 stays fp32 (every stored array, the vector-ALU first layers,
+ *        bias / relu / tanh / dropout, BCE, Adam); X3 takes X6's kernels, launch paths and f32
+ *        fallbacks with two parts. Not fp32-class and not the parity path: between BF16 and X6. */
 #define SPWGNN_MATH_F32 0
 #define SPWGNN_MATH_X6 1
 #define SPWGNN_MATH_BF16 2
+#define SPWGNN_MATH_X3 3
+
+/* bf16 MFMA products per fp32 product of a math id: 6 (X6), 3 (X3), 1 (BF16), 0 (F32: none, the
+ * f32 matrix instructions); −1 for an id this library does not know. Bindings probe support of a
+ * math with it and profilers price FLOPs by it. No device work. */
+int32_t spwgnn_math_products(int32_t math);
 
 #define SPWGNN_K_NONE 0
 #define SPWGNN_K_EDGE_FWD 1
@@ -229,7 +245,7 @@ int32_t spwgnn_team_max_blocks(int32_t set);
  * last K propagation steps also keeps its dh1pre, and the dA kernel reads those K steps back instead
  * of repeating their W2ᵀ products. Every K gives bitwise the same gradients; it trades matrix work for
  * streamed bytes. The slabs are workspace arrays that are dead meanwhile: no larger workspace. K is
- * clamped per call to min(4, mp_steps − 1) and is 0 for bf16 / fp32 math, small (team) batches and
+ * clamped per call to min(4, mp_steps − 1) and is 0 for bf16 / fp32 math (x3 stores like x6), small (team) batches and
  * receiver-block plans. set >= 0 sets K for the process and returns the previous value; set < 0 only
  * returns it. Read when a call plans its launches. */
 int32_t spwgnn_da_stored_steps(int32_t set);

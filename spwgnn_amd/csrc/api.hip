@@ -7,7 +7,8 @@
 #include "kernels.h"
 #include <vector>
 #include "../../include/spwgnn.h"
-static_assert(SPWGNN_MATH_F32 == spw::MATH_F32 && SPWGNN_MATH_X6 == spw::MATH_X6 && SPWGNN_MATH_BF16 == spw::MATH_BF16,
+static_assert(SPWGNN_MATH_F32 == spw::MATH_F32 && SPWGNN_MATH_X6 == spw::MATH_X6 && SPWGNN_MATH_BF16 == spw::MATH_BF16 &&
+                  SPWGNN_MATH_X3 == spw::MATH_X3,
               "math ids");
 
 namespace spw {
@@ -264,7 +265,7 @@ static int32_t validate(const spwgnn_batch* b, const spwgnn_run* r) {
     if (r->mp_steps < 1 || r->mp_steps > 64) return SPWGNN_E_SHAPE;
     if (!b->pos || !b->wtile || !b->edge_src || !b->edge_dst || !b->blk_csr) return SPWGNN_E_ARG;
     if (r->dropout < 0.f || r->dropout >= 1.f) return SPWGNN_E_ARG;
-    if (r->math != SPWGNN_MATH_F32 && r->math != SPWGNN_MATH_X6 && r->math != SPWGNN_MATH_BF16) return SPWGNN_E_ARG;
+    if (math_products(r->math) < 0) return SPWGNN_E_ARG;   // an id this library does not know
     if (r->training && r->dropout > 0.f && (!b->node_tower || !b->node_local)) return SPWGNN_E_ARG;
     return SPWGNN_OK;
 }
@@ -321,7 +322,7 @@ struct Prof {
 // SPWGNN_DA_RMW (diagnosis builds only) selects the read-add-write form for A/B.
 static bool rebuild_dA(const spwgnn_run* r, const spwgnn_batch* b) {
     const int m = kmath(r, kX6EdgeBwd);
-    return b->nw_max <= 16 && m != MATH_F32 && !(m == MATH_X6 && !team_blocks(b->n_wtiles) && getenv_flag("SPWGNN_DA_RMW"));
+    return b->nw_max <= 16 && m != MATH_F32 && !(math_split32(m) && !team_blocks(b->n_wtiles) && getenv_flag("SPWGNN_DA_RMW"));
 }
 
 // Stored dh1pre steps of that sum: on the wide x6 kernels the edge backward of steps
@@ -340,7 +341,7 @@ int da_stored_steps(int set) {
 }
 static bool bwd_fused_taken(const spwgnn_run* r, const spwgnn_batch* b);
 static int da_stored_planned(const spwgnn_run* r, const spwgnn_batch* b, const Ws& w) {
-    if (!rebuild_dA(r, b) || kmath(r, kX6EdgeBwd) != MATH_X6 || team_blocks(b->n_wtiles) || team_blocks(b->n_eblocks) ||
+    if (!rebuild_dA(r, b) || !math_split32(kmath(r, kX6EdgeBwd)) || team_blocks(b->n_wtiles) || team_blocks(b->n_eblocks) ||
         bwd_fused_taken(r, b))
         return 0;
     const int64_t step = w.dz3 - w.dz4;   // the four slabs at one stride, each a whole edge array
@@ -538,7 +539,7 @@ static int32_t run_forward(const float* params, const spwgnn_batch* b, const spw
         ef.n16 = store_b16_node(r, b);
         ef.uv16 = uv16;
         ef.n_nodes = b->n_nodes;
-        ef.recv_blocks = (b->flags & SPWGNN_BATCH_RECV_BLOCKS) && kmath(r, kX6EdgeFwd) == MATH_X6 &&
+        ef.recv_blocks = (b->flags & SPWGNN_BATCH_RECV_BLOCKS) && math_split32(kmath(r, kX6EdgeFwd)) &&
                          b->n_eblocks == b->n_nodes && !getenv_flag("SPWGNN_RB_ONEHOT");
         ef.mask2 = r->training ? c.u(w.m2_at(s)) : nullptr;
         ef.uv_zero = s == 0 && zero_prop;
@@ -799,7 +800,7 @@ static int32_t run_wgrad(const Ctx& c, const spwgnn_batch* b, const WgSpec& g, f
     }
     // a small x6 batch: the W2 gradient runs inside the batched weight-gradient launch
     // (the copy in the batched launch is the descriptor form: the pointer form runs as its own launch)
-    const bool w2_in_batch = ws && math == MATH_X6 && wsb && team_blocks(b->n_eblocks) && a.gather_desc &&
+    const bool w2_in_batch = ws && math_split32(math) && wsb && team_blocks(b->n_eblocks) && a.gather_desc &&
                              !getenv_flag("SPWGNN_NO_W2_MERGE");
     if (prof && g.recompute && !w2_in_batch) SPW_CHECK(prof->before(SPWGNN_K_WGRAD_W2));
     if (w2_in_batch) {
@@ -1362,6 +1363,10 @@ int32_t spwgnn_team_max_blocks(int32_t set) {
 
 int32_t spwgnn_da_stored_steps(int32_t set) {
     return da_stored_steps(set);
+}
+
+int32_t spwgnn_math_products(int32_t math) {
+    return math_products(math);
 }
 
 int32_t spwgnn_forward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,

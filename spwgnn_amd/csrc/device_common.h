@@ -139,9 +139,17 @@ __device__ __forceinline__ bf16x8 as_bf16x8(i16x4 lo, i16x4 hi) {
 __device__ __forceinline__ bf16x8 as_bf16x8(uint4 v) { return __builtin_bit_cast(bf16x8, v); }
 // acc += a·b over the six split products (a[p], b[p]: parts h, m, l); small terms first.
 // NP = 1 is the bf16 math (SPWGNN_MATH_BF16): the h parts alone, one product.
+// NP = 2 is the x3 math (SPWGNN_MATH_X3): parts h and m, the three products m·h, h·m, h·h — x6's
+// order without the terms that hold an l part and without m·m.
 template <int NP = 3>
 __device__ __forceinline__ f32x4 mfma16_x6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4 c) {
+    static_assert(NP >= 1 && NP <= 3, "parts");
     if constexpr (NP == 1) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
+    if constexpr (NP == 2) {
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
+    }
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], c, 0, 0, 0);
@@ -151,7 +159,13 @@ __device__ __forceinline__ f32x4 mfma16_x6(const bf16x8 (&a)[3], const bf16x8 (&
 }
 template <int NP = 3>
 __device__ __forceinline__ f32x16 mfma32_x6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 c) {
+    static_assert(NP >= 1 && NP <= 3, "parts");
     if constexpr (NP == 1) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
+    if constexpr (NP == 2) {
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
+    }
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
@@ -168,7 +182,15 @@ __device__ __forceinline__ void mfma32_x6_group(const bf16x8 (&a)[3], const bf16
     if constexpr (NP == 1) {
 #pragma unroll
         for (int u = 0; u < NT; ++u) acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[u][0], acc[u], 0, 0, 0);
+    } else if constexpr (NP == 2) {
+        constexpr int pa[3] = {1, 0, 0}, pb[3] = {0, 1, 0};
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int u = 0; u < NT; ++u)
+                acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[pa[p]], b[u][pb[p]], acc[u], 0, 0, 0);
     } else {
+        static_assert(NP == 3, "parts");
         constexpr int pa[6] = {2, 0, 1, 1, 0, 0}, pb[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
         for (int p = 0; p < 6; ++p)

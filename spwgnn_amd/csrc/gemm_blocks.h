@@ -496,7 +496,7 @@ __device__ __forceinline__ void ht_leave(const f32x4 (&q)[NC][2], f32x16 (&out)[
 template <int PARTS, int NC>
 __device__ __forceinline__ void ht_mfma(const bf16x8 (&a)[3], const uint32_t (&x0)[NC][3][4], const uint32_t (&x1)[NC][3][4],
                                         bool has1, f32x4 (&q)[NC][2]) {
-    constexpr int LP = PARTS == 1 ? 1 : 3;
+    constexpr int LP = PARTS;   // parts the math reads: x6 3, x3 2, bf16 1
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         bf16x8 b0[3], b1[3];
@@ -608,8 +608,8 @@ __device__ __forceinline__ void tgemm_x6(GetB&& getb, f32x16 (&out)[NC][NT_OUT],
 // Every wave of the workgroup calls the same tgemm_x6_wg sequence (no early exit: a wave with no
 // rows of its own runs on clamped rows and stores nothing), so the image streams from L2 once per
 // workgroup instead of once per wave. The image is cut into slices of KPS k-blocks (all NT_OUT steps,
-// the parts the math uses: x6 one k-block × 3 parts, bf16 three k-blocks × the h part — ≤ 15 KiB
-// either way), DMA'd (global_load_lds, 1 KiB per wave-instruction, the NW waves' pieces interleaved)
+// the parts the math uses: x6 one k-block × 3 parts, x3 one k-block × 2 parts, bf16 three k-blocks ×
+// the h part — ≤ 15 KiB each way), DMA'd (global_load_lds, 1 KiB per wave-instruction, the NW waves' pieces interleaved)
 // into a ring of kWgRing LDS slots kWgRing − 2 slices ahead of use. One barrier per slice, at its
 // last step: it certifies that slice sl+1 has landed (each wave waits for its own DMAs with a vmcnt
 // that leaves the newer slices in flight) and that no wave still reads slot (sl−1) mod kWgRing, which
@@ -632,7 +632,7 @@ __device__ __forceinline__ void tgemm_x6_wg(GetB&& getb, f32x16 (&out)[NC][NT_OU
     static_assert(!HT || NT_OUT == 4, "half tile: 4-tile products");
     static_assert(T0 + NT_OUT <= INT && (!HT || INT == NT_OUT), "output tiles within the image's");
     constexpr int SPD = HT ? 3 : 2;
-    constexpr int LP = PARTS == 1 ? 1 : 3;    // parts held in LDS
+    constexpr int LP = PARTS;                 // parts held in LDS (x3: h and m of the three-part image)
     constexpr int KPS = PARTS == 1 ? 3 : 1;   // k-blocks per slice
     static_assert(KPS * NT_OUT * LP * 64 <= kWgSlot, "slot size");
     constexpr int NS = NKB * NT_OUT, NP = 4 * NC, SST = KPS * NT_OUT;   // steps, pair-splits, steps per slice

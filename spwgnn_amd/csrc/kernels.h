@@ -428,7 +428,21 @@ hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st);
 hipError_t launch_enc_edge_bwd(const EncEdgeBwdArgs& a, int math, hipStream_t st);
 hipError_t launch_dA(const DaArgs& a, int math, hipStream_t st);
 hipError_t launch_enc_node_bwd(const EncNodeBwdArgs& a, int math, hipStream_t st);
-enum MathMode : int { MATH_F32 = 0, MATH_X6 = 1, MATH_BF16 = 2 };   // = SPWGNN_MATH_* (spwgnn.h)
+enum MathMode : int { MATH_F32 = 0, MATH_X6 = 1, MATH_BF16 = 2, MATH_X3 = 3 };   // = SPWGNN_MATH_* (spwgnn.h)
+// split math with fp32 storage: x6 (three parts) and x3 (two parts) take the same kernels, launch
+// paths and fallbacks and differ in the part count the kernels are instantiated with
+inline bool math_split32(int math) { return math == MATH_X6 || math == MATH_X3; }
+// bf16 MFMA products per fp32 product (spwgnn_math_products)
+inline int math_products(int math) {
+    return math == MATH_X6 ? 6 : math == MATH_X3 ? 3 : math == MATH_BF16 ? 1 : math == MATH_F32 ? 0 : -1;
+}
+// A launch of a kernel templated on the part count, in a split math with fp32 storage:
+// SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k<NP>), ...)) instantiates both forms and runs the math's
+#define SPW_SPLIT32(math, NPV, ...)                                 \
+    do {                                                            \
+        if ((math) == MATH_X3) { constexpr int NPV = 2; __VA_ARGS__; } \
+        else { constexpr int NPV = 3; __VA_ARGS__; }                \
+    } while (0)
 hipError_t launch_wgrad(const WgradArgs& a, int chunks, int math, hipStream_t st);
 hipError_t launch_wgrad_ws(const WgWsArgs& a, int wgs, int kx_pad, int ny_pad, int yrow, int mask, int math,
                            hipStream_t st, int b16 = 0);

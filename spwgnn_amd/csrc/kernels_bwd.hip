@@ -259,13 +259,23 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_bwd_x6(NodeBwdArg
             if (has[c]) store_cm<4>(a.dco + bN(c), D[c], lane, valid[c]);
         }
     }
+    // x3 (NP = 2): the lane index of the loads and stores from here on behind an opaque copy, so that
+    // their addresses are formed here instead of at the kernel's start and kept live through every
+    // chain — left to the compiler, this instantiation ran 3 registers over its 256 and spilled to
+    // scratch where its x6 twin does not; x6 and bf16 keep their code
+    // (& 63: the callees keep the lane range that every other caller gives them)
+    int late_lane = lane;
+    if constexpr (NP == 2) {
+        asm volatile("" : "+v"(late_lane));
+        late_lane &= 63;
+    }
     // effect part → g = da ⊙ (1 - a²) → G3 = g·W3ᵀ
     zero2(D);
     tchain_x6s<4, 7, 4, NC, kX6Ring, NP, NW, kHT>(G, D, kHT ? a.xh_wo1at : a.x_wo1at, lane, wr);
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         f32x16 Aa[4];
-        load_cm<4>(a.a + bN(c), Aa, lane);
+        load_cm<4>(a.a + bN(c), Aa, late_lane);
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -275,7 +285,7 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_bwd_x6(NodeBwdArg
             }
         if (has[c]) {
             if constexpr (N16) store_cm_b16<4>(reinterpret_cast<uint16_t*>(a.g) + bN(c), D[c], lane, valid[c]);
-            else store_cm<4>(a.g + bN(c), D[c], lane, valid[c]);
+            else store_cm<4>(a.g + bN(c), D[c], late_lane, valid[c]);
         }
     }
     f32x16 H[NC][5];
@@ -284,7 +294,7 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_bwd_x6(NodeBwdArg
     tchain_x6s<5, 7, 4, NC, kX6Ring, NP, NW>(D, H, a.x_w3t, lane, wr);
 #pragma unroll
     for (int c = 0; c < NC; ++c)
-        if (has[c]) store_cm<5>(a.G3 + bE(c), H[c], lane, valid[c]);
+        if (has[c]) store_cm<5>(a.G3 + bE(c), H[c], late_lane, valid[c]);
 }
 
 
@@ -709,7 +719,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 
 // ------------------------------------------------------------------------------------------------
 hipError_t launch_node_bwd(const NodeBwdArgs& a, int math, hipStream_t st) {
-    if ((math == MATH_X6 || math == MATH_BF16) && a.dco_sum && team_blocks((a.n_nodes + 31) / 32))
+    if ((math_split32(math) || math == MATH_BF16) && a.dco_sum && team_blocks((a.n_nodes + 31) / 32))
         return a.n16 ? hipErrorInvalidValue : launch_node_bwd_team(a, math, st);   // team kernels: fp32 arrays
     if (a.n16 && math != MATH_BF16) return hipErrorInvalidValue;
     if (math == MATH_BF16) {
@@ -718,13 +728,13 @@ hipError_t launch_node_bwd(const NodeBwdArgs& a, int math, hipStream_t st) {
         else hipLaunchKernelGGL((k_node_bwd_x6<1, 1, 4>), dim3((w + 3) / 4), dim3(256), 0, st, a);
         return hipGetLastError();
     }
-    if (math == MATH_X6) {
+    if (math_split32(math)) {
         // one 32-node column tile per wave at two waves per SIMD, weight images shared by the
         // workgroup's 4 waves (0.474 ms vs 0.557 for two tiles per wave at one wave per SIMD with
         // per-wave rings, 0.630 for that with the shared ring: 393K nodes)
         constexpr int NC = 1, NW = 4;
         const int w2 = ((a.n_nodes + 31) / 32 + NC - 1) / NC;
-        hipLaunchKernelGGL((k_node_bwd_x6<NC, 3, NW>), dim3((w2 + 3) / 4), dim3(256), 0, st, a);
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_node_bwd_x6<NC, NP, NW>), dim3((w2 + 3) / 4), dim3(256), 0, st, a));
         return hipGetLastError();
     }
     const int waves = (a.n_nodes + 31) / 32;
@@ -801,7 +811,7 @@ __device__ __forceinline__ float4 slab_load(const float4* p) {
 template <bool ACCUM, bool NODA = false, int NP = 3, int DBG = 0, bool N16 = false, bool SLAB = false,   // DBG 3 (diagnosis): G3 rows of the tile's first node
           bool DESC = false>
 __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_edge_bwd_x6(EdgeBwdArgs a) {
-    static_assert(!SLAB || (NODA && NP == 3 && !N16), "stored dh1pre steps: the x6 rebuild form only");
+    static_assert(!SLAB || (NODA && NP >= 2 && !N16), "stored dh1pre steps: the x6 / x3 rebuild form only");
     constexpr int PF = NP == 1 ? SPWGNN_EBWD_PF_B16 : SPWGNN_EBWD_PF, kWaves = 8;   // bf16: see k_dA_x6
     __shared__ uint4 wl[50 * 3 * 64];   // W2ᵀ x6 image: [kb·5 + T][part][lane]
     for (int idx = threadIdx.x; idx < 50 * 3 * 64; idx += blockDim.x) wl[idx] = a.x_w2t[idx];
@@ -949,6 +959,15 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         }
         float* dArow = a.dA + (int64_t)blk * 32 * kLdE + i;
         float4* slab4 = SLAB ? reinterpret_cast<float4*>(a.dh1_slab) + (int64_t)blk * (kCmBlk / 4) : nullptr;
+        // x3's stored-step pointer form: the slab stores' lane offsets formed here, behind an opaque copy,
+        // not ahead of the product loop — that instantiation alone ran 3 registers over its 256 and
+        // spilled where its x6 twin does not. & 63 / & 31: the range the plain index has
+        int slane = lane, si = i;
+        if constexpr (SLAB && !DESC && NP == 2) {
+            asm volatile("" : "+v"(slane));
+            slane &= 63;
+            si = slane & 31;
+        }
 #if SPWGNN_ONEHOT_BPERM && SPWGNN_OH_KB >= 10
         build_oh();
 #endif
@@ -980,10 +999,10 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 uint32_t hw[4], mw[4], lw[4];
 #pragma unroll
                 for (int m = 0; m < 4; ++m) split2(acc[t][8 * s + 2 * m], acc[t][8 * s + 2 * m + 1], hw[m], mw[m], lw[m]);
-                if constexpr (NP == 3) {
+                if constexpr (NP == 3)
                     nacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ao, as_bf16x8(make_uint4(lw[0], lw[1], lw[2], lw[3])), nacc[t], 0, 0, 0);
+                if constexpr (NP >= 2)   // x3: the sum of the 2-part roundings
                     nacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ao, as_bf16x8(make_uint4(mw[0], mw[1], mw[2], mw[3])), nacc[t], 0, 0, 0);
-                }
                 nacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ao, as_bf16x8(make_uint4(hw[0], hw[1], hw[2], hw[3])), nacc[t], 0, 0, 0);
                 // dA rows of this k-block's 8 registers, issued beside the MFMAs
 #pragma unroll
@@ -997,8 +1016,8 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
                     for (int q = 2 * s; q < 2 * s + 2; ++q) {
                         const float4 v = make_float4(acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]);
-                        if (t < 4) slab_store(slab4 + (4 * t + q) * 64 + lane, v);
-                        else if (i < kSlabT4) slab_store(slab4 + kSlabT4Base + (q * 2 + h) * kSlabT4 + i, v);
+                        if (t < 4) slab_store(slab4 + (4 * t + q) * 64 + slane, v);
+                        else if (si < kSlabT4) slab_store(slab4 + kSlabT4Base + (q * 2 + h) * kSlabT4 + si, v);
                     }
                 }
             }
@@ -1007,6 +1026,11 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         G4 = NG4;
     }
     // nacc[t] reg r = row rho(r,h): rows 0..15 receiver nodes, 16..31 sender nodes
+    int ti = i;   // (x3's stored-step pointer form: the tile's store offsets formed here, as the slab's above)
+    if constexpr (SLAB && !DESC && NP == 2) {
+        asm volatile("" : "+v"(ti));
+        ti &= 31;
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int row = rho(r, h);
@@ -1015,9 +1039,9 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             float* o = row < 16 ? a.dV : a.dU;   // chunk-major node rows
 #pragma unroll
             for (int t = 0; t < 5; ++t)
-                if (32 * t + i < 2 * kKhE) {
-                    if constexpr (N16) store_b16(o, cm_index<kKhE>(n0 + node, 32 * t + i), nacc[t][r]);
-                    else o[cm_index<kKhE>(n0 + node, 32 * t + i)] = nacc[t][r];
+                if (32 * t + ti < 2 * kKhE) {
+                    if constexpr (N16) store_b16(o, cm_index<kKhE>(n0 + node, 32 * t + ti), nacc[t][r]);
+                    else o[cm_index<kKhE>(n0 + node, 32 * t + ti)] = nacc[t][r];
                 }
         }
     }
@@ -1026,8 +1050,8 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 }
 
 hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st) {
-    // a stored dh1pre step: the wide x6 rebuild form only (k_dA_x6<3> is its one reader)
-    if (a.dh1_slab && (math != MATH_X6 || a.nw_max > 16 || !a.no_dA || team_blocks(a.n_wtiles))) return hipErrorInvalidValue;
+    // a stored dh1pre step: the wide x6 / x3 rebuild form only (k_dA_x6<NP, false, true> is its one reader)
+    if (a.dh1_slab && (!math_split32(math) || a.nw_max > 16 || !a.no_dA || team_blocks(a.n_wtiles))) return hipErrorInvalidValue;
     if (math != MATH_F32 && a.nw_max <= 16 && a.no_dA && team_blocks(a.n_wtiles))   // small batches
         return a.n16 ? hipErrorInvalidValue : launch_edge_bwd_team(a, math, st);   // team kernels: fp32 dU/dV
     if (a.n16 && (math != MATH_BF16 || a.nw_max > 16 || !a.no_dA)) return hipErrorInvalidValue;
@@ -1045,20 +1069,20 @@ hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st) {
             if (a.gather_desc) {   // G3 rows through a buffer descriptor (§3zk)
                 if (math == MATH_BF16 && a.n16) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 1, 0, true, false, true>), g, b, 0, st, a);
                 else if (math == MATH_BF16) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 1, 0, false, false, true>), g, b, 0, st, a);
-                else if (a.dh1_slab) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 3, 0, false, true, true>), g, b, 0, st, a);
-                else hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 3, 0, false, false, true>), g, b, 0, st, a);
+                else if (a.dh1_slab) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_bwd_x6<false, true, NP, 0, false, true, true>), g, b, 0, st, a));
+                else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_bwd_x6<false, true, NP, 0, false, false, true>), g, b, 0, st, a));
                 return hipGetLastError();
             }
             if (math == MATH_BF16 && a.n16) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 1, 0, true>), g, b, 0, st, a);
             else if (math == MATH_BF16) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 1>), g, b, 0, st, a);
-            else if (a.dh1_slab) hipLaunchKernelGGL((k_edge_bwd_x6<false, true, 3, 0, false, true>), g, b, 0, st, a);
-            else hipLaunchKernelGGL((k_edge_bwd_x6<false, true>), g, b, 0, st, a);
+            else if (a.dh1_slab) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_bwd_x6<false, true, NP, 0, false, true>), g, b, 0, st, a));
+            else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_bwd_x6<false, true, NP>), g, b, 0, st, a));
             return hipGetLastError();
         }
 #ifdef SPWGNN_DIAG   // per-step dA read-add-writes (SPWGNN_DA_RMW A/B builds only: 2.6x slower, §3f)
-        if (math != MATH_X6) return hipErrorInvalidValue;
-        if (a.dA_accumulate) hipLaunchKernelGGL((k_edge_bwd_x6<true>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((k_edge_bwd_x6<false>), g, b, 0, st, a);
+        if (!math_split32(math)) return hipErrorInvalidValue;
+        if (a.dA_accumulate) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_bwd_x6<true, false, NP>), g, b, 0, st, a));
+        else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_bwd_x6<false, false, NP>), g, b, 0, st, a));
         return hipGetLastError();
 #else
         return hipErrorInvalidValue;
@@ -1100,7 +1124,7 @@ hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st) {
 // of its first rebuilt pair, where the accumulators are zero and acc is free.
 template <int NP = 3, bool B16 = false, bool SLAB = false>
 __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_dA_x6(DaArgs a) {
-    static_assert(!SLAB || (NP == 3 && !B16), "stored dh1pre steps: x6 only");
+    static_assert(!SLAB || (NP >= 2 && !B16), "stored dh1pre steps: x6 / x3 only");
     // bf16 math (NP = 1): a k-block is 5 MFMAs, so the G3 rows run further ahead to cover HBM latency
     constexpr int kWaves = 8, PF = NP == 1 ? SPWGNN_DA_PF_B16 : 2;
     static_assert(10 % PF == 0, "ring slots carry over between (block, step) pairs");
@@ -1296,32 +1320,32 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 }
 
 hipError_t launch_dA(const DaArgs& a, int math, hipStream_t st) {
-    if (a.n_stored > 0 && (math != MATH_X6 || team_blocks(a.n_eblocks))) return hipErrorInvalidValue;
-    if ((math == MATH_X6 || math == MATH_BF16) && team_blocks(a.n_eblocks)) return launch_dA_team(a, math, st);
+    if (a.n_stored > 0 && (!math_split32(math) || team_blocks(a.n_eblocks))) return hipErrorInvalidValue;
+    if ((math_split32(math) || math == MATH_BF16) && team_blocks(a.n_eblocks)) return launch_dA_team(a, math, st);
     const dim3 g(edge_grid(a.n_eblocks, 8)), b(512);
     if (math == MATH_BF16 && a.b16) hipLaunchKernelGGL((k_dA_x6<1, true>), g, b, 0, st, a);
     else if (math == MATH_BF16) hipLaunchKernelGGL((k_dA_x6<1>), g, b, 0, st, a);
     else if (a.n_stored > 0) {
         if (a.n_stored >= a.S || !a.slab || a.b16) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_dA_x6<3, false, true>), g, b, 0, st, a);
-    } else hipLaunchKernelGGL((k_dA_x6<3>), g, b, 0, st, a);
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_dA_x6<NP, false, true>), g, b, 0, st, a));
+    } else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_dA_x6<NP>), g, b, 0, st, a));
     return hipGetLastError();
 }
 hipError_t launch_enc_edge_bwd(const EncEdgeBwdArgs& a, int math, hipStream_t st) {
     // one 32-edge block per wave at two waves per SIMD, weight images shared by the workgroup's 4
     // waves (x6: 2.44 → 2.33 ms against two blocks per wave at one wave per SIMD with per-wave rings)
     constexpr int NC = 1, NW = 4, NWB = SPWGNN_ENC_NW_B16;   // bf16: waves sharing one weight pass
-    if ((math == MATH_X6 || math == MATH_BF16) && team_blocks(a.n_eblocks)) return launch_enc_edge_bwd_team(a, math, st);
+    if ((math_split32(math) || math == MATH_BF16) && team_blocks(a.n_eblocks)) return launch_enc_edge_bwd_team(a, math, st);
     const dim3 g((a.n_eblocks + 4 * NC - 1) / (4 * NC)), gb((a.n_eblocks + NWB * NC - 1) / (NWB * NC));
     if (math == MATH_BF16) {
         if (a.b16) hipLaunchKernelGGL((k_enc_edge_bwd_x6<NC, 1, true, NWB>), gb, dim3(64 * NWB), 0, st, a);
         else hipLaunchKernelGGL((k_enc_edge_bwd_x6<NC, 1, false, NW>), g, dim3(256), 0, st, a);
         return hipGetLastError();
     }
-    if (math == MATH_X6) {
+    if (math_split32(math)) {
         constexpr int NWX = SPWGNN_ENC_NW_X6;
         const dim3 gx((a.n_eblocks + NWX * NC - 1) / (NWX * NC));
-        hipLaunchKernelGGL((k_enc_edge_bwd_x6<NC, 3, false, NWX>), gx, dim3(64 * NWX), 0, st, a);
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_edge_bwd_x6<NC, NP, false, NWX>), gx, dim3(64 * NWX), 0, st, a));
         return hipGetLastError();
     }
     hipLaunchKernelGGL(k_enc_edge_bwd, dim3((a.n_eblocks + 3) / 4), dim3(256), 0, st, a);
@@ -1384,7 +1408,7 @@ hipError_t launch_enc_node_bwd(const EncNodeBwdArgs& a, int math, hipStream_t st
     if (math != MATH_F32 && a.wo1ct && a.x_wo1ct && a.x_om1t) {
         if (team_blocks(waves)) return launch_enc_node_bwd_team(a, math, st);   // small batches
         if (math == MATH_BF16) hipLaunchKernelGGL((k_enc_node_bwd_x6<1, 4>), dim3((waves + 3) / 4), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_enc_node_bwd_x6<3, 4>), dim3((waves + 3) / 4), dim3(256), 0, st, a);
+        else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_node_bwd_x6<NP, 4>), dim3((waves + 3) / 4), dim3(256), 0, st, a));
         return hipGetLastError();
     }
     hipLaunchKernelGGL(k_enc_node_bwd, dim3((waves + 3) / 4), dim3(256), 0, st, a);

@@ -875,10 +875,10 @@ struct NodeSumX6 {
                 uint32_t hw[4], mw[4], lw[4];
 #pragma unroll
                 for (int m = 0; m < 4; ++m) split2(h2[t][8 * s + 2 * m], h2[t][8 * s + 2 * m + 1], hw[m], mw[m], lw[m]);
-                if constexpr (NP == 3) {
+                if constexpr (NP == 3)
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], as_bf16x8(make_uint4(lw[0], lw[1], lw[2], lw[3])), acc[t], 0, 0, 0);
+                if constexpr (NP >= 2)   // x3: the sum of the 2-part roundings
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], as_bf16x8(make_uint4(mw[0], mw[1], mw[2], mw[3])), acc[t], 0, 0, 0);
-                }
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], as_bf16x8(make_uint4(hw[0], hw[1], hw[2], hw[3])), acc[t], 0, 0, 0);
             }
         }
@@ -1457,9 +1457,9 @@ hipError_t launch_prep(const PrepArgs& a, const PrepX6Args* x, hipStream_t st) {
 hipError_t launch_enc_node(const EncNodeArgs& a, int math, hipStream_t st) {
     const int waves = (a.n_nodes + 31) / 32;
     if (a.uv16 && math != MATH_BF16) return hipErrorInvalidValue;   // rounded U0, V0: the bf16 kernels only
-    if ((math == MATH_X6 || math == MATH_BF16) && team_blocks(waves)) return launch_enc_node_team(a, math, st);
-    if (math == MATH_X6) {
-        hipLaunchKernelGGL((k_enc_node_x6<3, 4>), dim3((waves + 3) / 4), dim3(256), 0, st, a);
+    if ((math_split32(math) || math == MATH_BF16) && team_blocks(waves)) return launch_enc_node_team(a, math, st);
+    if (math_split32(math)) {
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_node_x6<NP, 4>), dim3((waves + 3) / 4), dim3(256), 0, st, a));
         return hipGetLastError();
     }
     if (math == MATH_BF16) {
@@ -1471,8 +1471,8 @@ hipError_t launch_enc_node(const EncNodeArgs& a, int math, hipStream_t st) {
 }
 hipError_t launch_enc_edge(const EncEdgeArgs& a, int math, hipStream_t st) {
     const bool train = a.z1 || a.ed;   // z1 null with ed set: training, z1 rebuilt by the W1 gradient
-    if ((math == MATH_X6 || math == MATH_BF16) && team_blocks(a.n_eblocks)) return launch_enc_edge_team(a, math, train, st);
-    if (math == MATH_X6 || math == MATH_BF16) {
+    if ((math_split32(math) || math == MATH_BF16) && team_blocks(a.n_eblocks)) return launch_enc_edge_team(a, math, train, st);
+    if (math_split32(math) || math == MATH_BF16) {
         // one 32-edge block per wave at two waves per SIMD, weight images shared by the workgroup's
         // 4 waves (x6: 2.48 → 2.11 ms against two blocks per wave at one wave per SIMD, per-wave rings)
         constexpr int NC = 1, NW = 4, NWB = SPWGNN_ENC_NW_B16;   // bf16: waves sharing one weight pass
@@ -1484,9 +1484,9 @@ hipError_t launch_enc_edge(const EncEdgeArgs& a, int math, hipStream_t st) {
         } else if (train) {
             constexpr int NWX = SPWGNN_ENC_NW_X6;
             const dim3 gx((a.n_eblocks + NWX * NC - 1) / (NWX * NC));
-            hipLaunchKernelGGL((k_enc_edge_x6<true, NC, 3, false, NWX>), gx, dim3(64 * NWX), 0, st, a);
+            SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_edge_x6<true, NC, NP, false, NWX>), gx, dim3(64 * NWX), 0, st, a));
         } else {
-            hipLaunchKernelGGL((k_enc_edge_x6<false, NC, 3, false, NW>), g, dim3(256), 0, st, a);
+            SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_edge_x6<false, NC, NP, false, NW>), g, dim3(256), 0, st, a));
         }
         return hipGetLastError();
     }
@@ -1514,7 +1514,7 @@ hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
     if (a.nw_max > kNwMaxLimit) return hipErrorInvalidValue;  // one-hot rows: ≤ 32 nodes per wave-tile
     if ((a.uv16 == kUvB16) != (a.n16 != 0)) return hipErrorInvalidValue;   // bf16 U, V: the N16 kernel reads them
     // small batches: a workgroup of five waves per wave-tile, one output tile per wave (kernels_team.hip)
-    if ((math == MATH_X6 || math == MATH_BF16) && a.nw_max <= 16 && team_blocks(a.n_wtiles))
+    if ((math_split32(math) || math == MATH_BF16) && a.nw_max <= 16 && team_blocks(a.n_wtiles))
         return a.n16 ? hipErrorInvalidValue : launch_edge_fwd_team(a, math, st);   // team kernels: fp32 H2s
     if (a.n16 && (math != MATH_BF16 || a.nw_max > 16 || !a.a_b16)) return hipErrorInvalidValue;
     if (math == MATH_BF16 && a.n16) {
@@ -1557,22 +1557,23 @@ hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
             hipLaunchKernelGGL((k_edge_fwd_x6<false, 0, 1>), dim3(edge_grid(a.n_wtiles, 4)), dim3(256), 0, st, a);
         return hipGetLastError();
     }
-    if (math == MATH_X6 && a.recv_blocks) {   // receiver blocks: column sums (spwgnn_plan_fill_recv)
+    if (math_split32(math) && a.recv_blocks) {   // receiver blocks: column sums (spwgnn_plan_fill_recv)
         int cus = 0, dev = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
             cus = 256;
         const int need = (a.n_nodes + 8 * 16 - 1) / (8 * 16);   // ≥ 16 blocks per wave
         const dim3 g(std::max(1, std::min(cus, need))), b(512);
-        if (a.mask1 || a.mask2) hipLaunchKernelGGL((k_edge_fwd_rb_x6<3, true>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((k_edge_fwd_rb_x6<3, false>), g, b, 0, st, a);
+        if (a.mask1 || a.mask2) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_fwd_rb_x6<NP, true>), g, b, 0, st, a));
+        else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_fwd_rb_x6<NP, false>), g, b, 0, st, a));
         return hipGetLastError();
     }
-    if (math == MATH_X6) {
-#ifdef SPWGNN_DIAG   // 1: A rows from 8 cached blocks (diagnosis only: wrong results)
+    if (math_split32(math)) {
+#ifdef SPWGNN_DIAG   // 1: A rows from 8 cached blocks (diagnosis only: wrong results; x6 only)
         static const int dbg = getenv("SPWGNN_EFWD_DBG") ? atoi(getenv("SPWGNN_EFWD_DBG")) : 0;
 #else
         constexpr int dbg = 0;
 #endif
+        if (dbg && math != MATH_X6) return hipErrorInvalidValue;
         if (a.nw_max <= 16 && dbg == 1)   // diagnosis: A rows from 8 cached blocks
             hipLaunchKernelGGL((k_edge_fwd_x6<true, 1>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
 #ifdef SPWGNN_DIAG
@@ -1580,12 +1581,12 @@ hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
             hipLaunchKernelGGL((k_edge_fwd_x6<true, 2>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
 #endif
         else if (a.nw_max <= 16 && kEfwdUv0 && a.uv_zero)
-            launch_edge_fwd16<3, false, false, true>(a, st);
+            SPW_SPLIT32(math, NP, (launch_edge_fwd16<NP, false, false, true>(a, st)));
         else if (a.nw_max <= 16)
-            launch_edge_fwd16<3, false, false, false>(a, st);
+            SPW_SPLIT32(math, NP, (launch_edge_fwd16<NP, false, false, false>(a, st)));
         else   // ≤ 32-node tiles: two waves per SIMD (config 5: 37.5 -> 34.4 ms per forward, A/B on one box;
                // 36 spilled registers, an inference-only instantiation without the mask code spills 612)
-            hipLaunchKernelGGL((k_edge_fwd_x6<false, 0, 3, false, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
+            SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_fwd_x6<false, 0, NP, false, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a));
         return hipGetLastError();
     }
     if (a.nw_max <= 16)
@@ -1596,17 +1597,17 @@ hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
 }
 hipError_t launch_node_fwd(const NodeFwdArgs& a, int math, hipStream_t st) {
     if ((a.uv16 == kUvB16) != (a.n16 != 0) || (a.uv16 && math != MATH_BF16)) return hipErrorInvalidValue;
-    if ((math == MATH_X6 || math == MATH_BF16) && team_blocks((a.n_nodes + 31) / 32))
+    if ((math_split32(math) || math == MATH_BF16) && team_blocks((a.n_nodes + 31) / 32))
         return a.n16 ? hipErrorInvalidValue : launch_node_fwd_team(a, math, st);   // team kernels: fp32 arrays
     if (a.n16 && math != MATH_BF16) return hipErrorInvalidValue;
     const int waves = (a.n_nodes + 31) / 32;
-    if (math == MATH_X6) {
+    if (math_split32(math)) {
         // one 32-node column tile per wave at two waves per SIMD (measured: 0.58 vs 0.62 ms for
         // two column tiles at one wave per SIMD, 393K nodes), weight images shared by the
         // workgroup's 4 waves through an LDS ring (0.532 → 0.437 ms)
         constexpr int NC = 1;
         const int w2 = (waves + NC - 1) / NC;
-        hipLaunchKernelGGL((k_node_fwd_x6<NC, 3, 4>), dim3((w2 + 3) / 4), dim3(256), 0, st, a);
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_node_fwd_x6<NC, NP, 4>), dim3((w2 + 3) / 4), dim3(256), 0, st, a));
         return hipGetLastError();
     }
     if (math == MATH_BF16) {

@@ -457,7 +457,7 @@ struct X6Img {
         const int li = lane & 15, row = 4 * (lane >> 4) + (li >> 2);
         return row * ROWB + 32 * (t ^ sigma(row)) + 8 * ((li & 3) ^ gsw(row));
     }
-    // NP = 1 (bf16 math): the h part only
+    // NP = 1 (bf16 math): the h part only; NP = 2 (x3 math): h and m
     template <int NP = 3>
     __device__ static __forceinline__ void put(char* S, int rr, int c4, float4 v) {
         uint32_t h0, m0, l0, h1, m1, l1;
@@ -465,10 +465,8 @@ struct X6Img {
         split2(v.z, v.w, h1, m1, l1);
         char* p = S + woff(rr, c4);
         *reinterpret_cast<uint2*>(p) = make_uint2(h0, h1);
-        if constexpr (NP == 3) {
-            *reinterpret_cast<uint2*>(p + PART) = make_uint2(m0, m1);
-            *reinterpret_cast<uint2*>(p + 2 * PART) = make_uint2(l0, l1);
-        }
+        if constexpr (NP >= 2) *reinterpret_cast<uint2*>(p + PART) = make_uint2(m0, m1);
+        if constexpr (NP == 3) *reinterpret_cast<uint2*>(p + 2 * PART) = make_uint2(l0, l1);
     }
     template <int NP = 3>
     __device__ static __forceinline__ void get(const char* S, int off, bf16x8 (&f)[3]) {
@@ -1435,12 +1433,13 @@ __device__ __forceinline__ void wgrad_ws_body(const WgWsArgs& a, int bid, char* 
             char* p = S + IX::woff(row, c4);
             const uint2 u = make_uint2(__float_as_uint(v.x) ^ __float_as_uint(v.y), __float_as_uint(v.z) ^ __float_as_uint(v.w));
             *reinterpret_cast<uint2*>(p) = u;
-            if constexpr (NP == 3) { *reinterpret_cast<uint2*>(p + IX::PART) = u; *reinterpret_cast<uint2*>(p + 2 * IX::PART) = u; }
+            if constexpr (NP >= 2) *reinterpret_cast<uint2*>(p + IX::PART) = u;
+            if constexpr (NP == 3) *reinterpret_cast<uint2*>(p + 2 * IX::PART) = u;
         } else if constexpr (DBG == 3) {
             uint32_t h0, m0, l0, h1, m1, l1;
             split2(v.x, v.y, h0, m0, l0);
             split2(v.z, v.w, h1, m1, l1);
-            dbg_sink ^= h0 ^ h1 ^ (NP == 3 ? (m0 ^ l0 ^ m1 ^ l1) : 0u);
+            dbg_sink ^= h0 ^ h1 ^ (NP >= 2 ? (m0 ^ m1) : 0u) ^ (NP == 3 ? (l0 ^ l1) : 0u);
         } else {
             IX::template put<NP>(S, row, c4, v);
         }
@@ -1450,12 +1449,13 @@ __device__ __forceinline__ void wgrad_ws_body(const WgWsArgs& a, int bid, char* 
             char* p = S + IY::woff(row, c4);
             const uint2 u = make_uint2(__float_as_uint(v.x) ^ __float_as_uint(v.y), __float_as_uint(v.z) ^ __float_as_uint(v.w));
             *reinterpret_cast<uint2*>(p) = u;
-            if constexpr (NP == 3) { *reinterpret_cast<uint2*>(p + IY::PART) = u; *reinterpret_cast<uint2*>(p + 2 * IY::PART) = u; }
+            if constexpr (NP >= 2) *reinterpret_cast<uint2*>(p + IY::PART) = u;
+            if constexpr (NP == 3) *reinterpret_cast<uint2*>(p + 2 * IY::PART) = u;
         } else if constexpr (DBG == 3) {
             uint32_t h0, m0, l0, h1, m1, l1;
             split2(v.x, v.y, h0, m0, l0);
             split2(v.z, v.w, h1, m1, l1);
-            dbg_sink ^= h0 ^ h1 ^ (NP == 3 ? (m0 ^ l0 ^ m1 ^ l1) : 0u);
+            dbg_sink ^= h0 ^ h1 ^ (NP >= 2 ? (m0 ^ m1) : 0u) ^ (NP == 3 ? (l0 ^ l1) : 0u);
         } else {
             IY::template put<NP>(S, row, c4, v);
         }
@@ -1593,8 +1593,8 @@ __global__ __launch_bounds__(kWsThreads, 1) __attribute__((amdgpu_waves_per_eu(2
 void k_wgrad_ws_batch(WsBatch b, Pos3Batch p3) {
     __shared__ __attribute__((aligned(16))) char smem[2 * kWsMaxBuf];
     const int w2_first = (int)gridDim.x - b.w2_wgs;
-    if (NP == 3 && (int)blockIdx.x >= w2_first) {
-        w2grad_ws_body<0, 3, false>(b.w2, b.w2_bpw, (int)blockIdx.x - w2_first, reinterpret_cast<char (*)[2 * kW2gImg]>(smem));
+    if (NP != 1 && (int)blockIdx.x >= w2_first) {   // x6 and x3
+        w2grad_ws_body<0, NP == 1 ? 3 : NP, false>(b.w2, b.w2_bpw, (int)blockIdx.x - w2_first, reinterpret_cast<char (*)[2 * kW2gImg]>(smem));
         return;
     }
     if ((int)blockIdx.x >= b.wgs) {
@@ -1975,6 +1975,8 @@ hipError_t launch_wgrad(const WgradArgs& a, int chunks, int math, hipStream_t st
     if (a.xmode == XM && a.ymode == YM && a.kx_pad == KX && a.ny_pad == NY) {                 \
         if (math == MATH_X6)                                                           \
             hipLaunchKernelGGL((k_wgrad_x6<XM, YM, KX, NY, (XM == XM_H1 || YM == YM_ROW) ? 1 : 2>), g, b, 0, st, a); \
+        else if (math == MATH_X3)                                                             \
+            hipLaunchKernelGGL((k_wgrad_x6<XM, YM, KX, NY, (XM == XM_H1 || YM == YM_ROW) ? 1 : 2, 2>), g, b, 0, st, a); \
         else                                                                                  \
             hipLaunchKernelGGL((k_wgrad_t<XM, YM, KX, NY>), g, b, 0, st, a);                  \
         return hipGetLastError();                                                             \
@@ -2056,12 +2058,13 @@ hipError_t launch_w2grad_ws(const WgradArgs& a, int wgs, int64_t blk_per_wg, int
         else hipLaunchKernelGGL((k_w2grad_ws<0, 1, false, false>), g, b, 0, st, a, blk_per_wg);
         return hipGetLastError();
     }
-    if (a.a_b16) return hipErrorInvalidValue;
+    if (a.a_b16 || !math_split32(math)) return hipErrorInvalidValue;
     if (dbg == 0) {
-        if (a.gather_desc) hipLaunchKernelGGL(k_w2grad_ws<0>, g, b, 0, st, a, blk_per_wg);
-        else hipLaunchKernelGGL((k_w2grad_ws<0, 3, false, false>), g, b, 0, st, a, blk_per_wg);
+        if (a.gather_desc) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_w2grad_ws<0, NP>), g, b, 0, st, a, blk_per_wg));
+        else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_w2grad_ws<0, NP, false, false>), g, b, 0, st, a, blk_per_wg));
         return hipGetLastError();
     }
+    if (math != MATH_X6) return hipErrorInvalidValue;   // the diagnosis variants: x6 only
 #ifdef SPWGNN_DIAG
     switch (dbg) {
         case 1: hipLaunchKernelGGL(k_w2grad_ws<1>, g, b, 0, st, a, blk_per_wg); break;
@@ -2113,7 +2116,7 @@ hipError_t launch_wgrad_ws(const WgWsArgs& a, int wgs, int kx_pad, int ny_pad, i
 #define SPW_WS(V, KX, NY, YR, MK, XD)                                                              \
         case V:                                                                                     \
             if (bf) hipLaunchKernelGGL((k_wgrad_ws<KX, NY, YR, MK, 1, XD>), g, b, 0, st, a);        \
-            else hipLaunchKernelGGL((k_wgrad_ws<KX, NY, YR, MK, 3, XD>), g, b, 0, st, a);           \
+            else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_wgrad_ws<KX, NY, YR, MK, NP, XD>), g, b, 0, st, a)); \
             break;
         SPW_WS(WSV_160_160, 160, 160, 0, false, 0)
         SPW_WS(WSV_160_160_ROW, 160, 160, 1, false, 0)
@@ -2138,10 +2141,10 @@ hipError_t launch_wgrad_ws_batch(const WsBatch& b, int math, hipStream_t st, con
     if (b.n > kMaxWsJobs || b.wgs < 0 || (b.n > 0 && b.wgs == 0) || b.w2_wgs < 0) return hipErrorInvalidValue;
     Pos3Batch none{};
     const Pos3Batch& q = p3 ? *p3 : none;
-    if (b.w2_wgs && math != MATH_X6) return hipErrorInvalidValue;
+    if (b.w2_wgs && !math_split32(math)) return hipErrorInvalidValue;
     const dim3 g(b.wgs + (q.ce + q.cn + 1) / 2 + b.w2_wgs);
     if (math == MATH_BF16) hipLaunchKernelGGL(k_wgrad_ws_batch<1>, g, dim3(kWsThreads), 0, st, b, q);
-    else hipLaunchKernelGGL(k_wgrad_ws_batch<3>, g, dim3(kWsThreads), 0, st, b, q);
+    else SPW_SPLIT32(math, NP, hipLaunchKernelGGL(k_wgrad_ws_batch<NP>, g, dim3(kWsThreads), 0, st, b, q));
     return hipGetLastError();
 }
 // Small batches (every gradient ≤ kReduceSmallChunks slabs): one thread per element sums its slabs in

@@ -1165,10 +1165,10 @@ __device__ __forceinline__ void edge_bwd_team_body(const EdgeBwdArgs& a, int wt,
             uint32_t hw[4], mw[4], lw[4];
 #pragma unroll
             for (int m = 0; m < 4; ++m) split2(acc[8 * sh + 2 * m], acc[8 * sh + 2 * m + 1], hw[m], mw[m], lw[m]);
-            if constexpr (NP == 3) {
+            if constexpr (NP == 3)
                 nacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ao, as_bf16x8(make_uint4(lw[0], lw[1], lw[2], lw[3])), nacc, 0, 0, 0);
+            if constexpr (NP >= 2)   // x3: the sum of the 2-part roundings
                 nacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ao, as_bf16x8(make_uint4(mw[0], mw[1], mw[2], mw[3])), nacc, 0, 0, 0);
-            }
             nacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ao, as_bf16x8(make_uint4(hw[0], hw[1], hw[2], hw[3])), nacc, 0, 0, 0);
         }
     }
@@ -1422,8 +1422,8 @@ hipError_t launch_edge_fwd_team(const EdgeFwdArgs& a, int math, hipStream_t st) 
     if (math == MATH_BF16) {
         if (a.a_b16) hipLaunchKernelGGL((k_edge_fwd_team<1, true>), g, b, 0, st, a);
         else hipLaunchKernelGGL((k_edge_fwd_team<1, false>), g, b, 0, st, a);
-    } else if (math == MATH_X6 && !a.a_b16) {
-        hipLaunchKernelGGL((k_edge_fwd_team<3, false>), g, b, 0, st, a);
+    } else if (math_split32(math) && !a.a_b16) {
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_fwd_team<NP, false>), g, b, 0, st, a));
     } else {
         return hipErrorInvalidValue;
     }
@@ -1433,7 +1433,7 @@ hipError_t launch_edge_bwd_team(const EdgeBwdArgs& a, int math, hipStream_t st) 
     if (a.nw_max > 16 || !a.no_dA) return hipErrorInvalidValue;
     const dim3 g(a.n_wtiles), b(64 * kTeamEdge);
     if (math == MATH_BF16) hipLaunchKernelGGL((k_edge_bwd_team<1>), g, b, 0, st, a);
-    else if (math == MATH_X6) hipLaunchKernelGGL((k_edge_bwd_team<3>), g, b, 0, st, a);
+    else if (math_split32(math)) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_bwd_team<NP>), g, b, 0, st, a));
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -1441,14 +1441,14 @@ hipError_t launch_dA_team(const DaArgs& a, int math, hipStream_t st) {
     const dim3 g(a.n_eblocks), b(64 * kTeamEdge);
     if (math == MATH_BF16 && a.b16) hipLaunchKernelGGL((k_dA_team<1, true>), g, b, 0, st, a);
     else if (math == MATH_BF16) hipLaunchKernelGGL((k_dA_team<1, false>), g, b, 0, st, a);
-    else if (math == MATH_X6) hipLaunchKernelGGL((k_dA_team<3, false>), g, b, 0, st, a);
+    else if (math_split32(math)) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_dA_team<NP, false>), g, b, 0, st, a));
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 hipError_t launch_enc_node_bwd_team(const EncNodeBwdArgs& a, int math, hipStream_t st) {
     const dim3 g((a.n_nodes + 31) / 32), b(256);
     if (math == MATH_BF16) hipLaunchKernelGGL((k_enc_node_bwd_team<1>), g, b, 0, st, a);
-    else if (math == MATH_X6) hipLaunchKernelGGL((k_enc_node_bwd_team<3>), g, b, 0, st, a);
+    else if (math_split32(math)) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_node_bwd_team<NP>), g, b, 0, st, a));
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -1458,9 +1458,9 @@ hipError_t launch_enc_edge_team(const EncEdgeArgs& a, int math, bool train, hipS
         if (train && a.b16) hipLaunchKernelGGL((k_enc_edge_team<true, 1, true>), g, b, 0, st, a);
         else if (train) hipLaunchKernelGGL((k_enc_edge_team<true, 1, false>), g, b, 0, st, a);
         else hipLaunchKernelGGL((k_enc_edge_team<false, 1, false>), g, b, 0, st, a);
-    } else if (math == MATH_X6) {
-        if (train) hipLaunchKernelGGL((k_enc_edge_team<true, 3, false>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((k_enc_edge_team<false, 3, false>), g, b, 0, st, a);
+    } else if (math_split32(math)) {
+        if (train) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_edge_team<true, NP, false>), g, b, 0, st, a));
+        else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_edge_team<false, NP, false>), g, b, 0, st, a));
     } else {
         return hipErrorInvalidValue;
     }
@@ -1470,12 +1470,12 @@ hipError_t launch_enc_node_team(const EncNodeArgs& a, int math, hipStream_t st) 
     if (a.uv16 == kUvB16) return hipErrorInvalidValue;
     const dim3 g((a.n_nodes + 31) / 32), b(64 * kTeamEdge);
     if (math == MATH_BF16) hipLaunchKernelGGL((k_enc_node_team<1>), g, b, 0, st, a);
-    else if (math == MATH_X6) hipLaunchKernelGGL((k_enc_node_team<3>), g, b, 0, st, a);
+    else if (math_split32(math)) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_node_team<NP>), g, b, 0, st, a));
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 bool enc_pair_team(int n_eblocks, int n_nodes, int math) {
-    return (math == MATH_X6 || math == MATH_BF16) && team_blocks(n_eblocks) && team_blocks((n_nodes + 31) / 32);
+    return (math_split32(math) || math == MATH_BF16) && team_blocks(n_eblocks) && team_blocks((n_nodes + 31) / 32);
 }
 hipError_t launch_enc_pair_team(const EncEdgeArgs& e, const EncNodeArgs& n, int math, bool train, hipStream_t st) {
     if (!enc_pair_team(e.n_eblocks, n.n_nodes, math) || n.uv16 == kUvB16) return hipErrorInvalidValue;
@@ -1485,9 +1485,9 @@ hipError_t launch_enc_pair_team(const EncEdgeArgs& e, const EncNodeArgs& n, int 
         else if (train) hipLaunchKernelGGL((k_enc_pair_team<true, 1, false>), g, b, 0, st, e, n);
         else hipLaunchKernelGGL((k_enc_pair_team<false, 1, false>), g, b, 0, st, e, n);
     } else if (train) {
-        hipLaunchKernelGGL((k_enc_pair_team<true, 3, false>), g, b, 0, st, e, n);
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_pair_team<true, NP, false>), g, b, 0, st, e, n));
     } else {
-        hipLaunchKernelGGL((k_enc_pair_team<false, 3, false>), g, b, 0, st, e, n);
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_pair_team<false, NP, false>), g, b, 0, st, e, n));
     }
     return hipGetLastError();
 }
@@ -1505,9 +1505,9 @@ hipError_t launch_fwd_fused_team(const FwdFusedArgs& a, int math, bool train, hi
         else if (train) hipLaunchKernelGGL((k_fwd_fused_team<true, 1, false>), g, b, 0, st, a);
         else if (!a.ee.b16) hipLaunchKernelGGL((k_fwd_fused_team<false, 1, false>), g, b, 0, st, a);
         else return hipErrorInvalidValue;
-    } else if (math == MATH_X6 && !a.ee.b16) {
-        if (train) hipLaunchKernelGGL((k_fwd_fused_team<true, 3, false>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((k_fwd_fused_team<false, 3, false>), g, b, 0, st, a);
+    } else if (math_split32(math) && !a.ee.b16) {
+        if (train) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_fwd_fused_team<true, NP, false>), g, b, 0, st, a));
+        else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_fwd_fused_team<false, NP, false>), g, b, 0, st, a));
     } else {
         return hipErrorInvalidValue;
     }
@@ -1520,7 +1520,7 @@ hipError_t launch_bwd_fused_team(const BwdFusedArgs& a, int math, hipStream_t st
     const dim3 g(a.eb.n_wtiles), b(64 * kTeamEdge);
     if (math == MATH_BF16 && a.da.b16) hipLaunchKernelGGL((k_bwd_fused_team<1, true>), g, b, 0, st, a);
     else if (math == MATH_BF16) hipLaunchKernelGGL((k_bwd_fused_team<1, false>), g, b, 0, st, a);
-    else if (math == MATH_X6 && !a.da.b16) hipLaunchKernelGGL((k_bwd_fused_team<3, false>), g, b, 0, st, a);
+    else if (math_split32(math) && !a.da.b16) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_bwd_fused_team<NP, false>), g, b, 0, st, a));
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -1531,7 +1531,7 @@ hipError_t launch_bwd_enc_pair_team(const DaArgs& da, const EncEdgeBwdArgs& eeb,
     const dim3 g(da.n_eblocks + (enb.n_nodes + 31) / 32), b(64 * kTeamEdge);
     if (math == MATH_BF16 && da.b16) hipLaunchKernelGGL((k_bwd_enc_pair_team<1, true>), g, b, 0, st, da, eeb, enb, with_dA);
     else if (math == MATH_BF16) hipLaunchKernelGGL((k_bwd_enc_pair_team<1, false>), g, b, 0, st, da, eeb, enb, with_dA);
-    else if (math == MATH_X6 && !da.b16) hipLaunchKernelGGL((k_bwd_enc_pair_team<3, false>), g, b, 0, st, da, eeb, enb, with_dA);
+    else if (math_split32(math) && !da.b16) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_bwd_enc_pair_team<NP, false>), g, b, 0, st, da, eeb, enb, with_dA));
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -1539,7 +1539,7 @@ hipError_t launch_node_fwd_team(const NodeFwdArgs& a, int math, hipStream_t st) 
     if (a.uv16 == kUvB16) return hipErrorInvalidValue;
     const dim3 g((a.n_nodes + 31) / 32), b(64 * kTeamEdge);
     if (math == MATH_BF16) hipLaunchKernelGGL((k_node_fwd_team<1>), g, b, 0, st, a);
-    else if (math == MATH_X6) hipLaunchKernelGGL((k_node_fwd_team<3>), g, b, 0, st, a);
+    else if (math_split32(math)) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_node_fwd_team<NP>), g, b, 0, st, a));
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -1547,7 +1547,7 @@ hipError_t launch_node_bwd_team(const NodeBwdArgs& a, int math, hipStream_t st) 
     if (!a.dco_sum) return hipErrorInvalidValue;
     const dim3 g((a.n_nodes + 31) / 32), b(64 * kTeamEdge);
     if (math == MATH_BF16) hipLaunchKernelGGL((k_node_bwd_team<1>), g, dim3(256), 0, st, a);
-    else if (math == MATH_X6) hipLaunchKernelGGL((k_node_bwd_team<3>), g, dim3(256), 0, st, a);
+    else if (math_split32(math)) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_node_bwd_team<NP>), g, dim3(256), 0, st, a));
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -1556,8 +1556,8 @@ hipError_t launch_enc_edge_bwd_team(const EncEdgeBwdArgs& a, int math, hipStream
     if (math == MATH_BF16) {
         if (a.b16) hipLaunchKernelGGL((k_enc_edge_bwd_team<1, true>), g, b, 0, st, a);
         else hipLaunchKernelGGL((k_enc_edge_bwd_team<1, false>), g, b, 0, st, a);
-    } else if (math == MATH_X6) {
-        hipLaunchKernelGGL((k_enc_edge_bwd_team<3, false>), g, b, 0, st, a);
+    } else if (math_split32(math)) {
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_edge_bwd_team<NP, false>), g, b, 0, st, a));
     } else {
         return hipErrorInvalidValue;
     }

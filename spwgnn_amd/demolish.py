@@ -50,7 +50,7 @@ def stability_sums(net: Net, towers_raw: np.ndarray, mode: str = "sum_prob") -> 
     objects = (towers_raw / RELATION_THRESHOLD).astype(np.float32)
     batch = TowerBatch.fully_connected(objects, device=g.device)
     with torch.no_grad():
-        z = E.forward(g.flat.detach(), batch, E.RunConfig(g.mp_steps, training=False), E.Workspace(g.device))
+        z = E.forward(g.flat.detach(), batch, g.run_config(), E.Workspace(g.device))
         return E.tower_readout(z, batch, mode)
 
 
@@ -72,7 +72,7 @@ def stability_gradients(net: Net, towers_raw: np.ndarray, mode: str = "sum_prob"
     objects = (towers_raw / RELATION_THRESHOLD).astype(np.float32)
     batch = TowerBatch.fully_connected(objects, device=g.device)
     flat = g.flat.detach()
-    run = E.RunConfig(g.mp_steps, training=True, dropout=0.0)
+    run = g.run_config(True, dropout=0.0)
     ws = E.Workspace(g.device)
     with torch.no_grad():
         z = E.forward(flat, batch, run, ws)

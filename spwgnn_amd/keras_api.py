@@ -138,7 +138,7 @@ class KerasModel:
         objects = np.asarray(x["objects"], np.float32)
         B, N = objects.shape[:2]
         out = np.zeros((B, N, 1), np.float32)
-        run = E.RunConfig(self.net.mp_steps, training=False)
+        run = self.net.run_config()
         for b0 in range(0, B, batch_size):
             sl = slice(b0, min(B, b0 + batch_size))
             prop = x.get("propagation")
@@ -158,7 +158,7 @@ class KerasModel:
         with the divisor max(#non-zero weights, 1) (one host sync to count them)."""
         net = self.net
         net._step_seed += 1
-        run = E.RunConfig(net.mp_steps, training=True, dropout=net.dropout, seed=net._step_seed)
+        run = net.run_config(True, dropout=net.dropout, seed=net._step_seed)
         z = E.forward(net.flat.data, batch, run, self._ws)
         out3, dz = E.bce(z, target, self._bce, node_weights=self._dev_weights(node_weights))
         E.backward(net.flat.data, batch, run, self._ws, dz, grads=self._grads)
@@ -187,7 +187,7 @@ class KerasModel:
                 pro.key, pro.step, pro.mode = ctr.key, ctr.step, _lib.STEP_KEY_COUNTER
             else:
                 E.step_advance(ctr.key, ctr.step, _lib.STEP_KEY_COUNTER)
-            run = E.RunConfig(net.mp_steps, training=True, dropout=net.dropout, seed_dev=ctr.key, prologue=pro)
+            run = net.run_config(True, dropout=net.dropout, seed_dev=ctr.key, prologue=pro)
             E.forward(net.flat.data, batch, run, ws, logits=z)
             # loss + epoch sums and the backward in one call: on the fused small-batch loop the loss
             # needs no launch of its own (spwgnn_bce_backward); weights / norm: a weighted fit's per-node
@@ -201,7 +201,7 @@ class KerasModel:
     def evaluate_batch(self, batch: TowerBatch, target: torch.Tensor, node_weights=None, norm=None):
         """out3 = [loss, correct, n] of an inference forward; `node_weights` / `norm` as engine.bce takes
         them (norm None: the non-zero weights are counted, one host sync)."""
-        run = E.RunConfig(self.net.mp_steps, training=False)
+        run = self.net.run_config()
         z = E.forward(self.net.flat.data, batch, run, self._ws)
         out3, _ = E.bce(z, target, self._bce, node_weights=self._dev_weights(node_weights), norm=norm)
         return out3
@@ -311,7 +311,11 @@ class PropagationNetwork:
     """Networks.py:12-104: getModel caches one compiled model per n_objects, all sharing the
     weights of the first one built (set_weights / reuse_model, Networks.py:40-56)."""
 
-    def __init__(self, device="cuda", seed: int = 0, mp_steps: int = E.REF_MP_STEPS, dropout: float = E.REF_DROPOUT):
+    def __init__(self, device="cuda", seed: int = 0, mp_steps: int = E.REF_MP_STEPS, dropout: float = E.REF_DROPOUT,
+                 math: str = "x6"):
+        if math not in E.MATH_MODES:
+            raise ValueError(f"math must be one of {sorted(E.MATH_MODES)}")
+        self._math = math   # every model's arithmetic (GraphNetwork.math); "x6": the fp32-class default
         self.Nets: Dict[int, KerasModel] = {}
         self.set_weights = False
         self._net: Optional[GraphNetwork] = None
@@ -321,7 +325,7 @@ class PropagationNetwork:
         if n_objects in self.Nets:
             return self.Nets[n_objects]
         if not self.set_weights:
-            self._net = GraphNetwork(self._mp, self._drop, self._seed, device=self._device)
+            self._net = GraphNetwork(self._mp, self._drop, self._seed, device=self._device, math=self._math)
             self.set_weights = True
         model = KerasModel(self._net, n_objects, object_dim)
         self.Nets[n_objects] = model

@@ -43,12 +43,17 @@ class GraphNetwork(nn.Module):
     """Propagation network (rm, om, rmp, omp) with shared weights across sizes and steps.
 
     ``mp_steps`` defaults to the reference's 5 (Networks.py:83); ``dropout`` to its 0.1 on the
-    two encodings (Networks.py:77-78), active only in training mode.
+    two encodings (Networks.py:77-78), active only in training mode. ``math`` ("x6" by default, the
+    fp32-class parity path; "x3", "bf16", "f32": `engine.MATH_MODES`) is the arithmetic of the matrix
+    products in training, inference and `forward_pooled`.
     """
 
     def __init__(self, mp_steps: int = E.REF_MP_STEPS, dropout: float = E.REF_DROPOUT, seed: int = 0,
-                 device="cuda", params: Optional[Dict[str, np.ndarray]] = None):
+                 device="cuda", params: Optional[Dict[str, np.ndarray]] = None, math: str = "x6"):
         super().__init__()
+        if math not in E.MATH_MODES:
+            raise ValueError(f"math must be one of {sorted(E.MATH_MODES)}")
+        self.math = math          # the matrix-product arithmetic of every run this network builds (engine.RunConfig.math)
         self.mp_steps = mp_steps
         self.dropout = dropout
         init = params if params is not None else P.glorot_uniform(seed)
@@ -66,6 +71,10 @@ class GraphNetwork(nn.Module):
         with torch.no_grad():
             self.flat.copy_(P.to_flat(params, device=self.flat.device))
 
+    def run_config(self, training: bool = False, **kw) -> E.RunConfig:
+        """A `RunConfig` of this network's step count and math (the front ends build theirs with it)."""
+        return E.RunConfig(self.mp_steps, training=training, math=self.math, **kw)
+
     def _run(self, input_grad: bool = False) -> E.RunConfig:
         need_grad = torch.is_grad_enabled() and (self.flat.requires_grad or input_grad)
         drop = self.training and self.dropout > 0 and need_grad
@@ -73,7 +82,8 @@ class GraphNetwork(nn.Module):
         if drop:
             self._step_seed += 1
             seed = self._step_seed
-        return E.RunConfig(self.mp_steps, training=need_grad, dropout=self.dropout if drop else 0.0, seed=seed)
+        return E.RunConfig(self.mp_steps, training=need_grad, dropout=self.dropout if drop else 0.0, seed=seed,
+                           math=self.math)
 
     def forward_batch(self, batch: TowerBatch, prop: Optional[torch.Tensor] = None,
                       objects: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -128,5 +138,5 @@ class GraphNetwork(nn.Module):
         ``objects`` included; `demolish.stability_gradients` gives d(readout)/d objects)."""
         batch = TowerBatch.from_dense(objects, sender_relations, receiver_relations, propagation, device=self.device)
         with torch.no_grad():
-            z = E.forward(self.flat.detach(), batch, E.RunConfig(self.mp_steps, training=False), E.Workspace(self.device))
+            z = E.forward(self.flat.detach(), batch, self.run_config(), E.Workspace(self.device))
             return E.tower_readout(z, batch, mode)
