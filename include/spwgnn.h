@@ -21,14 +21,15 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
 #define SPWGNN_E_SHAPE (-2)         /* shape outside what the kernels support                 */
 #define SPWGNN_E_RELATION (-3)      /* relation matrix column is not one-hot / both-or-neither */
 #define SPWGNN_E_WORKSPACE (-4)     /* workspace smaller than spwgnn_workspace_bytes()        */
-#define SPWGNN_E_CAPACITY (-5)      /* caller-provided output array too small                 */
+#define SPWGNN_E_CAPACITY (-5)      /* caller-provided output array too small; device plans: a tower holds
+                                     * more relations than its edge capacity                  */
 #define SPWGNN_E_NOTRAIN (-6)       /* backward on a workspace run with training == 0         */
 
 typedef void* spwgnn_stream_t;      /* a hipStream_t (NULL = default stream) */
@@ -47,7 +48,7 @@ typedef struct spwgnn_param_info {
 int32_t spwgnn_version(void);
 /* sizeof the ABI structs as this library was compiled (bindings check their own layouts against it):
  * which = 0 spwgnn_batch, 1 spwgnn_run, 2 spwgnn_plan_sizes, 3 spwgnn_param_info,
- * 4 spwgnn_loss_weights; -1 otherwise. */
+ * 4 spwgnn_loss_weights, 6 spwgnn_plan_device; -1 otherwise (5 is not used and stays -1). */
 int32_t spwgnn_struct_size(int32_t which);
 const char* spwgnn_strerror(int32_t status);
 int32_t spwgnn_param_tensor_count(void);
@@ -118,6 +119,62 @@ int32_t spwgnn_plan_fill_recv(int32_t n_towers, const int32_t* tower_nodes, cons
                               const int32_t* src, const int32_t* dst, int32_t nw_max, const spwgnn_plan_sizes* sizes,
                               int32_t* wtile, int32_t* edge_src, int32_t* edge_dst, int32_t* edge_id,
                               uint8_t* blk_csr);
+
+/* ------------------------------------------------- device-side plans (added within ABI 8) -- */
+/* A capacity plan (spwgnn_plan_size_cap / spwgnn_plan_fill_cap) fixes its geometry — wtile, node_tower,
+ * node_local, the block count — from the tower sizes and capacities alone; only edge_src, edge_dst and
+ * blk_csr depend on the relation set. The two calls below fill those three on the DEVICE, from device
+ * positions (the thresholded relation set of main.py:71-81) or from device relation matrices (the
+ * semantics of spwgnn_dense_to_edges), exactly where spwgnn_plan_fill_cap puts them on the host: no
+ * host round trip, no synchronisation, one launch each, hipGraph-capturable. Build the geometry once
+ * per shape with spwgnn_plan_fill_cap given zero edges (tower_edges all 0, src = dst = NULL), upload
+ * wtile and node_local, and add wtile_tower[w] = the index of wave-tile w's first tower.
+ * Every pointer is device memory. wtile, node_local, wtile_tower (and tower_cap when given) are read
+ * only and may be shared between batches of one shape.
+ * Memory safety does not depend on the input data: an edge beyond its wave-tile's 32·#blocks slots, or
+ * beyond its tower's capacity, is not written; *status (the caller zeroes it) then takes, by an atomic
+ * max, the POSITIVE code −SPWGNN_E_CAPACITY; a relation column that spwgnn_dense_to_edges rejects
+ * gives −SPWGNN_E_RELATION (the column counts as inactive), a geometry the kernel cannot serve
+ * −SPWGNN_E_SHAPE. The arrays of a batch whose status is non-zero must not be run. */
+typedef struct spwgnn_plan_device {
+    int32_t n_towers;
+    int32_t n_nodes;
+    int32_t n_wtiles;
+    int32_t n_eblocks;
+    int32_t nw_max;             /* 1..32 */
+    int32_t reserved;           /* 0 */
+    const int32_t* wtile;       /* [n_wtiles][4] of the capacity plan                                */
+    const int32_t* node_local;  /* [n_nodes]; a node with node_local == 0 starts a tower             */
+    const int32_t* wtile_tower; /* [n_wtiles] index of each wave-tile's first tower                  */
+    const int32_t* tower_cap;   /* [n_towers] the capacities the geometry was sized with; NULL =
+                                 * N(N-1) per tower (every relation slot: cannot overflow)           */
+    int32_t* edge_src;          /* out [n_eblocks*32]                                                */
+    int32_t* edge_dst;          /* out [n_eblocks*32]                                                */
+    uint8_t* blk_csr;           /* out [n_eblocks][128], 16-byte aligned                             */
+    float* pos;                 /* out [n_nodes][4], 16-byte aligned: raw.xyz / divisor, 0 (positions
+                                 * source; NULL = not written; must be NULL for the dense source)    */
+    int32_t* tower_edges;       /* out [n_towers] active relations per tower; NULL = not written     */
+    int32_t* status;            /* in/out device word, see above                                     */
+    void** prof_events;         /* NULL, or two hipEvent_t recorded before / after the launch (the
+                                 * timing hook of spwgnn_run, kernel id SPWGNN_K_PLAN_DEVICE)        */
+} spwgnn_plan_device;
+
+/* Relations from positions: raw [n_nodes][raw_stride >= 2] fp32 raw-pixel rows (x, y[, w, …]) in the
+ * plan's node order. Slot (m, j != m) of a tower — the sender-major order of main.py:72-81 — is
+ * active iff dx·dx + dy·dy < threshold·threshold, every operation rounded to fp32 on its own (no
+ * contraction, no square root); threshold <= 0 or NaN = fully connected (JengaBuilder.py:309-326).
+ * pos (when given; needs raw_stride >= 3) = raw.xyz / divisor in IEEE fp32 division (main.py:91: 170).
+ * SPWGNN_E_ARG / SPWGNN_E_SHAPE before any device work for a null or misaligned pointer, sizes that do
+ * not agree, nw_max outside 1..32, raw_stride < 2, a zero or NaN divisor. */
+int32_t spwgnn_plan_device_positions(const spwgnn_plan_device* plan, const float* raw, int32_t raw_stride,
+                                     float threshold, float divisor, spwgnn_stream_t stream);
+/* Relations from dense matrices: Rs, Rr device fp32 [B][N][E], E = N(N-1), uniform towers (n_towers
+ * == B, n_nodes == B·N, 1 <= N <= nw_max). Column k of tower b is the edge (row holding Rs's 1 → row
+ * holding Rr's 1); no receiver = inactive; a value outside {0, 1}, two ones in a column or a receiver
+ * without a sender = −SPWGNN_E_RELATION in *status. Same argument checks; N < 1 is SPWGNN_E_ARG; the
+ * empty matrices of single-box towers (N == 1, E = 0) may be NULL. */
+int32_t spwgnn_plan_device_dense(const spwgnn_plan_device* plan, const float* Rs, const float* Rr, int32_t B,
+                                 int32_t N, spwgnn_stream_t stream);
 
 /* ------------------------------------------------------------------- device batch ------- */
 #define SPWGNN_BATCH_RECV_BLOCKS 1   /* spwgnn_batch.flags: the plan is a receiver-block plan */
@@ -224,6 +281,7 @@ int32_t spwgnn_math_products(int32_t math);
 #define SPWGNN_K_ENC_NODE 10
 #define SPWGNN_K_ENC_NODE_BWD 11
 #define SPWGNN_K_INPUT_BWD 12  /* spwgnn_backward_inputs' one launch */
+#define SPWGNN_K_PLAN_DEVICE 13 /* spwgnn_plan_device_positions / _dense's one launch (spwgnn_plan_device.prof_events) */
 
 /* Workspace bytes for (n_nodes, n_eblocks, mp_steps, training). */
 int64_t spwgnn_workspace_bytes(int32_t n_nodes, int32_t n_eblocks, int32_t mp_steps, int32_t training);

@@ -55,10 +55,22 @@ class LossWeightsC(C.Structure):
     _fields_ = [("w", C.c_void_p), ("norm_dev", C.c_void_p), ("norm", C.c_double)]
 
 
+class PlanDeviceC(C.Structure):
+    """spwgnn_plan_device: the static geometry and the output arrays of a device-filled plan (added
+    within ABI 8)."""
+    _fields_ = [("n_towers", C.c_int32), ("n_nodes", C.c_int32), ("n_wtiles", C.c_int32), ("n_eblocks", C.c_int32),
+                ("nw_max", C.c_int32), ("reserved", C.c_int32),
+                ("wtile", C.c_void_p), ("node_local", C.c_void_p), ("wtile_tower", C.c_void_p),
+                ("tower_cap", C.c_void_p), ("edge_src", C.c_void_p), ("edge_dst", C.c_void_p),
+                ("blk_csr", C.c_void_p), ("pos", C.c_void_p), ("tower_edges", C.c_void_p), ("status", C.c_void_p),
+                ("prof_events", C.c_void_p)]
+
+
 K_EDGE_FWD, K_NODE_FWD, K_EDGE_BWD, K_NODE_BWD, K_ENC_EDGE, K_ENC_EDGE_BWD, K_WGRAD_W2, K_DA = 1, 2, 3, 4, 5, 6, 7, 8
-K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD, K_INPUT_BWD = 9, 10, 11, 12
+K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD, K_INPUT_BWD, K_PLAN_DEVICE = 9, 10, 11, 12, 13
 MATH_F32, MATH_X6, MATH_BF16, MATH_X3 = 0, 1, 2, 3
 E_ARG, E_WORKSPACE, E_NOTRAIN = -1, -4, -6   # SPWGNN_E_* statuses the bindings name
+E_SHAPE, E_RELATION, E_CAPACITY = -2, -3, -5
 STEP_KEY_COUNTER, STEP_KEY_SPLITMIX = 0, 1
 ABI_VERSION = 8        # SPWGNN_ABI_VERSION this binding's structs follow
 BATCH_RECV_BLOCKS = 1  # spwgnn_batch.flags: a receiver-block plan (spwgnn_plan_fill_recv)
@@ -92,6 +104,8 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_forward": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp]),
         "spwgnn_backward": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp, vp]),
         "spwgnn_backward_inputs": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp]),
+        "spwgnn_plan_device_positions": (i32, [C.POINTER(PlanDeviceC), vp, i32, f32, f32, vp]),
+        "spwgnn_plan_device_dense": (i32, [C.POINTER(PlanDeviceC), vp, vp, i32, i32, vp]),
         "spwgnn_bce_scratch_bytes": (i64, [i64]),
         "spwgnn_bce": (i32, [vp, vp, i64, vp, vp, vp, vp]),
         "spwgnn_bce_accumulate": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp]),
@@ -127,7 +141,7 @@ def lib() -> C.CDLL:
         if lib_.spwgnn_version() != ABI_VERSION:
             raise SpwgnnError(f"{path} implements ABI {lib_.spwgnn_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild with `python -m spwgnn_amd.build`")
-        for which, st in enumerate((BatchC, RunC, PlanSizes, ParamInfo, LossWeightsC)):
+        for which, st in ((0, BatchC), (1, RunC), (2, PlanSizes), (3, ParamInfo), (4, LossWeightsC), (6, PlanDeviceC)):
             if lib_.spwgnn_struct_size(which) != C.sizeof(st):
                 raise SpwgnnError(f"{path} was built with a different {st.__name__} layout "
                                   f"({lib_.spwgnn_struct_size(which)} vs {C.sizeof(st)} bytes): rebuild it")

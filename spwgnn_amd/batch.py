@@ -241,6 +241,8 @@ class TowerBatch:
     node_perm: Optional[np.ndarray] = None   # packed plans (HostPlan.build pack=True): plan node i = input node node_perm[i]
     _cstruct: Optional[_lib.BatchC] = field(default=None, repr=False)
 
+    generation = 0   # refills of a device-built batch (DeviceTowerBatch.refill); part of engine.Workspace.key
+
     def to_plan_order(self, x):
         """Per-node rows (targets, propagation) in the input's node order → the plan's (identity
         unless the plan was packed). numpy or torch, first axis = nodes."""
@@ -374,6 +376,78 @@ class TowerBatch:
         pos = np.concatenate([np.asarray(o, np.float32) for o in objects_list], axis=0)
         return TowerBatch.from_edges(pos, tower_nodes, src, dst, np.array(tes, np.int32), None, device, nw_max)
 
+    # ------------------------------------------------------------------ plans built on the device
+    @staticmethod
+    def from_positions(raw: torch.Tensor, threshold: Optional[float] = 170.0, divisor: float = 170.0,
+                       tower_nodes=None, nw_max: Optional[int] = None, edge_cap=None, tower_ids=None,
+                       propagation: Optional[torch.Tensor] = None, check: bool = False) -> "DeviceTowerBatch":
+        """Raw-pixel positions on the device → batch, without a host round trip: ``raw`` (B, N, ≥3) or,
+        with ``tower_nodes`` (T,), (n_nodes, ≥3) rows [x, y, w] of consecutive ragged towers. The
+        relation set is the reference's thresholded one (raw-pixel distance < ``threshold``,
+        main.py:71-81; None, ≤ 0 or NaN: fully connected, JengaBuilder.py:309-326) and the node rows are
+        raw / ``divisor`` (main.py:91), both computed by one kernel (spwgnn_plan_device_positions) on a
+        capacity plan whose geometry is cached per shape (`plan_geometry`). ``edge_cap``: relations each
+        tower's blocks are sized for (default N(N−1), every slot; a lower cap gives fewer padding blocks
+        and is guarded by the status word). ``check=False`` never synchronises: the status stays on the
+        device as ``batch.status``; ``check=True`` reads it and raises `SpwgnnError` on an error."""
+        raw = _device_f32(raw, "raw")
+        if raw.dim() == 3 and tower_nodes is None:
+            B, N = int(raw.shape[0]), int(raw.shape[1])
+            tn, node_shape = _Uniform(B, N), (B, N)
+        elif raw.dim() == 2 and tower_nodes is not None:
+            tn, node_shape = np.ascontiguousarray(tower_nodes, dtype=np.int32), None
+        else:
+            raise ValueError("raw must be (B, N, 3), or (n_nodes, 3) with tower_nodes")
+        rows = raw.reshape(-1, raw.shape[-1])
+        if rows.shape[1] < 3:
+            raise ValueError("raw rows must hold at least (x, y, w)")
+        geom = plan_geometry(tn, nw_max, edge_cap, tower_ids, raw.device)
+        if rows.shape[0] != geom.n_nodes:
+            raise ValueError(f"raw has {rows.shape[0]} rows, towers hold {geom.n_nodes} nodes")
+        thr = 0.0 if threshold is None else float(threshold)
+        batch = DeviceTowerBatch(geom, ("positions", thr, float(divisor)), node_shape)
+        if propagation is not None:
+            batch.prop = _device_f32(propagation, "propagation").reshape(geom.n_nodes, 100)
+        batch._fill(rows)
+        if check:
+            batch.check()
+        return batch
+
+    @staticmethod
+    def from_dense_device(objects: torch.Tensor, sender_relations: torch.Tensor, receiver_relations: torch.Tensor,
+                          propagation: Optional[torch.Tensor] = None, nw_max: Optional[int] = None,
+                          check: bool = False) -> "DeviceTowerBatch":
+        """`from_dense` for inputs that are already on the device (Networks.py:22-29): the relation
+        matrices are scanned by one kernel (spwgnn_plan_device_dense, the semantics of
+        spwgnn_dense_to_edges) into a capacity plan of N(N−1) slots per tower; nothing is copied to the
+        host and nothing synchronises unless ``check=True`` (see `from_positions`). A non-None
+        ``propagation`` is used as it is (an all-zero one is not detected)."""
+        obj = _device_f32(objects, "objects")
+        Rs = _device_f32(sender_relations, "sender_relations")
+        Rr = _device_f32(receiver_relations, "receiver_relations")
+        if obj.dim() != 3 or obj.shape[2] < 3:
+            raise ValueError("objects must be (B, N, 3)")
+        B, N = int(obj.shape[0]), int(obj.shape[1])
+        E = N * (N - 1)
+        if tuple(Rs.shape) != (B, N, E) or tuple(Rr.shape) != (B, N, E):
+            raise ValueError(f"relation matrices must be (B, N, N(N-1)) = {(B, N, E)}; got {tuple(Rs.shape)}, "
+                             f"{tuple(Rr.shape)}")
+        geom = plan_geometry(_Uniform(B, N), nw_max, None, None, obj.device)
+        batch = DeviceTowerBatch(geom, ("dense",), (B, N))
+        batch.pos.zero_()
+        batch.pos[:, :3] = obj.reshape(B * N, -1)[:, :3]
+        if propagation is not None:
+            batch.prop = _device_f32(propagation, "propagation").reshape(geom.n_nodes, 100)
+        batch._fill((Rs, Rr))
+        if check:
+            batch.check()
+        return batch
+
+    def refill(self, source, check: bool = False) -> "TowerBatch":
+        """Device-built batches only (`from_positions`, `from_dense_device`): fill the same device
+        arrays again from new positions, or new (Rs, Rr) — in place, one launch, capturable."""
+        raise _lib.SpwgnnError("refill needs a batch built on the device (TowerBatch.from_positions / from_dense_device)")
+
     # ------------------------------------------------------------------ C view
     def cstruct(self) -> _lib.BatchC:
         if self._cstruct is None:
@@ -395,5 +469,213 @@ class TowerBatch:
     def with_prop(self, prop: Optional[torch.Tensor]) -> "TowerBatch":
         """Same graph, different propagation input (device tensor (Nn, 100) or None)."""
         nb = TowerBatch(**{k: getattr(self, k) for k in self.__dataclass_fields__ if k != "_cstruct"})
+        nb.prop = None if prop is None else prop.reshape(self.n_nodes, 100).to(self.device, torch.float32).contiguous()
+        return nb
+
+
+# ---------------------------------------------------------------------- plans built on the device
+class _Uniform(tuple):
+    """(B, N): B towers of N nodes each, without materialising the size array."""
+
+    def __new__(cls, B: int, N: int):
+        return super().__new__(cls, (int(B), int(N)))
+
+
+def _device_f32(t, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise _lib.SpwgnnError(f"{what} must be a HIP device tensor; the device plan has no host path "
+                               "(TowerBatch.from_dense / ragged take host data)")
+    return t.detach().to(torch.float32).contiguous()
+
+
+@dataclass
+class PlanGeometry:
+    """What a capacity plan fixes from the tower sizes and capacities alone (spwgnn_plan_size_cap /
+    spwgnn_plan_fill_cap with zero edges): the host arrays, and — once `to` has uploaded them — the
+    device tensors every device-built batch of this shape shares read-only."""
+    n_towers: int
+    n_nodes: int
+    n_wtiles: int
+    n_eblocks: int
+    nw_max: int
+    tower_nodes: np.ndarray     # (T,) int32
+    tower_cap: np.ndarray       # (T,) int32 relations each tower's blocks are sized for
+    default_cap: bool           # tower_cap is N(N−1) everywhere: no tower can exceed it
+    wtile: np.ndarray           # (n_wtiles, 4) int32
+    node_tower: np.ndarray      # (n_nodes,) int32
+    node_local: np.ndarray      # (n_nodes,) int32
+    wtile_tower: np.ndarray     # (n_wtiles,) int32 index of each wave-tile's first tower
+    device: Optional[torch.device] = None
+    dev: Optional[dict] = field(default=None, repr=False)   # name → device tensor
+
+    def to(self, device) -> "PlanGeometry":
+        if self.dev is None or self.device != torch.device(device):
+            names = ["wtile", "node_tower", "node_local", "wtile_tower", "tower_cap"]
+            self.dev = dict(zip(names, upload([getattr(self, n) for n in names], device)))
+            self.device = torch.device(device)
+        return self
+
+
+def plan_geometry_host(tower_nodes, nw_max: Optional[int] = None, edge_cap=None, tower_ids=None) -> PlanGeometry:
+    """The static arrays of a capacity plan, from the host planner given zero edges. ``tower_nodes``
+    (T,) sizes; ``edge_cap`` scalar or (T,), default N(N−1) per tower. No device is touched."""
+    tn = np.full(tower_nodes[0], tower_nodes[1], np.int32) if isinstance(tower_nodes, _Uniform) else \
+        np.ascontiguousarray(tower_nodes, dtype=np.int32)
+    T = len(tn)
+    full = (tn.astype(np.int64) * (tn.astype(np.int64) - 1)).astype(np.int32)
+    if edge_cap is None:
+        cap = full
+    else:
+        cap = np.array(np.broadcast_to(np.asarray(edge_cap, np.int32), (T,)), dtype=np.int32)   # an own, writable copy
+        if np.any(cap < 0):
+            raise ValueError("edge_cap must be >= 0")
+    empty = np.zeros(0, np.int32)
+    plan = HostPlan.build(np.zeros((int(tn.sum()), 3), np.float32), tn, empty, empty, np.zeros(T, np.int32),
+                          nw_max=nw_max, tower_ids=tower_ids, edge_cap=cap)
+    wtile, node_tower, node_local = plan.arrays[3], plan.arrays[1], plan.arrays[2]
+    starts = np.concatenate([[0], np.cumsum(tn)[:-1]]).astype(np.int64)
+    wtile_tower = np.searchsorted(starts, wtile[:, 2].astype(np.int64)).astype(np.int32)
+    return PlanGeometry(T, plan.n_nodes, plan.n_wtiles, plan.n_eblocks, plan.nw_max, tn, cap,
+                        bool(np.all(cap >= full)), wtile, node_tower, node_local, wtile_tower)
+
+
+_GEOMETRY_CACHE: dict = {}
+_GEOMETRY_CACHE_MAX = 16
+
+
+def plan_geometry(tower_nodes, nw_max: Optional[int] = None, edge_cap=None, tower_ids=None,
+                  device="cuda") -> PlanGeometry:
+    """`plan_geometry_host` uploaded to ``device``, cached per (tower sizes, nw_max, edge_cap,
+    tower_ids, device): same-shape batches share the host planning, the upload and the arrays."""
+    if isinstance(tower_nodes, _Uniform):
+        tkey = ("uniform",) + tuple(tower_nodes)
+    else:
+        tower_nodes = np.ascontiguousarray(tower_nodes, dtype=np.int32)
+        tkey = tower_nodes.tobytes()
+    blob = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int64).tobytes()
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    key = (tkey, None if nw_max is None else int(nw_max), blob(edge_cap), blob(tower_ids), str(dev))
+    g = _GEOMETRY_CACHE.get(key)
+    if g is None:
+        g = plan_geometry_host(tower_nodes, nw_max, edge_cap, tower_ids).to(dev)
+        while len(_GEOMETRY_CACHE) >= _GEOMETRY_CACHE_MAX:
+            _GEOMETRY_CACHE.pop(next(iter(_GEOMETRY_CACHE)))
+        _GEOMETRY_CACHE[key] = g
+    return g
+
+
+class DeviceTowerBatch(TowerBatch):
+    """A TowerBatch whose edge arrays were filled on the device (TowerBatch.from_positions /
+    from_dense_device). The geometry tensors are shared with every batch of the same shape; pos,
+    edge_src, edge_dst, blk_csr, tower_edges_dev and the 4-byte ``status`` are this batch's own.
+
+    There is no host edge list: ``src``, ``dst``, ``tower_edges``, ``edge_id`` and ``n_edges`` are
+    fetched from the device on first access — a synchronising copy, which also raises `SpwgnnError`
+    if the status word reports an error (see ``check``). The engine reads none of them."""
+
+    def __init__(self, geom: PlanGeometry, source: tuple, node_shape):
+        d, dev = geom.dev, geom.device
+        self.geom, self.source = geom, source
+        self.n_towers, self.n_nodes = geom.n_towers, geom.n_nodes
+        self.tower_nodes = geom.tower_nodes
+        self.n_wtiles, self.n_eblocks, self.nw_max = geom.n_wtiles, geom.n_eblocks, geom.nw_max
+        self.device = dev
+        self.pos = torch.empty(geom.n_nodes, 4, dtype=torch.float32, device=dev)
+        self.prop = None
+        self.node_tower, self.node_local, self.wtile = d["node_tower"], d["node_local"], d["wtile"]
+        self.edge_src = torch.empty(geom.n_eblocks * 32, dtype=torch.int32, device=dev)
+        self.edge_dst = torch.empty(geom.n_eblocks * 32, dtype=torch.int32, device=dev)
+        self.blk_csr = torch.empty(geom.n_eblocks, 128, dtype=torch.uint8, device=dev)
+        self.tower_edges_dev = torch.empty(geom.n_towers, dtype=torch.int32, device=dev)
+        self.status = torch.empty(1, dtype=torch.int32, device=dev)
+        self.node_shape = node_shape
+        self.flags = 0
+        self.node_perm = None
+        self._cstruct = None
+        self.generation = 0
+        self._host = None   # (generation, src, dst, tower_edges, edge_id) once fetched
+
+    def __repr__(self):
+        return (f"DeviceTowerBatch(n_towers={self.n_towers}, n_nodes={self.n_nodes}, n_wtiles={self.n_wtiles}, "
+                f"n_eblocks={self.n_eblocks}, nw_max={self.nw_max}, source={self.source[0]!r}, "
+                f"generation={self.generation})")
+
+    # ---- the one launch
+    def _fill(self, source) -> None:
+        g, d = self.geom, self.geom.dev
+        p = _lib.PlanDeviceC()
+        p.n_towers, p.n_nodes, p.n_wtiles, p.n_eblocks, p.nw_max = g.n_towers, g.n_nodes, g.n_wtiles, g.n_eblocks, g.nw_max
+        p.wtile, p.node_local, p.wtile_tower = d["wtile"].data_ptr(), d["node_local"].data_ptr(), d["wtile_tower"].data_ptr()
+        p.tower_cap = None if g.default_cap else d["tower_cap"].data_ptr()
+        p.edge_src, p.edge_dst, p.blk_csr = self.edge_src.data_ptr(), self.edge_dst.data_ptr(), self.blk_csr.data_ptr()
+        p.tower_edges, p.status = self.tower_edges_dev.data_ptr(), self.status.data_ptr()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.status.zero_()
+        L = _lib.lib()
+        if self.source[0] == "positions":
+            rows = _device_f32(source, "raw")
+            rows = rows.reshape(-1, rows.shape[-1])
+            if rows.shape[0] != g.n_nodes or rows.shape[1] < 3:
+                raise ValueError(f"raw must hold {g.n_nodes} rows of at least (x, y, w)")
+            p.pos = self.pos.data_ptr()
+            st = L.spwgnn_plan_device_positions(C.byref(p), rows.data_ptr(), int(rows.shape[1]), self.source[1],
+                                                self.source[2], stream)
+        else:
+            Rs, Rr = (_device_f32(x, "relations") for x in source)
+            B, N = self.node_shape
+            if tuple(Rs.shape) != (B, N, N * (N - 1)) or tuple(Rr.shape) != tuple(Rs.shape):
+                raise ValueError(f"relation matrices must be {(B, N, N * (N - 1))}")
+            st = L.spwgnn_plan_device_dense(C.byref(p), Rs.data_ptr(), Rr.data_ptr(), B, N, stream)
+        _lib.check(st, "spwgnn_plan_device_" + self.source[0])
+
+    def refill(self, source, check: bool = False) -> "DeviceTowerBatch":
+        """New positions (a `from_positions` batch: the ``raw`` tensor, same shape) or new relations (a
+        `from_dense_device` batch: ``(Rs, Rr)``) into the SAME device arrays: one launch on the current
+        stream, no synchronisation, capturable in a hipGraph (torch.cuda.graph) together with the
+        forward. The generation counter moves on, so a forward stored on a `Workspace` before the
+        refill no longer passes for this batch (`engine.Workspace.holds`): its backward is refused."""
+        self.mark_refilled()
+        self._fill(source)
+        if check:
+            self.check()
+        return self
+
+    def mark_refilled(self) -> None:
+        """The device arrays hold a new relation set: `refill` calls this; call it yourself after
+        replaying a captured graph that contains a refill (the replay does not pass through Python).
+        Drops the fetched host fields and moves the generation on."""
+        self.generation += 1
+        self._host = None
+
+    def check(self) -> "DeviceTowerBatch":
+        """Read the 4-byte status word (a synchronising copy) and raise `SpwgnnError` if the fill
+        reported an error: a malformed relation column, or a tower above its edge capacity."""
+        st = int(self.status.item())
+        if st:
+            _lib.check(-st, "device plan (batch.status)")
+        return self
+
+    def _fetch(self):
+        if self._host is None or self._host[0] != self.generation:
+            self.check()
+            es, ed = self.edge_src.cpu().numpy(), self.edge_dst.cpu().numpy()
+            m = es >= 0
+            eid = np.full(len(es), -1, np.int32)
+            eid[m] = np.arange(int(m.sum()), dtype=np.int32)
+            self._host = (self.generation, es[m], ed[m], self.tower_edges_dev.cpu().numpy(), eid)
+        return self._host
+
+    src = property(lambda self: self._fetch()[1], doc="(Ne,) global senders, fetched from the device (synchronises; see check)")
+    dst = property(lambda self: self._fetch()[2], doc="(Ne,) global receivers, fetched from the device (synchronises)")
+    tower_edges = property(lambda self: self._fetch()[3], doc="(T,) active relations per tower, fetched from the device")
+    edge_id = property(lambda self: self._fetch()[4], doc="(n_eblocks*32,) edge index per slot or -1, fetched from the device")
+
+    def with_prop(self, prop: Optional[torch.Tensor]) -> "DeviceTowerBatch":
+        """Same graph and device arrays, different propagation input (no host field is touched)."""
+        import copy
+        nb = copy.copy(self)
+        nb._cstruct = None
         nb.prop = None if prop is None else prop.reshape(self.n_nodes, 100).to(self.device, torch.float32).contiguous()
         return nb

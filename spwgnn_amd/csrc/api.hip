@@ -1424,6 +1424,78 @@ int32_t spwgnn_backward_inputs(const float* params, const spwgnn_batch* batch, c
     return SPWGNN_OK;
 }
 
+// Argument checks of the device-plan calls (no device work): 0, or the status to return.
+static int32_t plan_device_check(const spwgnn_plan_device* p) {
+    if (!p) return SPWGNN_E_ARG;
+    if (p->n_towers < 1 || p->n_nodes < 1 || p->n_wtiles < 1 || p->n_eblocks < 1) return SPWGNN_E_ARG;
+    if (p->nw_max < 1 || p->nw_max > kNwMaxLimit) return SPWGNN_E_SHAPE;
+    // whole towers of >= 1 node in tiles of >= 1 tower and >= 1 block; 32·n_eblocks must stay an int32
+    if (p->n_towers > p->n_nodes || p->n_wtiles > p->n_towers || p->n_eblocks < p->n_wtiles ||
+        p->n_eblocks > (INT32_MAX >> 5) || (int64_t)p->n_wtiles * p->nw_max < p->n_nodes)
+        return SPWGNN_E_SHAPE;
+    if (!p->wtile || !p->node_local || !p->wtile_tower || !p->edge_src || !p->edge_dst || !p->blk_csr || !p->status)
+        return SPWGNN_E_ARG;
+    const auto mis = [](const void* q, uintptr_t al) { return reinterpret_cast<uintptr_t>(q) % al != 0; };
+    if (mis(p->wtile, 4) || mis(p->node_local, 4) || mis(p->wtile_tower, 4) || mis(p->tower_cap, 4) ||
+        mis(p->edge_src, 4) || mis(p->edge_dst, 4) || mis(p->blk_csr, 16) || mis(p->pos, 16) ||
+        mis(p->tower_edges, 4) || mis(p->status, 4))
+        return SPWGNN_E_ARG;
+    return SPWGNN_OK;
+}
+
+static int32_t plan_device_launch(const spwgnn_plan_device* p, PlanDevArgs& a, bool dense, hipStream_t st) {
+    a.n_wtiles = p->n_wtiles;
+    a.n_eblocks = p->n_eblocks;
+    a.n_nodes = p->n_nodes;
+    a.n_towers = p->n_towers;
+    a.wtile = p->wtile;
+    a.node_local = p->node_local;
+    a.wtile_tower = p->wtile_tower;
+    a.tower_cap = p->tower_cap;
+    a.esrc = p->edge_src;
+    a.edst = p->edge_dst;
+    a.csr = p->blk_csr;
+    a.tower_edges = p->tower_edges;
+    a.status = p->status;
+    if (p->prof_events) SPW_CHECK(hipEventRecord(static_cast<hipEvent_t>(p->prof_events[0]), st));
+    SPW_CHECK(launch_plan_device(a, dense, st));
+    if (p->prof_events) SPW_CHECK(hipEventRecord(static_cast<hipEvent_t>(p->prof_events[1]), st));
+    return SPWGNN_OK;
+}
+
+int32_t spwgnn_plan_device_positions(const spwgnn_plan_device* plan, const float* raw, int32_t raw_stride,
+                                     float threshold, float divisor, spwgnn_stream_t stream) {
+    const int32_t stt = plan_device_check(plan);
+    if (stt) return stt;
+    if (!raw || reinterpret_cast<uintptr_t>(raw) % 4 || raw_stride < 2) return SPWGNN_E_ARG;
+    if (plan->pos && raw_stride < 3) return SPWGNN_E_ARG;
+    if (!(divisor > 0.f || divisor < 0.f)) return SPWGNN_E_ARG;   // zero or NaN
+    PlanDevArgs a{};
+    a.raw = raw;
+    a.raw_stride = raw_stride;
+    a.thr = threshold;
+    a.divisor = divisor;
+    a.pos = reinterpret_cast<float4*>(plan->pos);
+    return plan_device_launch(plan, a, false, static_cast<hipStream_t>(stream));
+}
+
+int32_t spwgnn_plan_device_dense(const spwgnn_plan_device* plan, const float* Rs, const float* Rr, int32_t B,
+                                 int32_t N, spwgnn_stream_t stream) {
+    const int32_t stt = plan_device_check(plan);
+    if (stt) return stt;
+    if (B < 1 || N < 1 || plan->pos) return SPWGNN_E_ARG;
+    // single-box towers have no relation slot (E = 0): their empty matrices may be null
+    if (((!Rs || !Rr) && N > 1) || reinterpret_cast<uintptr_t>(Rs) % 4 || reinterpret_cast<uintptr_t>(Rr) % 4)
+        return SPWGNN_E_ARG;
+    if (N > plan->nw_max || B != plan->n_towers || (int64_t)B * N != plan->n_nodes) return SPWGNN_E_SHAPE;
+    PlanDevArgs a{};
+    a.Rs = Rs;
+    a.Rr = Rr;
+    a.N = N;
+    a.E = N * (N - 1);
+    return plan_device_launch(plan, a, true, static_cast<hipStream_t>(stream));
+}
+
 int32_t spwgnn_bce_backward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
                             int64_t workspace_bytes, const float* logits, const float* targets, int64_t n,
                             float* out3, float* dlogits, void* bce_scratch, const double* weights3, double* total3,

@@ -63,6 +63,7 @@ int32_t spwgnn_struct_size(int32_t which) {
         case 2: return (int32_t)sizeof(spwgnn_plan_sizes);
         case 3: return (int32_t)sizeof(spwgnn_param_info);
         case 4: return (int32_t)sizeof(spwgnn_loss_weights);
+        case 6: return (int32_t)sizeof(spwgnn_plan_device);   // 5 stays -1
         default: return -1;
     }
 }
@@ -74,7 +75,7 @@ const char* spwgnn_strerror(int32_t st) {
         case SPWGNN_E_SHAPE: return "spwgnn: shape not supported by the kernels";
         case SPWGNN_E_RELATION: return "spwgnn: relation column is not one-hot (or receiver without sender)";
         case SPWGNN_E_WORKSPACE: return "spwgnn: workspace too small";
-        case SPWGNN_E_CAPACITY: return "spwgnn: output capacity too small";
+        case SPWGNN_E_CAPACITY: return "spwgnn: output capacity too small (device plan: a tower exceeds its edge capacity)";
         case SPWGNN_E_NOTRAIN: return "spwgnn: backward needs a forward run with training=1";
         default: return st > 0 ? "spwgnn: HIP runtime error (status = hipError_t)" : "spwgnn: unknown error";
     }

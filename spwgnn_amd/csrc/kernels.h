@@ -488,6 +488,27 @@ struct InputBwdArgs {
     int b16;
 };
 hipError_t launch_input_bwd(const InputBwdArgs& a, hipStream_t st);
+// k_plan_device (kernels_plan.hip): the data-dependent arrays of a capacity plan, filled on the device
+struct PlanDevArgs {
+    int n_wtiles, n_eblocks, n_nodes, n_towers;
+    const int32_t* wtile;            // [n_wtiles][4] first block, #blocks, first node, #nodes (static)
+    const int32_t* node_local;       // [n_nodes] node index inside its tower (static; 0 starts a tower)
+    const int32_t* wtile_tower;      // [n_wtiles] index of each wave-tile's first tower (static)
+    const int32_t* tower_cap;        // [n_towers] edge capacity per tower, or NULL = n(n−1)
+    int32_t *esrc, *edst;            // [n_eblocks*32] out
+    uint8_t* csr;                    // [n_eblocks][128] out
+    int32_t* tower_edges;            // [n_towers] out: active relations per tower, or NULL
+    int32_t* status;                 // device word: atomic max of the positive error code
+    // positions source
+    const float* raw;                // [n_nodes][raw_stride] pixels
+    int raw_stride;
+    float thr, divisor;
+    float4* pos;                     // [n_nodes] out: raw.xyz / divisor, 0
+    // dense source (uniform N): Rs, Rr [B][N][E]
+    const float *Rs, *Rr;
+    int N, E;
+};
+hipError_t launch_plan_device(const PlanDevArgs& a, bool dense, hipStream_t st);
 
 // Team kernels (kernels_team.hip): one block per workgroup of waves that split each layer's output
 // tiles — the latency-bound small batches (the reference's batch 32) up to kTeamMaxBlocks blocks

@@ -143,7 +143,9 @@ class Workspace:
         # two same-shape batches (equal micro-batches under one seed) must not pass for each other
         return (run.math, int(run.mp_steps), bool(run.training), float(run.dropout), int(run.seed),
                 run.seed_dev.data_ptr() if run.seed_dev is not None else 0, batch.n_nodes, batch.n_eblocks, batch.n_wtiles, batch.pos.data_ptr(), batch.edge_src.data_ptr(),
-                batch.prop.data_ptr() if batch.prop is not None else 0)
+                batch.prop.data_ptr() if batch.prop is not None else 0,
+                # device-built batches are refilled in place (TowerBatch.refill): same arrays, new contents
+                int(getattr(batch, "generation", 0)))
 
     def holds(self, batch: TowerBatch, run: "RunConfig") -> bool:
         """True when the last forward on this workspace ran `batch` (the same object) with `run`."""

@@ -115,28 +115,66 @@ class GraphNetwork(nn.Module):
                 return E.forward(self.flat.detach(), batch, run, ws)
         return _PropagationFn.apply(self.flat, dummy, odummy, batch, run, ws)
 
-    def forward_logits(self, objects, sender_relations, receiver_relations, propagation=None) -> torch.Tensor:
+    def _dense_batch(self, objects, sender_relations, receiver_relations, propagation, plan: str) -> TowerBatch:
+        if plan == "host":
+            return TowerBatch.from_dense(objects, sender_relations, receiver_relations, propagation, device=self.device)
+        if plan != "device":
+            raise ValueError('plan must be "host" or "device"')
+        return TowerBatch.from_dense_device(objects, sender_relations, receiver_relations, propagation)
+
+    def forward_logits(self, objects, sender_relations, receiver_relations, propagation=None,
+                       plan: str = "host") -> torch.Tensor:
         """(B, N) logits. A torch ``objects`` that requires grad receives d/d objects (B, N, 3) on
-        backward (see `forward_batch`; the relations are constants)."""
-        batch = TowerBatch.from_dense(objects, sender_relations, receiver_relations, None, device=self.device)
+        backward (see `forward_batch`; the relations are constants).
+        ``plan``: "host" converts the relation matrices on the host (`TowerBatch.from_dense`: a copy to
+        the host, a C++ scan, an upload); "device" needs all inputs on the device and converts them there
+        (`TowerBatch.from_dense_device`: one kernel, no host round trip, no synchronisation). The two
+        plans order a tile's edges alike but pad differently, so the logits agree within the engine's
+        position-independence bound (DESIGN.md §3 "Determinism"), not bit for bit in every math."""
+        batch = self._dense_batch(objects, sender_relations, receiver_relations, None, plan)
         prop = None
         if propagation is not None:
             prop = torch.as_tensor(propagation, dtype=torch.float32, device=self.device).reshape(batch.n_nodes, 100)
         z = self.forward_batch(batch, prop, objects if isinstance(objects, torch.Tensor) else None)
         return z.reshape(batch.node_shape)
 
-    def forward(self, objects, sender_relations, receiver_relations, propagation=None) -> torch.Tensor:
+    def forward(self, objects, sender_relations, receiver_relations, propagation=None, plan: str = "host") -> torch.Tensor:
         """(B, N, 1) probabilities: sigmoid(x[:, :, :1]) of the last step (Networks.py:93-96);
-        differentiable in a torch ``objects`` like `forward_logits`."""
-        return torch.sigmoid(self.forward_logits(objects, sender_relations, receiver_relations, propagation))[..., None]
+        differentiable in a torch ``objects`` like `forward_logits` (``plan`` as there)."""
+        return torch.sigmoid(self.forward_logits(objects, sender_relations, receiver_relations, propagation,
+                                                 plan))[..., None]
 
     def forward_pooled(self, objects, sender_relations, receiver_relations, propagation=None,
-                       mode: str = "mean_prob") -> torch.Tensor:
+                       mode: str = "mean_prob", plan: str = "host") -> torch.Tensor:
         """(B,) per-tower pooled output — the optional GlobalBlock-style readout (not in the
         reference): "mean_prob" / "sum_prob" (Σŷ of JengaBuilder.py:252-256) /
         "mean_logit" / "sum_logit", reduced on device. Inference only (no autograd, a torch
-        ``objects`` included; `demolish.stability_gradients` gives d(readout)/d objects)."""
-        batch = TowerBatch.from_dense(objects, sender_relations, receiver_relations, propagation, device=self.device)
+        ``objects`` included; `demolish.stability_gradients` gives d(readout)/d objects).
+        ``plan`` as in `forward_logits`."""
+        batch = self._dense_batch(objects, sender_relations, receiver_relations, propagation, plan)
         with torch.no_grad():
             z = E.forward(self.flat.detach(), batch, self.run_config(), E.Workspace(self.device))
             return E.tower_readout(z, batch, mode)
+
+    def forward_positions(self, raw: torch.Tensor, threshold: Optional[float] = 170.0, divisor: float = 170.0,
+                          tower_nodes=None, nw_max: Optional[int] = None, edge_cap=None, tower_ids=None,
+                          propagation: Optional[torch.Tensor] = None, check: bool = False) -> torch.Tensor:
+        """Logits from raw-pixel positions on the device, (B, N) for ``raw`` (B, N, 3) or (n_nodes,) for
+        ragged towers ((n_nodes, 3) with ``tower_nodes``): the relation set (raw-pixel distance <
+        ``threshold``, main.py:71-81) and the objects rows raw / ``divisor`` (main.py:91) are built on
+        the device by `TowerBatch.from_positions`, whose other arguments these are.
+        A ``raw`` that requires grad receives d/d raw = (d/d objects) / divisor on backward. The relation
+        set is a CONSTANT of the graph: it is not differentiated, although it was computed from ``raw`` —
+        the gradient is that of the network on the relation set the positions select, and it does not
+        see a relation appear or vanish as a box crosses the threshold."""
+        batch = TowerBatch.from_positions(raw, threshold, divisor, tower_nodes, nw_max, edge_cap, tower_ids, None, check)
+        prop = None
+        if propagation is not None:
+            prop = torch.as_tensor(propagation, dtype=torch.float32, device=self.device).reshape(batch.n_nodes, 100)
+        objects = None
+        if torch.is_grad_enabled() and raw.requires_grad:
+            # the forward reads the batch's own rows (the kernel's raw / divisor); this node only carries
+            # d/d objects back to raw through the division
+            objects = raw.reshape(batch.n_nodes, raw.shape[-1])[:, :3] / divisor
+        z = self.forward_batch(batch, prop, objects)
+        return z.reshape(batch.node_shape) if batch.node_shape is not None else z
