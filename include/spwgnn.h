@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
@@ -282,6 +282,7 @@ int32_t spwgnn_math_products(int32_t math);
 #define SPWGNN_K_ENC_NODE_BWD 11
 #define SPWGNN_K_INPUT_BWD 12  /* spwgnn_backward_inputs' one launch */
 #define SPWGNN_K_PLAN_DEVICE 13 /* spwgnn_plan_device_positions / _dense's one launch (spwgnn_plan_device.prof_events) */
+#define SPWGNN_K_STATE 14      /* the layout launch of spwgnn_forward_state (P_S out) / spwgnn_backward_state (dstate in) */
 
 /* Workspace bytes for (n_nodes, n_eblocks, mp_steps, training). */
 int64_t spwgnn_workspace_bytes(int32_t n_nodes, int32_t n_eblocks, int32_t mp_steps, int32_t training);
@@ -289,6 +290,9 @@ int64_t spwgnn_workspace_bytes(int32_t n_nodes, int32_t n_eblocks, int32_t mp_st
 /* Which launches a forward / backward of this batch and run takes (no device work): bit 0 = the
  * forward's fused small-batch step loop, bit 1 = the backward's; < 0 = an error
  * status. Profilers attribute kernel time and FLOPs by it instead of restating the library's gate. */
+/* State-carrying calls (spwgnn_forward_state with a buffer, spwgnn_backward_state with a cotangent) take
+ * the same path as the plain calls of the batch: the fused loops run the seeded first step themselves
+ * (their resource use is unchanged), so this answer holds for them too. */
 int32_t spwgnn_fused_path(const spwgnn_batch* batch, const spwgnn_run* run);
 
 /* Batches of at most this many 32-row blocks (edge blocks, node blocks, wave-tiles; counted per
@@ -323,6 +327,36 @@ int32_t spwgnn_forward(const float* params, const spwgnn_batch* batch, const spw
 int32_t spwgnn_backward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
                         void* workspace, int64_t workspace_bytes, const float* dlogits,
                         float* grads, float* dprop, spwgnn_stream_t stream);
+
+/* The final propagation state and its gradient (added within ABI 8: new symbols only, no existing
+ * struct or signature changed). P_S = tanh(x[:, 1:] + P_{S-1}) of the last step (Networks.py:91) is the
+ * value a caller feeds to the next call as batch->prop: a belief state carried across the frames of a
+ * trajectory, a long propagation run in chunks, a loss on the state.
+ *
+ * spwgnn_forward_state: spwgnn_forward, and with state_out != NULL also P_S → state_out, [n_nodes][100]
+ * device fp32 (16-byte aligned), rows in the plan's node order, every row written, nothing past them.
+ * state_out == NULL is spwgnn_forward bit for bit; with a buffer the logits are the same bits as
+ * without it. Training and inference, every math, every plan kind. One more launch (kernel id
+ * SPWGNN_K_STATE); the large-batch split-bf16 node forward runs its last step without the "only the
+ * logit is read" shortcut so that P_S exists. */
+int32_t spwgnn_forward_state(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                             void* workspace, int64_t workspace_bytes, float* logits,
+                             float* state_out /* [n_nodes][100] device fp32, plan node order; NULL = none */,
+                             spwgnn_stream_t stream);
+/* spwgnn_backward_state: spwgnn_backward, and with dstate != NULL the backward of
+ *   Σ dlogits·z + Σ dstate·P_S
+ * in ONE pass over the step loop: dstate ([n_nodes][100] device fp32, 16-byte aligned, plan node order)
+ * enters as the incoming dP of step S-1. dstate == NULL is spwgnn_backward bit for bit. dlogits stays
+ * required: a caller with no loss on the logits passes zeros. grads_early_event, spwgnn_backward_inputs
+ * after it and the stored dh1pre steps work as after spwgnn_backward. One more launch (SPWGNN_K_STATE).
+ * CONTRACT for dstate != NULL: the forward on this workspace was spwgnn_forward_state with a non-NULL
+ * state_out and training == 1. After a plain spwgnn_forward the large-batch path has not written its
+ * P_S rows and the result is undefined (the reads stay inside the workspace either way). The library
+ * does not synchronise and cannot check this; the Python layer does (engine.Workspace). */
+int32_t spwgnn_backward_state(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                              void* workspace, int64_t workspace_bytes, const float* dlogits,
+                              const float* dstate /* [n_nodes][100] device fp32, plan node order; NULL = none */,
+                              float* grads, float* dprop, spwgnn_stream_t stream);
 
 /* ABI 8. d(loss)/d(batch->pos) of the last spwgnn_backward / spwgnn_bce_backward on this workspace
  * (same batch, same run; before the next forward on it): dpos [n_nodes][4] device fp32 (16-byte

@@ -402,8 +402,9 @@ static bool wide_node_side(const spwgnn_run* r, const spwgnn_batch* b) {
            (kmath(r, kX6NodeBwd) != MATH_F32 && kmath(r, kX6Wgrad) != MATH_F32 && !getenv_flag("SPWGNN_WG_OLD"));
 }
 
+// keep_state (spwgnn_forward_state with a buffer): the last step leaves P_S in P_at(S) on every path
 static int32_t run_forward(const float* params, const spwgnn_batch* b, const spwgnn_run* r, const Ws& w,
-                           char* base, float* logits, hipStream_t st) {
+                           char* base, float* logits, hipStream_t st, bool keep_state = false) {
     Ctx c{w, base};
     const bool zero_prop = b->prop == nullptr;   // 'propagation' = 0 (spwgnn.h): P0 = U0 = V0 = 0
     PrepArgs pa{};
@@ -587,7 +588,8 @@ static int32_t run_forward(const float* params, const spwgnn_batch* b, const spw
         nf.n16 = store_b16_node(r, b);
         nf.uv16 = uv16;
         nf.p_zero = s == 0 && zero_prop;
-        nf.last = s == S - 1 && wide_node_side(r, b);   // P_S unwritten: its one reader must know (§3zh)
+        // P_S unwritten: its one reader must know (§3zh); a state request takes the general path (§3zo)
+        nf.last = s == S - 1 && wide_node_side(r, b) && !keep_state;
         return nf;
     };
     if (fwd_fused_taken(r, b)) {
@@ -854,8 +856,11 @@ static void ws_group(WsBatch* wsb, int first, int n) {
     }
 }
 
+// dstate (spwgnn_backward_state): the cotangent of P_S, row-major; it enters the step loop as step
+// S−1's incoming dP (NodeBwdArgs::seeded), so the loop runs once for Σ dlogits·z + Σ dstate·P_S
 int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, char* base,
-                     const float* dlogits, float* grads, float* dprop, hipStream_t st, const BceArgs* bce = nullptr) {
+                     const float* dlogits, float* grads, float* dprop, hipStream_t st, const BceArgs* bce = nullptr,
+                     const float* dstate = nullptr) {
     (void)params;  // the packed copies made by the forward on this workspace are used
     Ctx c{w, base};
     const int S = r->mp_steps;
@@ -885,8 +890,9 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
         NodeBwdArgs nb{};
         nb.n_nodes = b->n_nodes;
         nb.first = first;
+        nb.seeded = first && dstate != nullptr;
         nb.tail = 0;
-        nb.dPin = first ? nullptr : c.f(w.dP_at(s + 1));
+        nb.dPin = first && !dstate ? nullptr : c.f(w.dP_at(s + 1));
         nb.dU = first ? nullptr : c.f(w.dU_at(s + 1));
         nb.dV = first ? nullptr : c.f(w.dV_at(s + 1));
         nb.Pn = c.f(w.P_at(s + 1));
@@ -1044,6 +1050,11 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
     // scratch and scalar spills, so its loss launch runs first on every path
     const bool bce_inline = bce && fused && bce->blocks == 1 && !bce->w;
     if (bce && !bce_inline) SPW_CHECK(launch_bce(*bce, st));
+    if (dstate) {   // dP_S ← dstate, chunk-major (the slot step S−2's node backward overwrites)
+        SPW_CHECK(prof.before(SPWGNN_K_STATE));
+        SPW_CHECK(launch_state_import(dstate, c.f(w.dP_at(S)), b->n_nodes, st));
+        SPW_CHECK(prof.after(SPWGNN_K_STATE));
+    }
     auto edge_encoder_bwd = [&]() -> int32_t {   // dA rebuild + relation encoder backward (wide kernels)
         if (rebuild) {
             SPW_CHECK(prof.before(SPWGNN_K_DA));
@@ -1059,6 +1070,7 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
         // small batch: the step loop, dA and both encoder backwards in one launch (timed as the node backward)
         BwdFusedArgs fa{};
         fa.nb = node_args(0);
+        fa.nb.seeded = dstate != nullptr;   // step S−1's (the loop sets each step's own)
         fa.nb.dU = c.f(w.dU_at(1));   // step 0's incoming dU/dV (BwdFusedArgs)
         fa.nb.dV = c.f(w.dV_at(1));
         if (bce_inline) {
@@ -1391,6 +1403,37 @@ int32_t spwgnn_backward(const float* params, const spwgnn_batch* batch, const sp
     if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
     return run_backward(params, batch, run, w, static_cast<char*>(workspace), dlogits, grads, dprop,
                         static_cast<hipStream_t>(stream));
+}
+
+int32_t spwgnn_forward_state(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                             int64_t workspace_bytes, float* logits, float* state_out, spwgnn_stream_t stream) {
+    int32_t stt = validate(batch, run);
+    if (stt) return stt;
+    if (!params || !workspace || !logits || reinterpret_cast<uintptr_t>(state_out) % 16) return SPWGNN_E_ARG;
+    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, run->training ? 1 : 0);
+    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    stt = run_forward(params, batch, run, w, static_cast<char*>(workspace), logits, st, state_out != nullptr);
+    if (stt || !state_out) return stt;
+    const Ctx c{w, static_cast<char*>(workspace)};
+    const Prof prof{run, st};
+    SPW_CHECK(prof.before(SPWGNN_K_STATE));
+    SPW_CHECK(launch_state_export(c.f(w.P_at(run->mp_steps)), state_out, batch->n_nodes, st));
+    SPW_CHECK(prof.after(SPWGNN_K_STATE));
+    return SPWGNN_OK;
+}
+
+int32_t spwgnn_backward_state(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                              int64_t workspace_bytes, const float* dlogits, const float* dstate, float* grads,
+                              float* dprop, spwgnn_stream_t stream) {
+    int32_t stt = validate(batch, run);
+    if (stt) return stt;
+    if (!run->training) return SPWGNN_E_NOTRAIN;
+    if (!params || !workspace || !dlogits || !grads || reinterpret_cast<uintptr_t>(dstate) % 16) return SPWGNN_E_ARG;
+    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, 1);
+    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
+    return run_backward(params, batch, run, w, static_cast<char*>(workspace), dlogits, grads, dprop,
+                        static_cast<hipStream_t>(stream), nullptr, dstate);
 }
 
 int32_t spwgnn_backward_inputs(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,

@@ -188,9 +188,11 @@ struct NodeFwdArgs {
 
 struct NodeBwdArgs {
     int n_nodes;
-    int first;      // 1 for the last propagation step (no incoming dP, dlogits present)
+    int first;      // 1 for the last propagation step: dlogits go into x' row 100, no dU / dV (no step S)
+    int seeded;     // first only: 1 = an incoming dP (the state cotangent, spwgnn_backward_state) is read
+                    //   from dPin and P_S from Pn; 0 = the incoming dP is zero (dPin null, P_S unread)
     int tail;       // 1: only compute dP0 = dPpart + dU·W1bᵀ + dV·W1cᵀ into dprop (ld 100)
-    const float *dPin, *dU, *dV;   // from step s+1 (null when first)
+    const float *dPin, *dU, *dV;   // from step s+1 (dU, dV null when first; dPin null when first and not seeded)
     const float *Pn, *o1, *a;      // P_{s+1}, o1_s, a_s
     const float* dlogits;
     float *dx, *do1, *g, *G3, *dPout, *dco, *dprop;
@@ -476,6 +478,10 @@ hipError_t launch_sigmoid(const float* z, float* p, int64_t n, hipStream_t st);
 hipError_t launch_accumulate_out3(const float* out3, const double* w, double* tot, hipStream_t st);
 hipError_t launch_copy_in(const void* src, void* dst, int64_t n16, hipStream_t st);
 hipError_t launch_tower_readout(const float* z, const int32_t* off, int n_towers, int mode, float* out, hipStream_t st);
+// The propagation state at the library's edge (spwgnn_forward_state / spwgnn_backward_state): P_S in
+// chunk-major node blocks → row-major [n_nodes][100], and a row-major cotangent → the chunk-major dP_S slot
+hipError_t launch_state_export(const float* P_cm, float* state, int n_nodes, hipStream_t st);
+hipError_t launch_state_import(const float* dstate, float* dP_cm, int n_nodes, hipStream_t st);
 // k_input_bwd (kernels_input.hip): d/d(pos) from the first encoder layers' pre-activation gradients
 struct InputBwdArgs {
     int n_wtiles, n_eblocks, n_nodes;

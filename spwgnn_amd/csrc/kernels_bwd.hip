@@ -25,12 +25,14 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const int pj = (h * 32 + j) * 4;                                        // this lane's piece
 
     f32x16 D[4];
-    if (a.first) {
+    if (a.first && !a.seeded) {
         zero_tiles(D);
     } else {
         load_cm<4>(a.dPin + bN, D, lane);
-        tgemm_stream_acc<4, kKhE, kLdN, 64>(a.dU + bE + pj, D, a.w1bt, lane);
-        tgemm_stream_acc<4, kKhE, kLdN, 64>(a.dV + bE + pj, D, a.w1ct, lane);
+        if (!a.first) {   // (seeded: the state cotangent alone — there is no step S)
+            tgemm_stream_acc<4, kKhE, kLdN, 64>(a.dU + bE + pj, D, a.w1bt, lane);
+            tgemm_stream_acc<4, kKhE, kLdN, 64>(a.dV + bE + pj, D, a.w1ct, lane);
+        }
     }
     if (a.tail) {  // dP0 = d/d 'propagation' (ld 100)
         if (valid) {
@@ -144,11 +146,16 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_bwd_x6(NodeBwdArg
         for (int c = 0; c < NC; ++c) zero_tiles(Z[c]);
     };
     f32x16 D[NC][4], G[NC][4];
-    if (a.first) {
+    // first has two meanings that a state cotangent separates: "dlogits go into x' row
+    // 100, there is no step S" stays a.first; "the incoming dP is zero" is zero_in, false when seeded
+    const bool zero_in = a.first && !a.seeded;
+    if (zero_in) {
         zero2(D);
     } else {
 #pragma unroll
         for (int c = 0; c < NC; ++c) load_cm<4>(a.dPin + bN(c), D[c], lane);
+    }
+    if (!a.first) {
         int64_t off[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) off[c] = bE(c);
@@ -180,14 +187,15 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_bwd_x6(NodeBwdArg
         }
         return;
     }
-    // Loop-end shortcuts, all workgroup-uniform. first: the incoming dP is zero, so
-    // P_S is not read (the last forward step does not store it), dpre = 0 is not stored and read
-    // back, and dx' is the logit row alone — Wo2'ᵀ runs over that row's k-block only. no_dP (step 0,
-    // no dprop request): dP_0 has no reader — no store, no do1·Wo1pᵀ.
-    const bool dp_rmw = !a.first && !a.no_dP;   // dP_s = dpre + do1·Wo1pᵀ through memory (D's registers are reused)
+    // Loop-end shortcuts, all workgroup-uniform. zero_in (first, no state cotangent):
+    // the incoming dP is zero, so P_S is not read (the last forward step does not store it), dpre = 0
+    // is not stored and read back, and dx' is the logit row alone — Wo2'ᵀ runs over that row's k-block
+    // only. A seeded first step is a middle step in all of this. no_dP (step 0, no dprop request):
+    // dP_0 has no reader — no store, no do1·Wo1pᵀ.
+    const bool dp_rmw = !zero_in && !a.no_dP;   // dP_s = dpre + do1·Wo1pᵀ through memory (D's registers are reused)
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        if (!a.first) {
+        if (!zero_in) {
             f32x16 Pn[4];
             load_cm<4>(a.Pn + bN(c), Pn, lane);
 #pragma unroll
@@ -208,7 +216,7 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_bwd_x6(NodeBwdArg
         }
     }
     zero2(G);
-    if (a.first)   // row 100 = k-block 6 (k = 16·6 + 4h), the chain's last
+    if (zero_in)   // row 100 = k-block 6 (k = 16·6 + 4h), the chain's last
         tchain_x6s_kb<4, 6, 4, NC, kX6Ring, NP, NW, kHT>(D, G, kHT ? a.xh_wo2t : a.x_wo2t, lane, wr);
     else
         tchain_x6s<4, 7, 4, NC, kX6Ring, NP, NW, kHT>(D, G, kHT ? a.xh_wo2t : a.x_wo2t, lane, wr);
@@ -234,7 +242,7 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_bwd_x6(NodeBwdArg
                 load_cm<4>(a.dPout + bN(c), T, lane);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) D[c][t] += T[t];
-            } else {   // first: dpre = +0 (the sum a stored zero tile would give: −0 + 0 = +0)
+            } else {   // zero_in: dpre = +0 (the sum a stored zero tile would give: −0 + 0 = +0)
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
 #pragma unroll

@@ -2265,4 +2265,53 @@ hipError_t launch_sigmoid(const float* z, float* p, int64_t n, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ---- the propagation state at the library's edge ----
+// A 32-node block of a chunk-major 104-feature array is 26 slots of [node i < 32][4 floats]: slot
+// 2q + h holds features 52h + 4q .. +3 (cm_offk<kKhN>), so thread (block, slot, i) owns the 16-byte
+// piece at float 4·(its index) of the chunk-major array — that side is one contiguous stream — and
+// the 16-byte piece 13h + q of row-major row 32·block + i (400-byte rows: every piece is aligned).
+// Piece 25 is the chunk-major padding (features 100..103), not part of a row. Pure copies, one owner
+// per piece: the same bits on every run.
+constexpr int kStateSlots = 2 * (kKhN / 4);   // 26
+static_assert(kStateSlots * 32 * 4 == kCmBlkN && cm_offk<kKhN>(0, kKhN) == 128, "chunk-major node block");
+__device__ __forceinline__ bool state_piece(int64_t idx, int n_nodes, int64_t& n, int& piece) {
+    const int i = (int)(idx & 31), slot = (int)((idx >> 5) % kStateSlots);
+    n = (idx >> 5) / kStateSlots * 32 + i;
+    piece = (slot >> 1) + (slot & 1) * (kKhN / 4);
+    return n < n_nodes;
+}
+// P_S → state_out: rows < n_nodes only, 25 pieces each
+__global__ __launch_bounds__(256) void k_state_export(const float4* __restrict__ P_cm, float4* __restrict__ state,
+                                                      int n_nodes, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    int64_t n;
+    int piece;
+    if (state_piece(idx, n_nodes, n, piece) && piece < kFN / 4) state[n * (kFN / 4) + piece] = P_cm[idx];
+}
+// dstate → the dP_S slot: rows < n_nodes from the cotangent; the padding piece and the last block's
+// rows past n_nodes are zero, as store_cm leaves them in every other dP (the array is RN rows long)
+__global__ __launch_bounds__(256) void k_state_import(const float4* __restrict__ dstate, float4* __restrict__ dP_cm,
+                                                      int n_nodes, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    int64_t n;
+    int piece;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (state_piece(idx, n_nodes, n, piece) && piece < kFN / 4) v = dstate[n * (kFN / 4) + piece];
+    dP_cm[idx] = v;
+}
+hipError_t launch_state_export(const float* P_cm, float* state, int n_nodes, hipStream_t st) {
+    const int64_t total = (int64_t)((n_nodes + 31) / 32) * kStateSlots * 32;
+    hipLaunchKernelGGL(k_state_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const float4*>(P_cm), reinterpret_cast<float4*>(state), n_nodes, total);
+    return hipGetLastError();
+}
+hipError_t launch_state_import(const float* dstate, float* dP_cm, int n_nodes, hipStream_t st) {
+    const int64_t total = (int64_t)((n_nodes + 31) / 32) * kStateSlots * 32;
+    hipLaunchKernelGGL(k_state_import, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const float4*>(dstate), reinterpret_cast<float4*>(dP_cm), n_nodes, total);
+    return hipGetLastError();
+}
+
 }  // namespace spw

@@ -670,6 +670,8 @@ __device__ __forceinline__ void node_bwd_team_body(const NodeBwdArgs& a, const T
     f32x16 dP;
     if (nw) {
         const f32x16 Pn = R.load<kKhN>(a.Pn, T);
+        // a first step with a state cotangent (§3zo): there is no step S, so no dU / dV — dP_S alone
+        if (a.seeded) D = R.load<kKhN>(a.dPin, T);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int f = rho(r, 0) + 4 * h + 32 * T;
@@ -1321,7 +1323,8 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_bwd_fused_team(BwdFusedArgs 
         opaque(nb.x_wo1at);
         opaque(nb.x_w3t);
         nb.first = first;
-        nb.dPin = first ? nullptr : dP0 + ((s + 1) & 1) * a.rowsN;
+        nb.seeded = first && a.nb.seeded;   // the host's flag is step S−1's (§3zo)
+        nb.dPin = first && !a.nb.seeded ? nullptr : dP0 + ((s + 1) & 1) * a.rowsN;
         nb.dU = first ? nullptr : a.nb.dU + sE;   // the host passes dU_at(1) / dV_at(1)
         nb.dV = first ? nullptr : a.nb.dV + sE;
         nb.Pn += sN;

@@ -136,6 +136,7 @@ class Workspace:
         self.fwd_key: Optional[tuple] = None   # what the last forward on this workspace stored
         self.fwd_batch = None                  # weakref to the batch that forward ran on
         self.bwd_key: Optional[tuple] = None   # fwd_key once a backward of that forward has run (backward_inputs)
+        self.has_state = False                 # that forward returned the final state (backward's dstate needs it)
 
     @staticmethod
     def key(batch: TowerBatch, run: "RunConfig") -> tuple:
@@ -226,8 +227,34 @@ class da_stored:
         return False
 
 
+STATE_WIDTH = 100   # the propagation state's features (Networks.py:29)
+
+
+def _check_dstate(ws: Workspace, batch: TowerBatch, dstate: torch.Tensor) -> torch.Tensor:
+    """The state cotangent of `backward`: the library cannot check its contract (spwgnn_backward_state),
+    so it is enforced here."""
+    if not ws.has_state:
+        raise ValueError("backward(dstate=...) needs forward(..., return_state=True) on this workspace: a plain "
+                         "forward does not keep the final state on every path")
+    if not isinstance(dstate, torch.Tensor) or tuple(dstate.shape) != (batch.n_nodes, STATE_WIDTH):
+        raise ValueError(f"dstate must be a ({batch.n_nodes}, {STATE_WIDTH}) tensor in the plan's node order "
+                         f"(got {tuple(getattr(dstate, 'shape', ()))})")
+    if dstate.dtype != torch.float32:
+        raise ValueError(f"dstate must be float32 (got {dstate.dtype})")
+    _require_gpu(dstate, "dstate")
+    want = torch.device(batch.device)   # "cuda" names the current device: compare the index only when given
+    if want.index is not None and dstate.device.index != want.index:
+        raise ValueError(f"dstate must be on the batch's device {batch.device} (got {dstate.device})")
+    return dstate.contiguous()
+
+
 def forward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
-            logits: Optional[torch.Tensor] = None) -> torch.Tensor:
+            logits: Optional[torch.Tensor] = None, return_state: bool = False,
+            state: Optional[torch.Tensor] = None):
+    """Logits (n_nodes,). With ``return_state`` also the final propagation state P_S, (n_nodes, 100) fp32
+    in the plan's node order (spwgnn_forward_state) — what the next call takes as its ``prop`` — as
+    ``(logits, state)``; the logits are the same bits either way. ``state``: the buffer to write it to
+    (a captured forward's static output, like ``logits``)."""
     _require_gpu(flat_params, "params")
     if flat_params.dtype != torch.float32 or not flat_params.is_contiguous() or flat_params.numel() != P.flat_size():
         raise ValueError("params must be a contiguous fp32 flat buffer of spwgnn_param_count() floats")
@@ -237,19 +264,39 @@ def forward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Wo
         logits = _poison(torch.empty(batch.n_nodes, dtype=torch.float32, device=batch.device))
     b = batch.cstruct()
     r = run.cstruct(with_prologue=True)
-    st = _lib.lib().spwgnn_forward(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
-                                   logits.data_ptr(), _stream(batch.device))
+    if not return_state:
+        if state is not None:
+            raise ValueError("a state buffer goes with return_state=True")
+    elif state is None:
+        state = _poison(torch.empty(batch.n_nodes, STATE_WIDTH, dtype=torch.float32, device=batch.device))
+    else:
+        _require_gpu(state, "state")
+        if tuple(state.shape) != (batch.n_nodes, STATE_WIDTH) or state.dtype != torch.float32 or not state.is_contiguous():
+            raise ValueError(f"state must be a contiguous fp32 ({batch.n_nodes}, {STATE_WIDTH}) tensor")
+    if return_state:
+        st = _lib.lib().spwgnn_forward_state(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(),
+                                             buf.numel(), logits.data_ptr(), state.data_ptr(), _stream(batch.device))
+    else:
+        st = _lib.lib().spwgnn_forward(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
+                                       logits.data_ptr(), _stream(batch.device))
     ws.fwd_key = Workspace.key(batch, run) if st == 0 else None
     ws.fwd_batch = weakref.ref(batch) if st == 0 else None
     ws.bwd_key = None
-    _lib.check(st, "spwgnn_forward")
-    return logits
+    ws.has_state = bool(return_state) and st == 0
+    _lib.check(st, "spwgnn_forward_state" if return_state else "spwgnn_forward")
+    return (logits, state) if return_state else logits
 
 
 def backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace, dlogits: torch.Tensor,
-             grads: Optional[torch.Tensor] = None, want_dprop: bool = False):
+             grads: Optional[torch.Tensor] = None, want_dprop: bool = False, dstate: Optional[torch.Tensor] = None):
+    """Gradients of Σ dlogits·z — and, with ``dstate`` ((n_nodes, 100) fp32 on the batch's device, plan node
+    order), of Σ dlogits·z + Σ dstate·P_S in the same single pass (spwgnn_backward_state); the forward on
+    this workspace must then have been ``forward(..., return_state=True)``. A caller with a loss on the
+    state alone passes zero ``dlogits``. Returns (grads, dprop)."""
     if not run.training:
         raise _lib.SpwgnnError("backward needs a training forward on the same workspace")
+    if dstate is not None:
+        dstate = _check_dstate(ws, batch, dstate)
     if not ws.holds(batch, run):
         # the backward reads what the forward stored (masks, activations, packed weights); the split-
         # bf16 maths do not store z1/zo1 at all, so a mismatched math or step count reads garbage
@@ -263,11 +310,16 @@ def backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: W
     b = batch.cstruct()
     r = run.cstruct()
     buf = ws.buf
-    st = _lib.lib().spwgnn_backward(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
-                                    dlogits.data_ptr(), grads.data_ptr(), dprop.data_ptr() if dprop is not None else None,
-                                    _stream(batch.device))
+    dprop_ptr = dprop.data_ptr() if dprop is not None else None
+    if dstate is not None:
+        st = _lib.lib().spwgnn_backward_state(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(),
+                                              buf.numel(), dlogits.data_ptr(), dstate.data_ptr(), grads.data_ptr(),
+                                              dprop_ptr, _stream(batch.device))
+    else:
+        st = _lib.lib().spwgnn_backward(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
+                                        dlogits.data_ptr(), grads.data_ptr(), dprop_ptr, _stream(batch.device))
     ws.bwd_key = ws.fwd_key if st == 0 else None
-    _lib.check(st, "spwgnn_backward")
+    _lib.check(st, "spwgnn_backward_state" if dstate is not None else "spwgnn_backward")
     return grads, dprop
 
 

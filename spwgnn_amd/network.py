@@ -6,7 +6,7 @@ relations (B,N,E), propagation (B,N,100) → per-object stability probability (B
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -20,23 +20,34 @@ from .batch import TowerBatch
 class _PropagationFn(torch.autograd.Function):
     """Forward/backward of the whole graph through the C-ABI; gradients w.r.t. the flat parameter
     buffer, the propagation input and the objects (the (n_nodes, 3) rows in the plan's node order;
-    the relation set is a constant of the graph and is not differentiated)."""
+    the relation set is a constant of the graph and is not differentiated). With ``want_state`` a second
+    output, the final state (n_nodes, 100), whose gradient enters the same backward pass as ``dstate``."""
 
     @staticmethod
-    def forward(ctx, flat, prop_dummy, obj_dummy, batch: TowerBatch, run: E.RunConfig, ws: E.Workspace):
-        logits = E.forward(flat, batch, run, ws)
+    def forward(ctx, flat, prop_dummy, obj_dummy, batch: TowerBatch, run: E.RunConfig, ws: E.Workspace,
+                want_state: bool = False):
         ctx.batch, ctx.run, ctx.ws = batch, run, ws
         ctx.save_for_backward(flat)
         ctx.want_prop = prop_dummy.requires_grad
         ctx.want_obj = obj_dummy.requires_grad
-        return logits
+        ctx.want_state = want_state
+        ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None, not as zeros
+        if want_state:
+            return E.forward(flat, batch, run, ws, return_state=True)
+        return E.forward(flat, batch, run, ws)
 
     @staticmethod
-    def backward(ctx, dlogits):
+    def backward(ctx, dlogits, dstate=None):
         (flat,) = ctx.saved_tensors
-        grads, dprop = E.backward(flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop)
+        if dlogits is None:   # a loss on the state alone: the library still takes a dlogits array
+            dlogits = torch.zeros(ctx.batch.n_nodes, dtype=torch.float32, device=flat.device)
+        if dstate is None:    # no loss on the state: the plain backward
+            grads, dprop = E.backward(flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop)
+        else:
+            grads, dprop = E.backward(flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop,
+                                      dstate=dstate.to(torch.float32).contiguous())
         dobj = E.backward_inputs(flat, ctx.batch, ctx.run, ctx.ws) if ctx.want_obj else None
-        return grads, dprop, dobj, None, None, None
+        return grads, dprop, dobj, None, None, None, None
 
 
 class GraphNetwork(nn.Module):
@@ -75,7 +86,7 @@ class GraphNetwork(nn.Module):
         """A `RunConfig` of this network's step count and math (the front ends build theirs with it)."""
         return E.RunConfig(self.mp_steps, training=training, math=self.math, **kw)
 
-    def _run(self, input_grad: bool = False) -> E.RunConfig:
+    def _run(self, input_grad: bool = False) -> E.RunConfig:   # input_grad: an input (objects, prop) wants a gradient
         need_grad = torch.is_grad_enabled() and (self.flat.requires_grad or input_grad)
         drop = self.training and self.dropout > 0 and need_grad
         seed = 0
@@ -86,8 +97,13 @@ class GraphNetwork(nn.Module):
                            math=self.math)
 
     def forward_batch(self, batch: TowerBatch, prop: Optional[torch.Tensor] = None,
-                      objects: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      objects: Optional[torch.Tensor] = None, return_state: bool = False):
         """Logits (n_nodes,) for a compact batch (the reference returns sigmoid of these).
+
+        ``return_state``: return ``(logits, state)`` — state (n_nodes, 100) is the propagation state after
+        the last step, P_S = tanh(x[:, 1:] + P_{S-1}) (Networks.py:91), in the plan's node order like the
+        logits, differentiable like them. Feed it to the next call as ``prop`` to carry the state on
+        (`rollout`); a state that carries a gradient makes that next call differentiate with respect to it.
 
         ``objects``: the torch tensor the batch's node rows were built from (n_nodes·3 elements, the
         input's node order, any device / float dtype). The forward reads the batch's own copy; when
@@ -95,7 +111,9 @@ class GraphNetwork(nn.Module):
         `engine.backward_inputs`), in its own shape, device and dtype. The relation set — a
         thresholded one included — is held constant: it is not differentiated."""
         want_obj = objects is not None and torch.is_grad_enabled() and objects.requires_grad
-        run = self._run(want_obj)
+        # a carried state that has a gradient path needs this call's backward even under frozen weights
+        want_prop = return_state and prop is not None and torch.is_grad_enabled() and prop.requires_grad
+        run = self._run(want_obj or want_prop)
         ws = E.Workspace(self.device)
         if prop is not None:
             batch = batch.with_prop(prop)
@@ -112,8 +130,32 @@ class GraphNetwork(nn.Module):
             odummy = dummy.new_zeros(0)
         if not run.training:
             with torch.no_grad():
-                return E.forward(self.flat.detach(), batch, run, ws)
+                return E.forward(self.flat.detach(), batch, run, ws, return_state=return_state)
+        if return_state:
+            return _PropagationFn.apply(self.flat, dummy, odummy, batch, run, ws, True)
         return _PropagationFn.apply(self.flat, dummy, odummy, batch, run, ws)
+
+    def rollout(self, batches: Sequence[TowerBatch], prop: Optional[torch.Tensor] = None,
+                objects: Optional[Sequence[Optional[torch.Tensor]]] = None) -> Tuple[List[torch.Tensor], torch.Tensor]:
+        """The network over the frames of a trajectory, the belief state carried from frame to frame as
+        BRDPN's propagation input is (Blocks.py is "directly taken from" it): ``batches`` holds one
+        `TowerBatch` per frame, the same nodes in the same plan order in each (positions and relation sets
+        may differ); frame k's final state is frame k + 1's ``prop``, frame 0 takes ``prop`` (None = zero).
+        Returns (the per-frame logits, the final state). Autograd flows through all frames — weights, the
+        initial ``prop`` and, with ``objects`` (one tensor or None per frame, as in `forward_batch`), the
+        positions; each frame keeps its own workspace until its backward has run."""
+        batches = list(batches)
+        if not batches:
+            raise ValueError("rollout needs at least one frame")
+        if any(b.n_nodes != batches[0].n_nodes for b in batches):
+            raise ValueError("rollout frames must hold the same nodes (n_nodes differs)")
+        if objects is not None and len(objects) != len(batches):
+            raise ValueError("objects must give one entry (or None) per frame")
+        logits, state = [], prop
+        for k, batch in enumerate(batches):
+            z, state = self.forward_batch(batch, state, objects[k] if objects is not None else None, return_state=True)
+            logits.append(z)
+        return logits, state
 
     def _dense_batch(self, objects, sender_relations, receiver_relations, propagation, plan: str) -> TowerBatch:
         if plan == "host":
@@ -123,8 +165,8 @@ class GraphNetwork(nn.Module):
         return TowerBatch.from_dense_device(objects, sender_relations, receiver_relations, propagation)
 
     def forward_logits(self, objects, sender_relations, receiver_relations, propagation=None,
-                       plan: str = "host") -> torch.Tensor:
-        """(B, N) logits. A torch ``objects`` that requires grad receives d/d objects (B, N, 3) on
+                       plan: str = "host", return_state: bool = False):
+        """(B, N) logits; with ``return_state`` ``(logits, state)``, state (B, N, 100) (see `forward_batch`). A torch ``objects`` that requires grad receives d/d objects (B, N, 3) on
         backward (see `forward_batch`; the relations are constants).
         ``plan``: "host" converts the relation matrices on the host (`TowerBatch.from_dense`: a copy to
         the host, a C++ scan, an upload); "device" needs all inputs on the device and converts them there
@@ -135,14 +177,22 @@ class GraphNetwork(nn.Module):
         prop = None
         if propagation is not None:
             prop = torch.as_tensor(propagation, dtype=torch.float32, device=self.device).reshape(batch.n_nodes, 100)
-        z = self.forward_batch(batch, prop, objects if isinstance(objects, torch.Tensor) else None)
+        z = self.forward_batch(batch, prop, objects if isinstance(objects, torch.Tensor) else None,
+                               return_state=return_state)
+        if return_state:
+            z, state = z
+            return z.reshape(batch.node_shape), state.reshape(*batch.node_shape, E.STATE_WIDTH)
         return z.reshape(batch.node_shape)
 
-    def forward(self, objects, sender_relations, receiver_relations, propagation=None, plan: str = "host") -> torch.Tensor:
+    def forward(self, objects, sender_relations, receiver_relations, propagation=None, plan: str = "host",
+                return_state: bool = False):
         """(B, N, 1) probabilities: sigmoid(x[:, :, :1]) of the last step (Networks.py:93-96);
-        differentiable in a torch ``objects`` like `forward_logits` (``plan`` as there)."""
-        return torch.sigmoid(self.forward_logits(objects, sender_relations, receiver_relations, propagation,
-                                                 plan))[..., None]
+        differentiable in a torch ``objects`` like `forward_logits` (``plan`` as there). With
+        ``return_state`` ``(probabilities, state)``, state (B, N, 100)."""
+        z = self.forward_logits(objects, sender_relations, receiver_relations, propagation, plan, return_state)
+        if return_state:
+            return torch.sigmoid(z[0])[..., None], z[1]
+        return torch.sigmoid(z)[..., None]
 
     def forward_pooled(self, objects, sender_relations, receiver_relations, propagation=None,
                        mode: str = "mean_prob", plan: str = "host") -> torch.Tensor:
@@ -158,7 +208,7 @@ class GraphNetwork(nn.Module):
 
     def forward_positions(self, raw: torch.Tensor, threshold: Optional[float] = 170.0, divisor: float = 170.0,
                           tower_nodes=None, nw_max: Optional[int] = None, edge_cap=None, tower_ids=None,
-                          propagation: Optional[torch.Tensor] = None, check: bool = False) -> torch.Tensor:
+                          propagation: Optional[torch.Tensor] = None, check: bool = False, return_state: bool = False):
         """Logits from raw-pixel positions on the device, (B, N) for ``raw`` (B, N, 3) or (n_nodes,) for
         ragged towers ((n_nodes, 3) with ``tower_nodes``): the relation set (raw-pixel distance <
         ``threshold``, main.py:71-81) and the objects rows raw / ``divisor`` (main.py:91) are built on
@@ -176,5 +226,10 @@ class GraphNetwork(nn.Module):
             # the forward reads the batch's own rows (the kernel's raw / divisor); this node only carries
             # d/d objects back to raw through the division
             objects = raw.reshape(batch.n_nodes, raw.shape[-1])[:, :3] / divisor
-        z = self.forward_batch(batch, prop, objects)
+        z = self.forward_batch(batch, prop, objects, return_state=return_state)
+        if return_state:
+            z, state = z
+            if batch.node_shape is None:
+                return z, state
+            return z.reshape(batch.node_shape), state.reshape(*batch.node_shape, E.STATE_WIDTH)
         return z.reshape(batch.node_shape) if batch.node_shape is not None else z
