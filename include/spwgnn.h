@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
@@ -241,7 +241,8 @@ typedef struct spwgnn_run {
     void* grads_early_event;
 } spwgnn_run;
 
-/* Matrix-product arithmetic. F32 and X6 give fp32-class results; X3 and BF16 do not:
+/* Matrix-product arithmetic. F32 and X6 give fp32-class results, H3 fp32-class logits
+ * and X6's gradients; X3 and BF16 do not:
  *   F32  v_mfma_f32_*_f32: one fp32 fma chain per output (the f32 MFMA rate, 157 TF)
  *   X6   each fp32 operand split into three bf16 parts, six bf16 MFMA products per fp32 product,
  *        fp32 accumulation (6/16 of the f32 MFMA cost; error O(2^-24) per product)
@@ -257,16 +258,36 @@ typedef struct spwgnn_run {
  *        receiver sums of dh1pre) and bias gradients sum the two-part roundings of their values.
  *        Everything X6 keeps in fp32 stays fp32 (every stored array, the vector-ALU first layers,
  *        bias / relu / tanh / dropout, BCE, Adam); X3 takes X6's kernels, launch paths and f32
- *        fallbacks with two parts. Not fp32-class and not the parity path: between BF16 and X6. */
+ *        fallbacks with two parts. Not fp32-class and not the parity path: between BF16 and X6.
+ *   H3   (added within ABI 8) a mixed math: the forward's matrix products (the
+ *        encoders, the edge and node forward of every step, training and inference) split each fp32
+ *        operand x into two IEEE half parts, h = f16_rne(x), m = f16_rne(x − h), subnormal halves
+ *        kept, and run three f16 MFMA products per fp32 product in X3's order (a_m·b_h, a_h·b_m,
+ *        a_h·b_h) with fp32 accumulation; the forward receiver sum of h2 multiplies the exact one-hot
+ *        by the two parts. The operand error floor is 2^-25 absolute (22 mantissa bits for
+ *        |x| ≥ 2^-14): fp32-class logits at X3's instruction count. Every backward product (edge and
+ *        node backward, dA, every weight gradient, the encoder backwards, spwgnn_backward_inputs,
+ *        spwgnn_backward_state) is X6's, unchanged: gradients shrink below fp16's range layer by
+ *        layer, and fp16 parts there need per-tensor scales that are not built. Storage, workspace
+ *        size and layout, launch paths and fallbacks are X6's.
+ *        RANGE: an operand of a forward product (a weight, an activation, 'propagation') of
+ *        magnitude ≥ 65,520 rounds to inf in fp16 (65,504 is the largest half) and the logits become
+ *        inf / NaN; the library does not check this. Positions never enter a matrix product (the
+ *        first layers run in fp32 on the vector ALU) and a 'propagation' that comes from the network
+ *        is tanh-bounded. */
 #define SPWGNN_MATH_F32 0
 #define SPWGNN_MATH_X6 1
 #define SPWGNN_MATH_BF16 2
 #define SPWGNN_MATH_X3 3
+#define SPWGNN_MATH_H3 4
 
-/* bf16 MFMA products per fp32 product of a math id: 6 (X6), 3 (X3), 1 (BF16), 0 (F32: none, the
- * f32 matrix instructions); −1 for an id this library does not know. Bindings probe support of a
- * math with it and profilers price FLOPs by it. No device work. */
+/* 16-bit MFMA products per fp32 product of a math id: 6 (X6), 3 (X3, and H3: its forward's), 1 (BF16),
+ * 0 (F32: none, the f32 matrix instructions); −1 for an id this library does not know. Bindings probe
+ * support of a math with it and profilers price FLOPs by it. No device work. */
 int32_t spwgnn_math_products(int32_t math);
+/* (added within ABI 8) The same for the backward's products: 6 (X6 and H3), 3 (X3), 1 (BF16), 0 (F32),
+ * −1 for an unknown id — what a profiler prices the backward kernels at. No device work. */
+int32_t spwgnn_math_products_bwd(int32_t math);
 
 #define SPWGNN_K_NONE 0
 #define SPWGNN_K_EDGE_FWD 1

@@ -68,7 +68,7 @@ class PlanDeviceC(C.Structure):
 
 K_EDGE_FWD, K_NODE_FWD, K_EDGE_BWD, K_NODE_BWD, K_ENC_EDGE, K_ENC_EDGE_BWD, K_WGRAD_W2, K_DA = 1, 2, 3, 4, 5, 6, 7, 8
 K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD, K_INPUT_BWD, K_PLAN_DEVICE, K_STATE = 9, 10, 11, 12, 13, 14
-MATH_F32, MATH_X6, MATH_BF16, MATH_X3 = 0, 1, 2, 3
+MATH_F32, MATH_X6, MATH_BF16, MATH_X3, MATH_H3 = 0, 1, 2, 3, 4
 E_ARG, E_WORKSPACE, E_NOTRAIN = -1, -4, -6   # SPWGNN_E_* statuses the bindings name
 E_SHAPE, E_RELATION, E_CAPACITY = -2, -3, -5
 STEP_KEY_COUNTER, STEP_KEY_SPLITMIX = 0, 1
@@ -100,6 +100,7 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_team_max_blocks": (i32, [i32]),
         "spwgnn_da_stored_steps": (i32, [i32]),
         "spwgnn_math_products": (i32, [i32]),
+        "spwgnn_math_products_bwd": (i32, [i32]),
         "spwgnn_host_device_ptr": (i32, [vp, C.POINTER(vp)]),
         "spwgnn_forward": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp]),
         "spwgnn_backward": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp, vp]),

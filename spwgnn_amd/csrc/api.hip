@@ -8,7 +8,7 @@
 #include <vector>
 #include "../../include/spwgnn.h"
 static_assert(SPWGNN_MATH_F32 == spw::MATH_F32 && SPWGNN_MATH_X6 == spw::MATH_X6 && SPWGNN_MATH_BF16 == spw::MATH_BF16 &&
-                  SPWGNN_MATH_X3 == spw::MATH_X3,
+                  SPWGNN_MATH_X3 == spw::MATH_X3 && SPWGNN_MATH_H3 == spw::MATH_H3,
               "math ids");
 
 namespace spw {
@@ -283,7 +283,10 @@ static int kmath(const spwgnn_run* r, int bit) {
 #else
     constexpr int mask = -1;
 #endif
-    return (r->math != MATH_F32 && (mask & bit)) ? r->math : MATH_F32;
+    // a backward kernel runs the math of the run's backward (h3: x6's instantiations, math_bwd)
+    constexpr int bwd_bits = kX6NodeBwd | kX6EdgeBwd | kX6EncEdgeBwd | kX6Wgrad;
+    const int m = (bit & bwd_bits) ? math_bwd(r->math) : r->math;
+    return (r->math != MATH_F32 && (mask & bit)) ? m : MATH_F32;
 }
 
 // The rm.1 / om.1 weight gradients rebuild their operands z1 = relu(rm.0(d)) and zo1 = relu(om.0(y, w))
@@ -386,9 +389,9 @@ static bool fwd_fused_taken(const spwgnn_run* r, const spwgnn_batch* b) {
            !(b->flags & SPWGNN_BATCH_RECV_BLOCKS) && !store_b16_node(r, b) && !getenv_flag("SPWGNN_NO_FWD_FUSED");
 }
 static bool bwd_fused_taken(const spwgnn_run* r, const spwgnn_batch* b) {
-    const bool one_math = r->math == kmath(r, kX6NodeBwd) && r->math == kmath(r, kX6EdgeBwd) &&
-                          r->math == kmath(r, kX6EncEdgeBwd);
-    return one_math && rebuild_dA(r, b) && fwd_fused_team(b->n_wtiles, b->nw_max, b->n_eblocks, b->n_nodes, r->math) &&
+    const int mb = math_bwd(r->math);
+    const bool one_math = mb == kmath(r, kX6NodeBwd) && mb == kmath(r, kX6EdgeBwd) && mb == kmath(r, kX6EncEdgeBwd);
+    return one_math && rebuild_dA(r, b) && fwd_fused_team(b->n_wtiles, b->nw_max, b->n_eblocks, b->n_nodes, mb) &&
            !(b->flags & SPWGNN_BATCH_RECV_BLOCKS) && !store_b16_node(r, b) && !getenv_flag("SPWGNN_NO_BWD_FUSED");
 }
 
@@ -423,6 +426,7 @@ static int32_t run_forward(const float* params, const spwgnn_batch* b, const spw
             d.nkb = x6_nkb(sp);
             d.kh = sp.kh;
             d.ht = sp.ht;
+            d.f16 = math_fwd_f16(r->math) && x6_forward_image(sp.pack);   // h3: the forward's images as f16 parts
             d.dst = w.x6off[id];
             // an image reads pack elements (k < rows, col < cols) only
             if ((sp.kh ? 2 * sp.kh : 16 * sp.nkb) > pack_rows(sp.pack) || 32 * sp.nt_out > pack_cols(sp.pack))
@@ -1093,11 +1097,11 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
         fa.encoders = getenv_flag("SPWGNN_FUSED_ENC");
         fa.dA_in_loop = !getenv_flag("SPWGNN_DA_PAIR");
         SPW_CHECK(prof.before(SPWGNN_K_NODE_BWD));
-        SPW_CHECK(launch_bwd_fused_team(fa, r->math, st));
+        SPW_CHECK(launch_bwd_fused_team(fa, math_bwd(r->math), st));
         SPW_CHECK(prof.after(SPWGNN_K_NODE_BWD));
         if (!fa.encoders) {
             SPW_CHECK(prof.before(SPWGNN_K_ENC_EDGE_BWD));
-            SPW_CHECK(launch_bwd_enc_pair_team(da, eeb, enb, r->math, !fa.dA_in_loop, st));
+            SPW_CHECK(launch_bwd_enc_pair_team(da, eeb, enb, math_bwd(r->math), !fa.dA_in_loop, st));
             SPW_CHECK(prof.after(SPWGNN_K_ENC_EDGE_BWD));
         }
     } else {
@@ -1379,6 +1383,10 @@ int32_t spwgnn_da_stored_steps(int32_t set) {
 
 int32_t spwgnn_math_products(int32_t math) {
     return math_products(math);
+}
+
+int32_t spwgnn_math_products_bwd(int32_t math) {
+    return math_products_bwd(math);
 }
 
 int32_t spwgnn_forward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,

@@ -132,6 +132,45 @@ __device__ __forceinline__ void split2(float a, float b, uint32_t& h, uint32_t& 
     m = pk_bf16(ra, rb);
     l = pk_bf16(ra - bf16_lo_perm(m), rb - bf16_hi(m));
 }
+// The part count of a split-math instantiation with the element type of its parts: bf16 (x6, x3,
+// bf16 math) or, f16 set, IEEE half (the h3 math's forward: two parts, SPWGNN_MATH_H3). It reads as
+// the plain count wherever a kernel sizes or compares by parts (NP == 3, p < NP, [2 * NP * 64]).
+struct Np {
+    int n;
+    bool f16;
+    constexpr Np(int n_, bool f16_ = false) : n(n_), f16(f16_) {}
+    constexpr operator int() const { return n; }
+};
+constexpr Np kNpH3{2, true};
+// fp16 forms (h3): (a, b) → one packed f16 pair, RNE (v_cvt_pk_f16_f32 — the plain conversion; the
+// builtin cvt_pkrtz rounds toward zero); subnormal halves are kept (the kernels' default f16 mode),
+// |x| ≥ 65520 becomes inf
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ uint32_t pk_f16(float a, float b) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    const h2 r = {(_Float16)a, (_Float16)b};
+    return __builtin_bit_cast(uint32_t, r);
+}
+__device__ __forceinline__ float f16_lo(uint32_t p) {
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)(p & 0xffffu));
+}
+__device__ __forceinline__ float f16_hi(uint32_t p) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p >> 16)); }
+// the two-part fp16 split of h3: h = f16_rne(x), m = f16_rne(x − h) (x − h is exact in fp32); no third
+// part (l = 0: never read by an NP = 2 product)
+__device__ __forceinline__ void split2_f16(float a, float b, uint32_t& h, uint32_t& m, uint32_t& l) {
+    h = pk_f16(a, b);
+    m = pk_f16(a - f16_lo(h), b - f16_hi(h));
+    l = 0u;
+}
+// the split of a kernel's math: bf16 parts, or f16 parts when F16 (Np::f16 of its part count)
+template <bool F16>
+__device__ __forceinline__ void split2(float a, float b, uint32_t& h, uint32_t& m, uint32_t& l) {
+    if constexpr (F16) split2_f16(a, b, h, m, l);
+    else split2(a, b, h, m, l);
+}
+// 1.0 in the low half of a word, in the part type: the one-hot operands' entries
+template <bool F16>
+constexpr uint32_t kOne16 = F16 ? 0x3C00u : 0x3F80u;
 __device__ __forceinline__ bf16x8 as_bf16x8(i16x4 lo, i16x4 hi) {
     const i16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(bf16x8, v);
@@ -141,9 +180,18 @@ __device__ __forceinline__ bf16x8 as_bf16x8(uint4 v) { return __builtin_bit_cast
 // NP = 1 is the bf16 math (SPWGNN_MATH_BF16): the h parts alone, one product.
 // NP = 2 is the x3 math (SPWGNN_MATH_X3): parts h and m, the three products m·h, h·m, h·h — x6's
 // order without the terms that hold an l part and without m·m.
-template <int NP = 3>
+// NP.f16 (h3's forward, NP = 2): the same 16-bit packs read as IEEE halves, v_mfma_f32_*_f16 — x3's
+// three products in x3's order.
+__device__ __forceinline__ f16x8 as_f16x8(bf16x8 v) { return __builtin_bit_cast(f16x8, v); }
+template <Np NP = 3>
 __device__ __forceinline__ f32x4 mfma16_x6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4 c) {
     static_assert(NP >= 1 && NP <= 3, "parts");
+    if constexpr (NP.f16) {
+        static_assert(NP == 2, "f16 parts: the two-part form only");
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(a[1]), as_f16x8(b[0]), c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(a[0]), as_f16x8(b[1]), c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(a[0]), as_f16x8(b[0]), c, 0, 0, 0);
+    }
     if constexpr (NP == 1) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
     if constexpr (NP == 2) {
         c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], c, 0, 0, 0);
@@ -157,9 +205,15 @@ __device__ __forceinline__ f32x4 mfma16_x6(const bf16x8 (&a)[3], const bf16x8 (&
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
 }
-template <int NP = 3>
+template <Np NP = 3>
 __device__ __forceinline__ f32x16 mfma32_x6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 c) {
     static_assert(NP >= 1 && NP <= 3, "parts");
+    if constexpr (NP.f16) {
+        static_assert(NP == 2, "f16 parts: the two-part form only");
+        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(a[1]), as_f16x8(b[0]), c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(a[0]), as_f16x8(b[1]), c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(a[0]), as_f16x8(b[0]), c, 0, 0, 0);
+    }
     if constexpr (NP == 1) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
     if constexpr (NP == 2) {
         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
@@ -173,13 +227,31 @@ __device__ __forceinline__ f32x16 mfma32_x6(const bf16x8 (&a)[3], const bf16x8 (
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
 }
+// one product of the part type: a one-hot (or any single-part) operand times one part
+template <bool F16>
+__device__ __forceinline__ f32x16 mfma32_part(bf16x8 a, bf16x8 b, f32x16 c) {
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(a), as_f16x8(b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+template <bool F16>
+__device__ __forceinline__ f32x4 mfma16_part(bf16x8 a, bf16x8 b, f32x4 c) {
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(a), as_f16x8(b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
 // The six products of NT output tiles interleaved (product p for every tile before product p+1):
 // consecutive MFMAs write different accumulators, which the matrix pipe overlaps better than one
 // tile's chain of six (measured, tools/mb/x6dep.hip: 0.77 -> 0.80 of the bf16 peak at two waves per
 // SIMD with LDS-fed fragments). Same products and per-accumulator order as mfma32_x6: bit-identical.
-template <int NP, int NT>
+template <Np NP, int NT>
 __device__ __forceinline__ void mfma32_x6_group(const bf16x8 (&a)[3], const bf16x8 (&b)[NT][3], f32x16* acc) {
-    if constexpr (NP == 1) {
+    if constexpr (NP.f16) {
+        static_assert(NP == 2, "f16 parts: the two-part form only");
+        constexpr int pa[3] = {1, 0, 0}, pb[3] = {0, 1, 0};
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int u = 0; u < NT; ++u) acc[u] = mfma32_part<true>(a[pa[p]], b[u][pb[p]], acc[u]);
+    } else if constexpr (NP == 1) {
 #pragma unroll
         for (int u = 0; u < NT; ++u) acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[u][0], acc[u], 0, 0, 0);
     } else if constexpr (NP == 2) {

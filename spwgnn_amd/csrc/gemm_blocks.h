@@ -493,7 +493,7 @@ __device__ __forceinline__ void ht_leave(const f32x4 (&q)[NC][2], f32x16 (&out)[
         }
 }
 // k-block pair (x0 = k-block 2P, x1 = 2P + 1 or absent) of column tile c into its two half accumulators
-template <int PARTS, int NC>
+template <Np PARTS, int NC>
 __device__ __forceinline__ void ht_mfma(const bf16x8 (&a)[3], const uint32_t (&x0)[NC][3][4], const uint32_t (&x1)[NC][3][4],
                                         bool has1, f32x4 (&q)[NC][2]) {
     constexpr int LP = PARTS;   // parts the math reads: x6 3, x3 2, bf16 1
@@ -538,7 +538,7 @@ template <int NT_OUT, int INT, int T0>
 __device__ __forceinline__ constexpr int x6_img_step(int u) {
     return INT == NT_OUT && T0 == 0 ? u : (u / NT_OUT) * INT + T0 + u % NT_OUT;
 }
-template <int NT_OUT, int NKB, int NC, int D = kX6Ring, int PARTS = 3, bool HT = false, int INT = NT_OUT, int T0 = 0,
+template <int NT_OUT, int NKB, int NC, int D = kX6Ring, Np PARTS = 3, bool HT = false, int INT = NT_OUT, int T0 = 0,
           class GetB>
 __device__ __forceinline__ void tgemm_x6(GetB&& getb, f32x16 (&out)[NC][NT_OUT], const uint4* __restrict__ img,
                                          int lane) {
@@ -566,7 +566,7 @@ __device__ __forceinline__ void tgemm_x6(GetB&& getb, f32x16 (&out)[NC][NT_OUT],
         } else {
             float v[8];
             getb(c, kb, v);
-            split2(v[2 * m], v[2 * m + 1], sp[kb % SPD][c][0][m], sp[kb % SPD][c][1][m], sp[kb % SPD][c][2][m]);
+            split2<PARTS.f16>(v[2 * m], v[2 * m + 1], sp[kb % SPD][c][0][m], sp[kb % SPD][c][1][m], sp[kb % SPD][c][2][m]);
         }
     };
 #pragma unroll
@@ -626,7 +626,7 @@ template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
-template <int NT_OUT, int NKB, int NC, int NW, int PARTS = 3, bool HT = false, int INT = NT_OUT, int T0 = 0, class GetB>
+template <int NT_OUT, int NKB, int NC, int NW, Np PARTS = 3, bool HT = false, int INT = NT_OUT, int T0 = 0, class GetB>
 __device__ __forceinline__ void tgemm_x6_wg(GetB&& getb, f32x16 (&out)[NC][NT_OUT], const uint4* __restrict__ img,
                                             int lane, const WgRing<NW>& wr) {
     static_assert(!HT || NT_OUT == 4, "half tile: 4-tile products");
@@ -669,7 +669,7 @@ __device__ __forceinline__ void tgemm_x6_wg(GetB&& getb, f32x16 (&out)[NC][NT_OU
         } else {
             float v[8];
             getb(c, kb, v);
-            split2(v[2 * m], v[2 * m + 1], sp[kb % SPD][c][0][m], sp[kb % SPD][c][1][m], sp[kb % SPD][c][2][m]);
+            split2<PARTS.f16>(v[2 * m], v[2 * m + 1], sp[kb % SPD][c][0][m], sp[kb % SPD][c][1][m], sp[kb % SPD][c][2][m]);
         }
     };
 #pragma unroll
@@ -720,7 +720,7 @@ __device__ __forceinline__ void tgemm_x6_wg(GetB&& getb, f32x16 (&out)[NC][NT_OU
     }
     if constexpr (HT) ht_leave(hq, out);
 }
-template <int NT_OUT, int NKB, int NT_IN, int NC, int NW, int PARTS = 3, bool HT = false>
+template <int NT_OUT, int NKB, int NT_IN, int NC, int NW, Np PARTS = 3, bool HT = false>
 __device__ __forceinline__ void tchain_x6_wg(const f32x16 (&in)[NC][NT_IN], f32x16 (&out)[NC][NT_OUT],
                                              const uint4* __restrict__ img, int lane, const WgRing<NW>& wr) {
     static_assert(NKB <= 2 * NT_IN, "k-blocks beyond the input tiles");
@@ -735,7 +735,7 @@ __device__ __forceinline__ void tchain_x6_wg(const f32x16 (&in)[NC][NT_IN], f32x
 // Chain layer: B = the C layout of the previous layer; k-block kb of tile t = kb>>1 is registers
 // 8(kb&1) .. +7 of in[c][t] (element e of lane half h = feature 16kb + 8(e>>2) + 4h + (e&3): image
 // kind X6_CHAIN).
-template <int NT_OUT, int NKB, int NT_IN, int NC, int D = kX6Ring, int PARTS = 3, bool HT = false>
+template <int NT_OUT, int NKB, int NT_IN, int NC, int D = kX6Ring, Np PARTS = 3, bool HT = false>
 __device__ __forceinline__ void tchain_x6(const f32x16 (&in)[NC][NT_IN], f32x16 (&out)[NC][NT_OUT],
                                           const uint4* __restrict__ img, int lane) {
     static_assert(NKB <= 2 * NT_IN, "k-blocks beyond the input tiles");
@@ -750,13 +750,13 @@ __device__ __forceinline__ void tchain_x6(const f32x16 (&in)[NC][NT_IN], f32x16 
 // Kernels templated on the weight source: NW = 0 → each wave streams the image itself (tgemm_x6's
 // register ring, depth D), NW > 0 → the workgroup's shared LDS ring (tgemm_x6_wg).
 // HT: the half-tile form (4-tile products on the ht images, kernels.h X6Desc)
-template <int NT_OUT, int NKB, int NC, int D, int PARTS, int NW, bool HT = false, class GetB>
+template <int NT_OUT, int NKB, int NC, int D, Np PARTS, int NW, bool HT = false, class GetB>
 __device__ __forceinline__ void tgemm_x6s(GetB&& getb, f32x16 (&out)[NC][NT_OUT], const uint4* __restrict__ img, int lane,
                                           const WgRing<NW>& wr) {
     if constexpr (NW > 0) tgemm_x6_wg<NT_OUT, NKB, NC, NW, PARTS, HT>(getb, out, img, lane, wr);
     else tgemm_x6<NT_OUT, NKB, NC, D, PARTS, HT>(getb, out, img, lane);
 }
-template <int NT_OUT, int NKB, int NT_IN, int NC, int D, int PARTS, int NW, bool HT = false>
+template <int NT_OUT, int NKB, int NT_IN, int NC, int D, Np PARTS, int NW, bool HT = false>
 __device__ __forceinline__ void tchain_x6s(const f32x16 (&in)[NC][NT_IN], f32x16 (&out)[NC][NT_OUT],
                                            const uint4* __restrict__ img, int lane, const WgRing<NW>& wr) {
     if constexpr (NW > 0) tchain_x6_wg<NT_OUT, NKB, NT_IN, NC, NW, PARTS, HT>(in, out, img, lane, wr);
@@ -766,7 +766,7 @@ __device__ __forceinline__ void tchain_x6s(const f32x16 (&in)[NC][NT_IN], f32x16
 // backward's first step: dx' is the logit row alone). The skipped k-blocks would add ±0 to the
 // accumulators, so for KB the last k-block the sums are those of the whole chain. (HT: KB must be
 // the image's last k-block and even — its half-tile slot then holds that k-block alone.)
-template <int NT_OUT, int KB, int NT_IN, int NC, int D, int PARTS, int NW, bool HT = false>
+template <int NT_OUT, int KB, int NT_IN, int NC, int D, Np PARTS, int NW, bool HT = false>
 __device__ __forceinline__ void tchain_x6s_kb(const f32x16 (&in)[NC][NT_IN], f32x16 (&out)[NC][NT_OUT],
                                               const uint4* __restrict__ img, int lane, const WgRing<NW>& wr) {
     static_assert(KB < 2 * NT_IN, "k-block beyond the input tiles");
@@ -780,7 +780,7 @@ __device__ __forceinline__ void tchain_x6s_kb(const f32x16 (&in)[NC][NT_IN], f32
 // Output tile T0 alone of a chain product on an INT-tile image (the node forward's last step: only
 // the logit's tile of o1·Wo2' is consumed). The tile's accumulator takes the MFMAs it takes in the
 // whole product, in the same k order: bit-identical.
-template <int T0, int INT, int NKB, int NT_IN, int NC, int D, int PARTS, int NW>
+template <int T0, int INT, int NKB, int NT_IN, int NC, int D, Np PARTS, int NW>
 __device__ __forceinline__ void tchain_x6s_tile(const f32x16 (&in)[NC][NT_IN], f32x16 (&out)[NC][1],
                                                 const uint4* __restrict__ img, int lane, const WgRing<NW>& wr) {
     static_assert(NKB <= 2 * NT_IN, "k-blocks beyond the input tiles");

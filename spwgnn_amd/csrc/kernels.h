@@ -88,11 +88,22 @@ constexpr X6Spec kX6Specs[X6_COUNT] = {
 #define SPWGNN_HT 0
 #endif
 constexpr bool kHT = SPWGNN_HT != 0;
+// an image that a forward kernel reads (h3: built as f16 parts); no backward kernel reads one of these
+inline bool x6_forward_image(int pack) {
+    switch (pack) {
+        case PK_RM1: case PK_RM2: case PK_RM3: case PK_W1A: case PK_W2: case PK_W3A: case PK_WO1C: case PK_WO1A:
+        case PK_WO1P: case PK_WO2: case PK_W1B: case PK_W1C: case PK_OM1:
+            return true;
+        default:
+            return false;
+    }
+}
 inline int x6_nkb(const X6Spec& s) { return s.ht && !kHT ? 0 : s.nkb; }
 struct X6Desc {
     int32_t pack;       // source fp32 pack (PackId): element (k, col) of it
     int32_t nt_out, nkb;
     int32_t kh, ht;
+    int32_t f16;        // h3 math, an image a forward kernel reads: parts h, m as IEEE halves (x6_forward_image)
     int64_t dst;        // uint4 offset into the image buffer
 };
 // the images k_prep builds: the half-tile forms only in kHT builds (kernel-argument space)
@@ -430,20 +441,37 @@ hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st);
 hipError_t launch_enc_edge_bwd(const EncEdgeBwdArgs& a, int math, hipStream_t st);
 hipError_t launch_dA(const DaArgs& a, int math, hipStream_t st);
 hipError_t launch_enc_node_bwd(const EncNodeBwdArgs& a, int math, hipStream_t st);
-enum MathMode : int { MATH_F32 = 0, MATH_X6 = 1, MATH_BF16 = 2, MATH_X3 = 3 };   // = SPWGNN_MATH_* (spwgnn.h)
-// split math with fp32 storage: x6 (three parts) and x3 (two parts) take the same kernels, launch
-// paths and fallbacks and differ in the part count the kernels are instantiated with
-inline bool math_split32(int math) { return math == MATH_X6 || math == MATH_X3; }
-// bf16 MFMA products per fp32 product (spwgnn_math_products)
+enum MathMode : int { MATH_F32 = 0, MATH_X6 = 1, MATH_BF16 = 2, MATH_X3 = 3, MATH_H3 = 4 };   // = SPWGNN_MATH_* (spwgnn.h)
+// split math with fp32 storage: x6 (three parts), x3 (two parts) and h3 (two f16 parts forward, x6
+// backward) take the same kernels, launch paths and fallbacks and differ in the parts the kernels are
+// instantiated with
+inline bool math_split32(int math) { return math == MATH_X6 || math == MATH_X3 || math == MATH_H3; }
+// What a math's two directions are instantiated with — the one place that knows h3 is mixed:
+//   math_fwd_f16  the forward's part type is IEEE half (h3) instead of bf16
+//   math_bwd      the math whose instantiations the backward kernels (edge / node backward, dA, weight
+//                 gradients, encoder backwards, input gradients) run: h3's backward is x6's, unchanged
+inline bool math_fwd_f16(int math) { return math == MATH_H3; }
+inline int math_bwd(int math) { return math == MATH_H3 ? MATH_X6 : math; }
+// 16-bit MFMA products per fp32 product of the forward (spwgnn_math_products) and of the backward
+// (spwgnn_math_products_bwd)
 inline int math_products(int math) {
-    return math == MATH_X6 ? 6 : math == MATH_X3 ? 3 : math == MATH_BF16 ? 1 : math == MATH_F32 ? 0 : -1;
+    return math == MATH_X6 ? 6 : (math == MATH_X3 || math == MATH_H3) ? 3 : math == MATH_BF16 ? 1 : math == MATH_F32 ? 0 : -1;
 }
+inline int math_products_bwd(int math) { return math_products(math) < 0 ? -1 : math_products(math_bwd(math)); }
 // A launch of a kernel templated on the part count, in a split math with fp32 storage:
-// SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k<NP>), ...)) instantiates both forms and runs the math's
+// SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k<NP>), ...)) instantiates both forms and runs the math's.
+// The backward's form: callers hand it math_bwd(math), so h3 never arrives (it would run x6's).
 #define SPW_SPLIT32(math, NPV, ...)                                 \
     do {                                                            \
         if ((math) == MATH_X3) { constexpr int NPV = 2; __VA_ARGS__; } \
         else { constexpr int NPV = 3; __VA_ARGS__; }                \
+    } while (0)
+// The forward's form: also h3's two f16 parts (Np, device_common.h)
+#define SPW_SPLIT32F(math, NPV, ...)                                        \
+    do {                                                                    \
+        if ((math) == MATH_X3) { constexpr Np NPV = 2; __VA_ARGS__; }       \
+        else if ((math) == MATH_H3) { constexpr Np NPV = kNpH3; __VA_ARGS__; } \
+        else { constexpr Np NPV = 3; __VA_ARGS__; }                         \
     } while (0)
 hipError_t launch_wgrad(const WgradArgs& a, int chunks, int math, hipStream_t st);
 hipError_t launch_wgrad_ws(const WgWsArgs& a, int wgs, int kx_pad, int ny_pad, int yrow, int mask, int math,

@@ -83,7 +83,11 @@ __global__ void k_prep(PrepArgs a, PrepX6Args x) {
         }
         uint32_t hw[4], mw[4], lw[4];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) split2(w[2 * m], w[2 * m + 1], hw[m], mw[m], lw[m]);
+        for (int m = 0; m < 4; ++m) {
+            // h3: an image the forward reads holds f16 h and m (its third part zero: never read)
+            if (d.f16) split2_f16(w[2 * m], w[2 * m + 1], hw[m], mw[m], lw[m]);
+            else split2(w[2 * m], w[2 * m + 1], hw[m], mw[m], lw[m]);
+        }
         uint4* o = x.img + d.dst + (int64_t)u * 3 * 64 + lane;
         o[0] = make_uint4(hw[0], hw[1], hw[2], hw[3]);
         o[64] = make_uint4(mw[0], mw[1], mw[2], mw[3]);
@@ -160,7 +164,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 // wave, two waves per SIMD).
 // NW > 0: weight images shared by the workgroup's waves (tgemm_x6_wg); a wave past the last node
 // block runs on the last block and stores nothing.
-template <int NP, int NW = 0>
+template <Np NP, int NW = 0>
 __global__ __launch_bounds__(256, 2) void k_enc_node_x6(EncNodeArgs a) {
     const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
     const int nb = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -321,7 +325,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #ifndef SPWGNN_ENC_NW_X6    // the same in split-bf16 (x6) math
 #define SPWGNN_ENC_NW_X6 4
 #endif
-template <bool TRAIN, int NC, int NP = 3, bool B16 = false, int NW = 0>
+template <bool TRAIN, int NC, Np NP = 3, bool B16 = false, int NW = 0>
 __global__ __launch_bounds__(NW > 4 ? 64 * NW : 256, NC == 1 && NW <= 4 ? 2 : 1) void k_enc_edge_x6(EncEdgeArgs a) {
     constexpr int kWaves = NW > 4 ? NW : 4;   // waves per workgroup (NW > 0: all share one weight ring)
     const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
@@ -710,7 +714,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 // NW > 0: the workgroup's 4 waves share each weight image through an LDS ring (tgemm_x6_wg; no
 // early exit, a wave past the last node block runs on the clamped block and stores nothing).
 // N16 (bf16 math, §3o): H2s read and o1 stored as bf16
-template <int NC, int NP = 3, int NW = 0, bool N16 = false>
+template <int NC, Np NP = 3, int NW = 0, bool N16 = false>
 __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_fwd_x6(NodeFwdArgs a) {
     const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
     const int nb0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * NC;
@@ -842,7 +846,7 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_fwd_x6(NodeFwdArg
 // operand straight from the loads; W2 (x6 image, 150 KB) is the LDS B operand. The receiver sum
 // runs as one-hot [node][edge] (exact in bf16) × h2 parts: 3 MFMAs per 16 edges per feature tile.
 // 4 waves (one per SIMD: 512 registers) per CU, A/U/V prefetched kX6Pf k-blocks ahead.
-template <int NP>
+template <Np NP>
 struct NodeSumX6 {
     f32x16 acc[5];
     int key;
@@ -864,7 +868,7 @@ struct NodeSumX6 {
                     const int e = 2 * m + q;
                     const int d0 = __builtin_amdgcn_readlane(d, rho(8 * s + e, 0));
                     const int d1 = __builtin_amdgcn_readlane(d, rho(8 * s + e, 1));
-                    w |= ((h ? d1 : d0) == key ? 0x3F80u : 0u) << (16 * q);
+                    w |= ((h ? d1 : d0) == key ? kOne16<NP.f16> : 0u) << (16 * q);
                 }
                 oh[m] = w;
             }
@@ -874,12 +878,12 @@ struct NodeSumX6 {
             for (int t = 0; t < 5; ++t) {
                 uint32_t hw[4], mw[4], lw[4];
 #pragma unroll
-                for (int m = 0; m < 4; ++m) split2(h2[t][8 * s + 2 * m], h2[t][8 * s + 2 * m + 1], hw[m], mw[m], lw[m]);
+                for (int m = 0; m < 4; ++m) split2<NP.f16>(h2[t][8 * s + 2 * m], h2[t][8 * s + 2 * m + 1], hw[m], mw[m], lw[m]);
                 if constexpr (NP == 3)
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], as_bf16x8(make_uint4(lw[0], lw[1], lw[2], lw[3])), acc[t], 0, 0, 0);
+                    acc[t] = mfma32_part<NP.f16>(a[0], as_bf16x8(make_uint4(lw[0], lw[1], lw[2], lw[3])), acc[t]);
                 if constexpr (NP >= 2)   // x3: the sum of the 2-part roundings
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], as_bf16x8(make_uint4(mw[0], mw[1], mw[2], mw[3])), acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], as_bf16x8(make_uint4(hw[0], hw[1], hw[2], hw[3])), acc[t], 0, 0, 0);
+                    acc[t] = mfma32_part<NP.f16>(a[0], as_bf16x8(make_uint4(mw[0], mw[1], mw[2], mw[3])), acc[t]);
+                acc[t] = mfma32_part<NP.f16>(a[0], as_bf16x8(make_uint4(hw[0], hw[1], hw[2], hw[3])), acc[t]);
             }
         }
     }
@@ -906,7 +910,7 @@ struct NodeSumX6 {
 // register pair turns the 32-feature C tiles into two 16-feature B operands of 32 edges each
 // (lane group g of a swapped register = edges of (s = g&1, h = g>>1)), so a block costs 30 MFMAs of
 // 16 cycles into 40 accumulator registers.
-template <int NP>
+template <Np NP>
 struct NodeSum16X6 {
     f32x4 acc[10];   // sub-tile u: features 16u + (lane & 15), nodes 4(lane >> 4) + r
     int key, n0;
@@ -933,12 +937,12 @@ struct NodeSum16X6 {
                 const int e = 2 * m + q, base = 8 * (e >> 2) + (e & 3);
 #if SPWGNN_ONEHOT_BPERM
                 const int dn = __builtin_amdgcn_ds_bpermute(4 * (gb + base), ld);
-                w |= (dn == (lane & 15) ? 0x3F80u : 0u) << (16 * q);
+                w |= (dn == (lane & 15) ? kOne16<NP.f16> : 0u) << (16 * q);
 #else
                 const int d0 = __builtin_amdgcn_readlane(d, base), d1 = __builtin_amdgcn_readlane(d, base + 16);
                 const int d2 = __builtin_amdgcn_readlane(d, base + 4), d3 = __builtin_amdgcn_readlane(d, base + 20);
                 const int dn = g == 0 ? d0 : g == 1 ? d1 : g == 2 ? d2 : d3;
-                w |= (dn == key ? 0x3F80u : 0u) << (16 * q);
+                w |= (dn == key ? kOne16<NP.f16> : 0u) << (16 * q);
 #endif
             }
             oh[m] = w;
@@ -951,7 +955,7 @@ struct NodeSum16X6 {
             for (int s = 0; s < 2; ++s)
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
-                    split2(h2[t][8 * s + 2 * m], h2[t][8 * s + 2 * m + 1], P[s][0][m], P[s][1][m], P[s][2][m]);
+                    split2<NP.f16>(h2[t][8 * s + 2 * m], h2[t][8 * s + 2 * m + 1], P[s][0][m], P[s][1][m], P[s][2][m]);
 #pragma unroll
             for (int p = 0; p < 3; ++p)
 #pragma unroll
@@ -964,8 +968,8 @@ struct NodeSum16X6 {
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int p = NP - 1; p >= 0; --p)
-                    acc[2 * t + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        ao, as_bf16x8(make_uint4(P[u][p][0], P[u][p][1], P[u][p][2], P[u][p][3])), acc[2 * t + u], 0, 0, 0);
+                    acc[2 * t + u] = mfma16_part<NP.f16>(
+                        ao, as_bf16x8(make_uint4(P[u][p][0], P[u][p][1], P[u][p][2], P[u][p][3])), acc[2 * t + u]);
         }
     }
     // B16: bf16 at the element index (bf16 math: H2s only ever feeds bf16 MFMA operands, §3o)
@@ -1011,7 +1015,7 @@ struct NodeSum16X6 {
 // DESC (§3zk): the A rows and the gathered U, V rows through buffer descriptors — the block's A base
 // and the node arrays are wave-uniform, a lane keeps one 32-bit offset per row and the chunk goes
 // into the load's scalar offset (the pointer form adds 64·q·16 bytes to a 64-bit pointer per piece)
-template <bool NW16, int DBG = 0, int NP = 3, bool AB16 = false, bool W8 = false, bool N16 = false,   // AB16: A stored as bf16 (§3g)
+template <bool NW16, int DBG = 0, Np NP = 3, bool AB16 = false, bool W8 = false, bool N16 = false,   // AB16: A stored as bf16 (§3g)
           bool UV0 = false, bool DESC = false>
 __global__ __launch_bounds__((NW16 || W8) ? 512 : 256, 1) __attribute__((amdgpu_waves_per_eu((NW16 || W8) ? 2 : 1, (NW16 || W8) ? 2 : 1)))
 void k_edge_fwd_x6(EdgeFwdArgs a) {
@@ -1137,7 +1141,7 @@ void k_edge_fwd_x6(EdgeFwdArgs a) {
             }
             uint32_t hw[4], mw[4], lw[4];
 #pragma unroll
-            for (int m = 0; m < 4; ++m) split2(xv[2 * m], xv[2 * m + 1], hw[m], mw[m], lw[m]);
+            for (int m = 0; m < 4; ++m) split2<NP.f16>(xv[2 * m], xv[2 * m + 1], hw[m], mw[m], lw[m]);
             if (kb + kPfA < 10) ldA(cur.ai, cur.ab, kb + kPfA, ca);
             else ldA(nai, DBG == 1 ? (nblk & 7) : nblk, kb + kPfA - 10, ca);
             if (kb + kX6Pf < 10) {
@@ -1259,7 +1263,7 @@ void k_edge_fwd_x6(EdgeFwdArgs a) {
 #ifndef SPWGNN_RB_PF
 #define SPWGNN_RB_PF 2
 #endif
-template <int NP = 3, bool MASKS = true>
+template <Np NP = 3, bool MASKS = true>
 __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_edge_fwd_rb_x6(EdgeFwdArgs a) {
     constexpr int kWaves = 8, kPf = SPWGNN_RB_PF;
@@ -1321,7 +1325,7 @@ void k_edge_fwd_rb_x6(EdgeFwdArgs a) {
             }
             uint32_t hw[4], mw[4], lw[4];
 #pragma unroll
-            for (int m = 0; m < 4; ++m) split2(xv[2 * m], xv[2 * m + 1], hw[m], mw[m], lw[m]);
+            for (int m = 0; m < 4; ++m) split2<NP.f16>(xv[2 * m], xv[2 * m + 1], hw[m], mw[m], lw[m]);
             if (kb + kPf < 10) {
                 ld(cur, kb + kPf, cr);
             } else {
@@ -1459,7 +1463,7 @@ hipError_t launch_enc_node(const EncNodeArgs& a, int math, hipStream_t st) {
     if (a.uv16 && math != MATH_BF16) return hipErrorInvalidValue;   // rounded U0, V0: the bf16 kernels only
     if ((math_split32(math) || math == MATH_BF16) && team_blocks(waves)) return launch_enc_node_team(a, math, st);
     if (math_split32(math)) {
-        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_node_x6<NP, 4>), dim3((waves + 3) / 4), dim3(256), 0, st, a));
+        SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_enc_node_x6<NP, 4>), dim3((waves + 3) / 4), dim3(256), 0, st, a));
         return hipGetLastError();
     }
     if (math == MATH_BF16) {
@@ -1484,9 +1488,9 @@ hipError_t launch_enc_edge(const EncEdgeArgs& a, int math, hipStream_t st) {
         } else if (train) {
             constexpr int NWX = SPWGNN_ENC_NW_X6;
             const dim3 gx((a.n_eblocks + NWX * NC - 1) / (NWX * NC));
-            SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_edge_x6<true, NC, NP, false, NWX>), gx, dim3(64 * NWX), 0, st, a));
+            SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_enc_edge_x6<true, NC, NP, false, NWX>), gx, dim3(64 * NWX), 0, st, a));
         } else {
-            SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_edge_x6<false, NC, NP, false, NW>), g, dim3(256), 0, st, a));
+            SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_enc_edge_x6<false, NC, NP, false, NW>), g, dim3(256), 0, st, a));
         }
         return hipGetLastError();
     }
@@ -1504,7 +1508,7 @@ hipError_t launch_enc_edge(const EncEdgeArgs& a, int math, hipStream_t st) {
 #endif
 constexpr bool kEfwdUv0 = SPWGNN_EFWD_UV0 != 0;
 // the ≤ 16-node wide forms: buffer-descriptor loads (EdgeFwdArgs::gather_desc) or 64-bit pointers
-template <int NP, bool AB16, bool N16, bool UV0>
+template <Np NP, bool AB16, bool N16, bool UV0>
 static void launch_edge_fwd16(const EdgeFwdArgs& a, hipStream_t st) {
     const dim3 g(edge_grid(a.n_wtiles, 8)), b(512);
     if (a.gather_desc) hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, NP, AB16, false, N16, UV0, true>), g, b, 0, st, a);
@@ -1563,8 +1567,8 @@ hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
             cus = 256;
         const int need = (a.n_nodes + 8 * 16 - 1) / (8 * 16);   // ≥ 16 blocks per wave
         const dim3 g(std::max(1, std::min(cus, need))), b(512);
-        if (a.mask1 || a.mask2) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_fwd_rb_x6<NP, true>), g, b, 0, st, a));
-        else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_fwd_rb_x6<NP, false>), g, b, 0, st, a));
+        if (a.mask1 || a.mask2) SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_edge_fwd_rb_x6<NP, true>), g, b, 0, st, a));
+        else SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_edge_fwd_rb_x6<NP, false>), g, b, 0, st, a));
         return hipGetLastError();
     }
     if (math_split32(math)) {
@@ -1581,12 +1585,12 @@ hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
             hipLaunchKernelGGL((k_edge_fwd_x6<true, 2>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a);
 #endif
         else if (a.nw_max <= 16 && kEfwdUv0 && a.uv_zero)
-            SPW_SPLIT32(math, NP, (launch_edge_fwd16<NP, false, false, true>(a, st)));
+            SPW_SPLIT32F(math, NP, (launch_edge_fwd16<NP, false, false, true>(a, st)));
         else if (a.nw_max <= 16)
-            SPW_SPLIT32(math, NP, (launch_edge_fwd16<NP, false, false, false>(a, st)));
+            SPW_SPLIT32F(math, NP, (launch_edge_fwd16<NP, false, false, false>(a, st)));
         else   // ≤ 32-node tiles: two waves per SIMD (config 5: 37.5 -> 34.4 ms per forward, A/B on one box;
                // 36 spilled registers, an inference-only instantiation without the mask code spills 612)
-            SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_fwd_x6<false, 0, NP, false, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a));
+            SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_edge_fwd_x6<false, 0, NP, false, true>), dim3(edge_grid(a.n_wtiles, 8)), dim3(512), 0, st, a));
         return hipGetLastError();
     }
     if (a.nw_max <= 16)
@@ -1607,7 +1611,7 @@ hipError_t launch_node_fwd(const NodeFwdArgs& a, int math, hipStream_t st) {
         // workgroup's 4 waves through an LDS ring (0.532 → 0.437 ms)
         constexpr int NC = 1;
         const int w2 = (waves + NC - 1) / NC;
-        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_node_fwd_x6<NC, NP, 4>), dim3((w2 + 3) / 4), dim3(256), 0, st, a));
+        SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_node_fwd_x6<NC, NP, 4>), dim3((w2 + 3) / 4), dim3(256), 0, st, a));
         return hipGetLastError();
     }
     if (math == MATH_BF16) {

@@ -35,8 +35,9 @@ constexpr int kTeamEdge = 5;   // waves per edge block (150-wide layers: 5 tiles
 // LDS exchange of C-layout tiles, already split: [buf][tile][kh][part][lane] uint4 = the bf16 parts
 // (split2, as tgemm_x6 splits them) of registers 8kh .. 8kh+7 of the tile — the B operand of the
 // next layer's k-block 2t + kh. The producer splits its tile once; the consumers only read.
-template <int NT, int NP>
+template <int NT, Np NPT>
 struct TeamAct {
+    static constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     uint4* s;
     __device__ __forceinline__ uint4* at(int buf, int t, int kh, int p, int lane) const {
         return s + (((buf * NT + t) * 2 + kh) * NP + p) * 64 + lane;
@@ -46,7 +47,7 @@ struct TeamAct {
         for (int kh = 0; kh < 2; ++kh) {
             uint32_t sp[3][4];
 #pragma unroll
-            for (int m = 0; m < 4; ++m) split2(x[8 * kh + 2 * m], x[8 * kh + 2 * m + 1], sp[0][m], sp[1][m], sp[2][m]);
+            for (int m = 0; m < 4; ++m) split2<NPT.f16>(x[8 * kh + 2 * m], x[8 * kh + 2 * m + 1], sp[0][m], sp[1][m], sp[2][m]);
 #pragma unroll
             for (int p = 0; p < NP; ++p) *at(buf, t, kh, p, lane) = make_uint4(sp[p][0], sp[p][1], sp[p][2], sp[p][3]);
         }
@@ -68,14 +69,16 @@ __device__ __forceinline__ void team_sync() {
     asm volatile("" ::: "memory");
 }
 // B values in registers (8 per k-block) → the split operand
+template <bool F16 = false>   // F16: the h3 forward's part type (Np::f16)
 __device__ __forceinline__ void split8(const float (&v)[8], uint32_t (&sp)[3][4]) {
 #pragma unroll
-    for (int m = 0; m < 4; ++m) split2(v[2 * m], v[2 * m + 1], sp[0][m], sp[1][m], sp[2][m]);
+    for (int m = 0; m < 4; ++m) split2<F16>(v[2 * m], v[2 * m + 1], sp[0][m], sp[1][m], sp[2][m]);
 }
 
 // wave T's fragments of one x6 image (the parts the math uses)
-template <int NKB, int NP>
+template <int NKB, Np NPT>
 struct TeamFrags {
+    static constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     uint4 f[NKB][3];
     __device__ __forceinline__ void load_kb(const uint4* __restrict__ img, int nt_out, int T, int lane, int kb) {
 #pragma unroll
@@ -93,8 +96,9 @@ struct TeamFrags {
 // next(kb) may refill f[kb] with the next layer's fragment.
 // K (default: all NKB) k-blocks: a layer of fewer k-blocks may run on the first K fragments of a
 // larger set (one fragment array serves a 10-k-block layer and the 7-k-block layers after it)
-template <int K = -1, int NKB, int NP, class GetSp, class Next>
-__device__ __forceinline__ f32x16 team_gemm(TeamFrags<NKB, NP>& F, GetSp&& getsp, Next&& next, f32x16 acc = zero16()) {
+template <int K = -1, int NKB, Np NPT, class GetSp, class Next>
+__device__ __forceinline__ f32x16 team_gemm(TeamFrags<NKB, NPT>& F, GetSp&& getsp, Next&& next, f32x16 acc = zero16()) {
+    constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     constexpr int NK = K < 0 ? NKB : K;
     static_assert(NK <= NKB, "k-blocks beyond the fragment set");
     uint32_t sp[2][3][4];
@@ -109,7 +113,7 @@ __device__ __forceinline__ f32x16 team_gemm(TeamFrags<NKB, NP>& F, GetSp&& getsp
         }
         if (kb + 1 < NK) getsp(kb + 1, sp[(kb + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
-        acc = mfma32_x6<NP>(a, b, acc);
+        acc = mfma32_x6<NPT>(a, b, acc);
         next(kb);
         __builtin_amdgcn_sched_barrier(0);   // keep the refills behind their k-block's products
     }
@@ -148,7 +152,7 @@ __device__ __forceinline__ f32x16 load_cm_tile(const float* __restrict__ blk, in
     return x;
 }
 // a chunk-major block's half rows as the B operand (HalfRows: lane half h holds features KH·h ..)
-template <int KH>
+template <int KH, bool F16 = false>
 struct TeamHalf {
     static constexpr int Q = KH / 4;
     float4 raw[Q];
@@ -168,18 +172,18 @@ struct TeamHalf {
         const float4 x = raw[2 * kb];
         const float4 y = 2 * kb + 1 < Q ? raw[2 * kb + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
         const float v[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-        split8(v, sp);
+        split8<F16>(v, sp);
     }
 };
 // B operand from C-layout tiles held in registers (tchain_x6: k-block kb = registers 8(kb&1).. of tile kb>>1)
-template <int NT>
+template <int NT, bool F16 = false>
 struct TeamRegs {
     const f32x16 (&x)[NT];
     __device__ __forceinline__ void operator()(int kb, uint32_t (&sp)[3][4]) const {
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = x[kb >> 1][8 * (kb & 1) + e];
-        split8(v, sp);
+        split8<F16>(v, sp);
     }
 };
 // threadIdx.x & 63, opaque to the compiler: a body inlined into a loop (k_fwd_fused_team) would
@@ -245,8 +249,8 @@ struct TeamRows {
     __device__ __forceinline__ f32x16 load(const float* __restrict__ base, int t) const {
         return load_cm_tile<KH>(base + (KH == kKhE ? oE : oN), t, vl);
     }
-    template <int KH>
-    __device__ __forceinline__ void half(TeamHalf<KH>& hr, const float* __restrict__ base) const {
+    template <int KH, bool F16>
+    __device__ __forceinline__ void half(TeamHalf<KH, F16>& hr, const float* __restrict__ base) const {
         hr.load(base + (KH == kKhE ? oE : oN), vl);
     }
 };
@@ -292,14 +296,15 @@ __device__ __forceinline__ void bias_act_tile(f32x16& x, const float (&bv)[16]) 
 // ------------------------------------------------------------------------------------------------
 // rm encoder (k_enc_edge_x6's chain, Networks.py:75,77): d → relu(rm.0) → 3 × (150×150 + relu) →
 // dropout = c_r → A = c_r·W1a + b1, one 32-edge block per 5-wave workgroup.
-template <bool TRAIN, int NP, bool B16>
+template <bool TRAIN, Np NPT, bool B16>
 __device__ __forceinline__ void enc_edge_team_body(const EncEdgeArgs& a, int blk, uint4* act_s) {
-    const TeamAct<kTeamEdge, NP> act{act_s};
+    constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
+    const TeamAct<kTeamEdge, NPT> act{act_s};
     const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
     const int T = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t e = (int64_t)blk * 32 + j;
     TEAM_STAMP(0);
-    TeamFrags<10, NP> F;
+    TeamFrags<10, NPT> F;
     F.load(a.x_rm1, 5, T, lane);   // layer 1's fragments stream in during layer 0
     const int src = a.esrc[e], dst = a.edst[e];
     float dx = 0.f, dy = 0.f;
@@ -373,10 +378,11 @@ __device__ __forceinline__ void enc_edge_team_body(const EncEdgeArgs& a, int blk
     }
     TEAM_STAMP(10);
 }
-template <bool TRAIN, int NP, bool B16>
+template <bool TRAIN, Np NPT, bool B16>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_enc_edge_team(EncEdgeArgs a) {
+    constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     __shared__ uint4 act_s[2 * kTeamEdge * 2 * NP * 64];   // ≤ 60 KiB
-    enc_edge_team_body<TRAIN, NP, B16>(a, blockIdx.x, act_s);
+    enc_edge_team_body<TRAIN, NPT, B16>(a, blockIdx.x, act_s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -438,13 +444,14 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_enc_edge_bwd_team(EncEdgeBwd
 // om encoder (k_enc_node_x6's chain, Networks.py:76,78): every wave rebuilds the four tiles of
 // z1 = relu(om.0(y, w)) and of P0 (the 'propagation' input) in registers — cheap VALU and loads — so
 // no layer output crosses waves: wave T < 4 owns tile T of c_o, waves 0..4 tile T of U0 and V0.
-template <int NP>
+template <Np NPT>
 __device__ __forceinline__ void enc_node_team_body(const EncNodeArgs& a, const TeamRows& R) {
+    constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int T = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int n = R.n, nc = R.nc;
     const bool valid = R.valid;
-    TeamFrags<7, NP> F;
+    TeamFrags<7, NPT> F;
     if (T < 4) F.load(a.x_om1, 4, T, lane);
     else F.load(a.x_w1b, 5, T, lane);
     if (T < 4) {
@@ -467,7 +474,7 @@ __device__ __forceinline__ void enc_node_team_body(const EncNodeArgs& a, const T
         float bv[16];
         bias_tile(bv, a.b_om1, T, h);
         const uint32_t key = a.dropout_on ? drop_row_key(run_seed(a), 2u, (uint32_t)a.node_tower[nc], (uint32_t)a.node_local[nc], 0xffffu) : 0u;
-        f32x16 C = team_gemm(F, TeamRegs<4>{Z}, [&](int kb) { F.load_kb(a.x_w1b, 5, T, lane, kb); });
+        f32x16 C = team_gemm(F, TeamRegs<4, NPT.f16>{Z}, [&](int kb) { F.load_kb(a.x_w1b, 5, T, lane, kb); });
         bias_act_tile<true>(C, bv);   // relu(om(.)) — Networks.py:76
         if (a.dropout_on) {           // Networks.py:78
 #pragma unroll
@@ -496,43 +503,46 @@ __device__ __forceinline__ void enc_node_team_body(const EncNodeArgs& a, const T
             if (T == t) pt = P[t];
         R.store<kKhN>(a.P0, pt, T);
     }
-    f32x16 U = team_gemm(F, TeamRegs<4>{P}, [&](int kb) { F.load_kb(a.x_w1c, 5, T, lane, kb); });
+    f32x16 U = team_gemm(F, TeamRegs<4, NPT.f16>{P}, [&](int kb) { F.load_kb(a.x_w1c, 5, T, lane, kb); });
     round_uv_tile(U, a.uv16);   // bf16 math (training): rounded as the wide kernels store them (§3ze)
     R.store<kKhE>(a.U0, U, T);
-    U = team_gemm(F, TeamRegs<4>{P}, [&](int) {});
+    U = team_gemm(F, TeamRegs<4, NPT.f16>{P}, [&](int) {});
     round_uv_tile(U, a.uv16);
     R.store<kKhE>(a.V0, U, T);
 }
-template <int NP>
+template <Np NPT>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_enc_node_team(EncNodeArgs a) {
-    enc_node_team_body<NP>(a, TeamRows::block(blockIdx.x, a.n_nodes, threadIdx.x & 63));
+    constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
+    enc_node_team_body<NPT>(a, TeamRows::block(blockIdx.x, a.n_nodes, threadIdx.x & 63));
 }
 // Both encoders of a small batch in ONE launch (they are independent): workgroups [0, n_eblocks) run
 // the relation encoder's blocks, the rest the object encoder's node blocks — one dependent launch and
 // one ramp-up fewer in the replayed step of the reference's batch 32 (the object encoder's ≈ 10 µs
 // run beside the relation encoder's 16 instead of before it).
-template <bool TRAIN, int NP, bool B16>
+template <bool TRAIN, Np NPT, bool B16>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_enc_pair_team(EncEdgeArgs e, EncNodeArgs n) {
+    constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     __shared__ uint4 act_s[2 * kTeamEdge * 2 * NP * 64];
-    if ((int)blockIdx.x < e.n_eblocks) enc_edge_team_body<TRAIN, NP, B16>(e, blockIdx.x, act_s);
-    else enc_node_team_body<NP>(n, TeamRows::block((int)blockIdx.x - e.n_eblocks, n.n_nodes, threadIdx.x & 63));
+    if ((int)blockIdx.x < e.n_eblocks) enc_edge_team_body<TRAIN, NPT, B16>(e, blockIdx.x, act_s);
+    else enc_node_team_body<NPT>(n, TeamRows::block((int)blockIdx.x - e.n_eblocks, n.n_nodes, threadIdx.x & 63));
 }
 
 // ------------------------------------------------------------------------------------------------
 // node side of one step (k_node_fwd_x6's chain, Networks.py:88-96): waves 0..3 own the four node
 // tiles of a, o1, x' and P' (three LDS exchanges), all five waves one tile each of U', V'.
-template <int NP>
+template <Np NPT>
 // h2l (the fused forward): the tile's H2s rows as one chunk-major 32-row block in LDS, rows = R.jl,
 // written by the step's edge side — read instead of the global rows (the same values)
 __device__ __forceinline__ void node_fwd_team_body(const NodeFwdArgs& a, const TeamRows& R, uint4* act_s,
                                                    const float* h2l = nullptr) {
-    const TeamAct<4, NP> act{act_s};
+    constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
+    const TeamAct<4, NPT> act{act_s};
     const int lane = opaque_lane(), h = lane >> 5;
     const int T = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const bool valid = R.valid;
     const bool nw = T < 4;   // node-tile wave
     // one fragment set: W3a's ten k-blocks, refilled k-block by k-block with the 7-k-block layers
-    TeamFrags<10, NP> F;
+    TeamFrags<10, NPT> F;
     const uint4* const first7 = a.cw_in ? a.x_wo1a : a.x_wo1c;
     if (nw) F.load(a.x_w3a, 4, T, lane);
     TEAM_STAMP(0);
@@ -541,7 +551,7 @@ __device__ __forceinline__ void node_fwd_team_body(const NodeFwdArgs& a, const T
         // a = tanh([H2s | deg]·[W3; b3])   (Networks.py:88, layer 3 after the sum)
         f32x16 E;
         {
-            TeamHalf<kKhE> hr;
+            TeamHalf<kKhE, NPT.f16> hr;
             if (h2l) hr.load_lds(h2l, (lane & 32) | R.jl);
             else R.half(hr, a.H2s);
             E = team_gemm(F, hr, [&](int kb) {
@@ -560,7 +570,7 @@ __device__ __forceinline__ void node_fwd_team_body(const NodeFwdArgs& a, const T
         if (a.cw_in) {
             O = R.load<kKhN>(a.cw_in, T);
         } else {
-            TeamHalf<kKhN> hr;
+            TeamHalf<kKhN, NPT.f16> hr;
             R.half(hr, a.co);
             O = team_gemm<7>(F, hr, [&](int kb) { F.load_kb(a.x_wo1a, 4, T, lane, kb); });
             if (a.cw_out) R.store_all<kKhN>(a.cw_out, O, T);
@@ -573,7 +583,7 @@ __device__ __forceinline__ void node_fwd_team_body(const NodeFwdArgs& a, const T
         O = team_gemm<7>(F, [&](int kb, uint32_t (&sp)[3][4]) { act.get(0, kb, sp, lane); },
                       [&](int kb) { F.load_kb(a.x_wo1p, 4, T, lane, kb); }, O);
         {
-            TeamHalf<kKhN> hr;
+            TeamHalf<kKhN, NPT.f16> hr;
             R.half(hr, a.P);
             float bv[16];
             bias_tile(bv, a.bo1, T, h);
@@ -623,10 +633,11 @@ __device__ __forceinline__ void node_fwd_team_body(const NodeFwdArgs& a, const T
     }
 }
 
-template <int NP>
+template <Np NPT>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_node_fwd_team(NodeFwdArgs a) {
+    constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     __shared__ uint4 act_s[2 * 4 * 2 * NP * 64];
-    node_fwd_team_body<NP>(a, TeamRows::block(blockIdx.x, a.n_nodes, threadIdx.x & 63), act_s);
+    node_fwd_team_body<NPT>(a, TeamRows::block(blockIdx.x, a.n_nodes, threadIdx.x & 63), act_s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -780,8 +791,9 @@ __device__ __forceinline__ void team_dh2_kblocks(const float* __restrict__ G3, c
     }
 }
 // acc = Σ_kb A(kb) · W(kb, T) over the ten k-blocks in LDS, in mfma32_x6's product order
-template <int NP>
-__device__ __forceinline__ f32x16 team_lds_gemm(const uint4* buf, const uint4 (&wf)[10][NP], int lane) {
+template <Np NPT>
+__device__ __forceinline__ f32x16 team_lds_gemm(const uint4* buf, const uint4 (&wf)[10][NPT.n], int lane) {
+    constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     f32x16 acc = zero16();
     uint4 cur[3], nxt[3];
 #pragma unroll
@@ -799,7 +811,7 @@ __device__ __forceinline__ f32x16 team_lds_gemm(const uint4* buf, const uint4 (&
             bp[p] = as_bf16x8(p < NP ? wf[kb][p] : make_uint4(0u, 0u, 0u, 0u));
         }
         __builtin_amdgcn_sched_barrier(0);
-        acc = mfma32_x6<NP>(ap, bp, acc);
+        acc = mfma32_x6<NPT>(ap, bp, acc);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int p = 0; p < NP; ++p) cur[p] = nxt[p];
@@ -817,8 +829,9 @@ __device__ __forceinline__ f32x16 team_lds_gemm(const uint4* buf, const uint4 (&
 // the one-hot receiver sum of tile T are k_edge_fwd_x6's (mfma32_x6 / NodeSum16X6), so H2s and both
 // masks are bit-identical. Wave T writes the h2 > 0 word of tile T (wave 0 also the padding words).
 // hs: two buffers of 10 k-blocks × 3 parts × 64 lanes (uint4), 60 KiB, blocks alternate.
-template <int NP, bool AB16>
+template <Np NPT, bool AB16>
 __device__ __forceinline__ void edge_fwd_team_body(const EdgeFwdArgs& a, int wt, uint4* hs, float* h2l = nullptr) {
+    constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     const int lane = opaque_lane(), h = lane >> 5, i = lane & 31;
     const int T = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int4 info = reinterpret_cast<const int4*>(a.wtile)[wt];
@@ -873,7 +886,7 @@ __device__ __forceinline__ void edge_fwd_team_body(const EdgeFwdArgs& a, int wt,
                 if (k == 0) TEAM_STAMP(23);
                 uint32_t sp[3][4];
 #pragma unroll
-                for (int m = 0; m < 4; ++m) split2(xv[2 * m], xv[2 * m + 1], sp[0][m], sp[1][m], sp[2][m]);
+                for (int m = 0; m < 4; ++m) split2<NPT.f16>(xv[2 * m], xv[2 * m + 1], sp[0][m], sp[1][m], sp[2][m]);
 #pragma unroll
                 for (int p = 0; p < NP; ++p) buf[(kb * 3 + p) * 64 + lane] = make_uint4(sp[p][0], sp[p][1], sp[p][2], sp[p][3]);
                 if (k == 0) TEAM_STAMP(24);
@@ -908,7 +921,7 @@ __device__ __forceinline__ void edge_fwd_team_body(const EdgeFwdArgs& a, int wt,
         TEAM_STAMP(17);
         team_sync();   // the block's split h1 (the other buffer is free: every wave passed this barrier)
         TEAM_STAMP(18);
-        f32x16 acc = team_lds_gemm<NP>(buf, wf, lane);
+        f32x16 acc = team_lds_gemm<NPT>(buf, wf, lane);
         TEAM_STAMP(19);
         const uint32_t vh = (uint32_t)vmask >> (4 * h);
 #pragma unroll
@@ -955,12 +968,12 @@ __device__ __forceinline__ void edge_fwd_team_body(const EdgeFwdArgs& a, int wt,
                     const int e = 2 * m + q, base = 8 * (e >> 2) + (e & 3);
 #if SPWGNN_ONEHOT_BPERM
                     const int dn = __builtin_amdgcn_ds_bpermute(4 * (gb + base), ld);
-                    w |= (dn == (lane & 15) ? 0x3F80u : 0u) << (16 * q);
+                    w |= (dn == (lane & 15) ? kOne16<NPT.f16> : 0u) << (16 * q);
 #else
                     const int d0 = __builtin_amdgcn_readlane(d, base), d1 = __builtin_amdgcn_readlane(d, base + 16);
                     const int d2 = __builtin_amdgcn_readlane(d, base + 4), d3 = __builtin_amdgcn_readlane(d, base + 20);
                     const int dn = g == 0 ? d0 : g == 1 ? d1 : g == 2 ? d2 : d3;
-                    w |= (dn == key ? 0x3F80u : 0u) << (16 * q);
+                    w |= (dn == key ? kOne16<NPT.f16> : 0u) << (16 * q);
 #endif
                 }
                 oh[m] = w;
@@ -971,7 +984,7 @@ __device__ __forceinline__ void edge_fwd_team_body(const EdgeFwdArgs& a, int wt,
             for (int sh = 0; sh < 2; ++sh)
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
-                    split2(acc[8 * sh + 2 * m], acc[8 * sh + 2 * m + 1], P[sh][0][m], P[sh][1][m], P[sh][2][m]);
+                    split2<NPT.f16>(acc[8 * sh + 2 * m], acc[8 * sh + 2 * m + 1], P[sh][0][m], P[sh][1][m], P[sh][2][m]);
 #pragma unroll
             for (int p = 0; p < 3; ++p)
 #pragma unroll
@@ -984,8 +997,8 @@ __device__ __forceinline__ void edge_fwd_team_body(const EdgeFwdArgs& a, int wt,
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int p = NP - 1; p >= 0; --p)
-                    nacc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        ao, as_bf16x8(make_uint4(P[u][p][0], P[u][p][1], P[u][p][2], P[u][p][3])), nacc[u], 0, 0, 0);
+                    nacc[u] = mfma16_part<NPT.f16>(
+                        ao, as_bf16x8(make_uint4(P[u][p][0], P[u][p][1], P[u][p][2], P[u][p][3])), nacc[u]);
         }
     }
     TEAM_STAMP(21);
@@ -1010,10 +1023,11 @@ constexpr int kTeamHsU4 = 2 * 10 * 3 * 64;   // edge bodies' split-operand buffe
 // LDS of a launch that runs edge bodies and five-tile exchanges (TeamAct<5>) one after the other
 template <int NP>
 constexpr int kTeamLdsU4 = kTeamHsU4 > 2 * kTeamEdge * 2 * NP * 64 ? kTeamHsU4 : 2 * kTeamEdge * 2 * NP * 64;
-template <int NP, bool AB16>
+template <Np NPT, bool AB16>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_edge_fwd_team(EdgeFwdArgs a) {
+    constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     __shared__ uint4 hs[kTeamHsU4];
-    if ((int)blockIdx.x < a.n_wtiles) edge_fwd_team_body<NP, AB16>(a, blockIdx.x, hs);
+    if ((int)blockIdx.x < a.n_wtiles) edge_fwd_team_body<NPT, AB16>(a, blockIdx.x, hs);
 }
 
 // ---- a small batch's forward step loop in one launch (FwdFusedArgs, kernels.h) ----
@@ -1034,8 +1048,9 @@ __device__ __forceinline__ void opaque(T*& p) {
     asm volatile("" : "+s"(g));
     p = (T*)g;
 }
-template <bool TRAIN, int NP, bool AB16>
+template <bool TRAIN, Np NPT, bool AB16>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_fwd_fused_team(FwdFusedArgs a) {
+    constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     __shared__ uint4 act_s[kTeamLdsU4<NP>];
     __shared__ float h2l[kCmBlk];   // the step's H2s rows of the tile (≤ 16 nodes), edge side → node side
     const int wt = blockIdx.x;
@@ -1043,8 +1058,8 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_fwd_fused_team(FwdFusedArgs 
     const TeamRows R = TeamRows::tile(info.z, info.w, threadIdx.x & 63);
     TEAM_STAMP(10);
     if (a.encoders) {   // else both encoders ran before, side by side (k_enc_pair_team)
-        for (int b = 0; b < info.y; ++b) enc_edge_team_body<TRAIN, NP, AB16>(a.ee, info.x + b, act_s);
-        enc_node_team_body<NP>(a.en, R);
+        for (int b = 0; b < info.y; ++b) enc_edge_team_body<TRAIN, NPT, AB16>(a.ee, info.x + b, act_s);
+        enc_node_team_body<NPT>(a.en, R);
         __syncthreads();   // A, U0, V0 of the tile
     }
     for (int s = 0; s < a.S; ++s) {
@@ -1059,7 +1074,7 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_fwd_fused_team(FwdFusedArgs 
         if (ef.mask1) ef.mask1 += s * a.m1_step;
         if (ef.mask2) ef.mask2 += s * a.m2_step;
         if (s == 0) TEAM_STAMP(11);
-        edge_fwd_team_body<NP, AB16>(ef, wt, act_s, h2l);
+        edge_fwd_team_body<NPT, AB16>(ef, wt, act_s, h2l);
         if (s == 0) TEAM_STAMP(12);
         __syncthreads();   // H2s of step s
         NodeFwdArgs nf = a.nf;
@@ -1085,7 +1100,7 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_fwd_fused_team(FwdFusedArgs 
         nf.U = s + 1 < a.S ? const_cast<float*>(a.ef.U) + sE1 : nullptr;   // the same workspace arrays
         nf.V = s + 1 < a.S ? const_cast<float*>(a.ef.V) + sE1 : nullptr;
         if (s == 0) TEAM_STAMP(13);
-        node_fwd_team_body<NP>(nf, R.opaque(), act_s, h2l);
+        node_fwd_team_body<NPT>(nf, R.opaque(), act_s, h2l);
         if (s == 0) TEAM_STAMP(14);
         __syncthreads();   // P', U', V' of step s + 1
         if (s == 0) TEAM_STAMP(15);
@@ -1426,7 +1441,7 @@ hipError_t launch_edge_fwd_team(const EdgeFwdArgs& a, int math, hipStream_t st) 
         if (a.a_b16) hipLaunchKernelGGL((k_edge_fwd_team<1, true>), g, b, 0, st, a);
         else hipLaunchKernelGGL((k_edge_fwd_team<1, false>), g, b, 0, st, a);
     } else if (math_split32(math) && !a.a_b16) {
-        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_fwd_team<NP, false>), g, b, 0, st, a));
+        SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_edge_fwd_team<NP, false>), g, b, 0, st, a));
     } else {
         return hipErrorInvalidValue;
     }
@@ -1462,8 +1477,8 @@ hipError_t launch_enc_edge_team(const EncEdgeArgs& a, int math, bool train, hipS
         else if (train) hipLaunchKernelGGL((k_enc_edge_team<true, 1, false>), g, b, 0, st, a);
         else hipLaunchKernelGGL((k_enc_edge_team<false, 1, false>), g, b, 0, st, a);
     } else if (math_split32(math)) {
-        if (train) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_edge_team<true, NP, false>), g, b, 0, st, a));
-        else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_edge_team<false, NP, false>), g, b, 0, st, a));
+        if (train) SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_enc_edge_team<true, NP, false>), g, b, 0, st, a));
+        else SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_enc_edge_team<false, NP, false>), g, b, 0, st, a));
     } else {
         return hipErrorInvalidValue;
     }
@@ -1473,7 +1488,7 @@ hipError_t launch_enc_node_team(const EncNodeArgs& a, int math, hipStream_t st) 
     if (a.uv16 == kUvB16) return hipErrorInvalidValue;
     const dim3 g((a.n_nodes + 31) / 32), b(64 * kTeamEdge);
     if (math == MATH_BF16) hipLaunchKernelGGL((k_enc_node_team<1>), g, b, 0, st, a);
-    else if (math_split32(math)) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_node_team<NP>), g, b, 0, st, a));
+    else if (math_split32(math)) SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_enc_node_team<NP>), g, b, 0, st, a));
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -1488,9 +1503,9 @@ hipError_t launch_enc_pair_team(const EncEdgeArgs& e, const EncNodeArgs& n, int 
         else if (train) hipLaunchKernelGGL((k_enc_pair_team<true, 1, false>), g, b, 0, st, e, n);
         else hipLaunchKernelGGL((k_enc_pair_team<false, 1, false>), g, b, 0, st, e, n);
     } else if (train) {
-        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_pair_team<true, NP, false>), g, b, 0, st, e, n));
+        SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_enc_pair_team<true, NP, false>), g, b, 0, st, e, n));
     } else {
-        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_enc_pair_team<false, NP, false>), g, b, 0, st, e, n));
+        SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_enc_pair_team<false, NP, false>), g, b, 0, st, e, n));
     }
     return hipGetLastError();
 }
@@ -1509,8 +1524,8 @@ hipError_t launch_fwd_fused_team(const FwdFusedArgs& a, int math, bool train, hi
         else if (!a.ee.b16) hipLaunchKernelGGL((k_fwd_fused_team<false, 1, false>), g, b, 0, st, a);
         else return hipErrorInvalidValue;
     } else if (math_split32(math) && !a.ee.b16) {
-        if (train) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_fwd_fused_team<true, NP, false>), g, b, 0, st, a));
-        else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_fwd_fused_team<false, NP, false>), g, b, 0, st, a));
+        if (train) SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_fwd_fused_team<true, NP, false>), g, b, 0, st, a));
+        else SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_fwd_fused_team<false, NP, false>), g, b, 0, st, a));
     } else {
         return hipErrorInvalidValue;
     }
@@ -1542,7 +1557,7 @@ hipError_t launch_node_fwd_team(const NodeFwdArgs& a, int math, hipStream_t st) 
     if (a.uv16 == kUvB16) return hipErrorInvalidValue;
     const dim3 g((a.n_nodes + 31) / 32), b(64 * kTeamEdge);
     if (math == MATH_BF16) hipLaunchKernelGGL((k_node_fwd_team<1>), g, b, 0, st, a);
-    else if (math_split32(math)) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_node_fwd_team<NP>), g, b, 0, st, a));
+    else if (math_split32(math)) SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_node_fwd_team<NP>), g, b, 0, st, a));
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -29,7 +29,8 @@ def _require_gpu(t: torch.Tensor, what: str):
         raise _lib.SpwgnnError(f"{what} must be a HIP device tensor (got {t.device}); the HIP path has no CPU fallback")
 
 
-MATH_MODES = {"f32": _lib.MATH_F32, "x6": _lib.MATH_X6, "bf16": _lib.MATH_BF16, "x3": _lib.MATH_X3}
+MATH_MODES = {"f32": _lib.MATH_F32, "x6": _lib.MATH_X6, "bf16": _lib.MATH_BF16, "x3": _lib.MATH_X3,
+              "h3": _lib.MATH_H3}
 
 
 # Replayed steps fold their batch upload and key/step advance into the forward's first launch
@@ -44,7 +45,8 @@ class RunConfig:
     dropout: float = 0.0
     seed: int = 0
     math: str = "x6"                     # "x6" 3-part split-bf16 products (fp32-class, the parity path) | "f32" f32 MFMA |
-                                         # "x3" 2-part split, 3 products (16-bit operand mantissa) | "bf16" (spwgnn.h)
+                                         # "x3" 2-part split, 3 products (16-bit operand mantissa) | "bf16" |
+                                         # "h3" forward on 2 fp16 parts, 3 products (fp32-class), backward x6 (spwgnn.h)
     prof_kernel: int = 0                 # SPWGNN_K_* to bracket with HIP events (bench only)
     prof_events: Optional[list] = None   # raw hipEvent_t handles, 2 per launch
     seed_dev: Optional[torch.Tensor] = None   # (1,) int64 device word holding the dropout key (replayable steps)

@@ -55,7 +55,7 @@ class GraphNetwork(nn.Module):
 
     ``mp_steps`` defaults to the reference's 5 (Networks.py:83); ``dropout`` to its 0.1 on the
     two encodings (Networks.py:77-78), active only in training mode. ``math`` ("x6" by default, the
-    fp32-class parity path; "x3", "bf16", "f32": `engine.MATH_MODES`) is the arithmetic of the matrix
+    fp32-class parity path; "h3", "x3", "bf16", "f32": `engine.MATH_MODES`) is the arithmetic of the matrix
     products in training, inference and `forward_pooled`.
     """
 

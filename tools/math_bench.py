@@ -1,12 +1,17 @@
 #!/usr/bin/env python
-"""Time the `Trainer` step in x6, x3 and bf16 math on one box, in one process, alternating.
+"""Time the `Trainer` step in x6, x3, h3 and bf16 math on one box, in one process, alternating.
 
 Two shapes: the headline (65,536 fully connected six-box towers, S = 5, dropout 0.1: bench.py config 0)
-and the reference's batch of 32 such towers. Per shape the maths run in rounds (x6, x3, bf16, x6, x3,
-bf16, ...; at least three), each entry `--steps` back-to-back steps between two device events, so a
-drift of the box shows as a spread inside every math instead of as a gap between maths. x3 counts as
-faster than x6 only if every x3 round beats every x6 round. For x6 and x3 the launches of every
-library kernel are then timed through the `prof_kernel` hook (spwgnn_run.prof_kernel), summed per step.
+and the reference's batch of 32 such towers. Per shape the maths run in rounds (x6, x3, h3, bf16, x6,
+x3, h3, bf16, ...; at least three), each entry `--steps` back-to-back steps between two device events,
+so a drift of the box shows as a spread inside every math instead of as a gap between maths. A math
+counts as faster than x6 only if every one of its rounds beats every x6 round by more than x6's own
+spread. For x6, x3 and h3 the launches of every library kernel are then timed through the `prof_kernel`
+hook (spwgnn_run.prof_kernel), summed per step.
+
+Forward only (inference, `engine.forward` with training=False; "forward" in the JSON): the same
+alternation at the headline shape and at a config-5-like shape (towers of 32 boxes, S = 10, fully
+connected: a receiver-block plan), x6 / x3 / h3 — h3's backward is x6's, so this is where it differs.
 
 Writes one JSON with every round's numbers (not only the best):
 
@@ -25,7 +30,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from spwgnn_amd import TowerBatch, _lib, data as D, engine as E, params as P  # noqa: E402
 from spwgnn_amd.trainer import Trainer  # noqa: E402
 
-MATHS = ("x6", "x3", "bf16")
+MATHS = ("x6", "x3", "h3", "bf16")
+FWD_MATHS = ("x6", "x3", "h3")
+FWD_KERNELS = ("enc_edge", "enc_node", "edge_fwd", "node_fwd")
 KERNELS = {"enc_edge": _lib.K_ENC_EDGE, "enc_node": _lib.K_ENC_NODE, "edge_fwd": _lib.K_EDGE_FWD,
            "node_fwd": _lib.K_NODE_FWD, "node_bwd": _lib.K_NODE_BWD, "edge_bwd": _lib.K_EDGE_BWD, "dA": _lib.K_DA,
            "enc_edge_bwd": _lib.K_ENC_EDGE_BWD, "enc_node_bwd": _lib.K_ENC_NODE_BWD, "wgrad_w2": _lib.K_WGRAD_W2,
@@ -91,6 +98,59 @@ def kernel_table(trainer, batch, tgt, steps):
     return table
 
 
+def forward_ms(flat, batch, run, ws, z, steps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(steps):
+        E.forward(flat, batch, run, ws, logits=z)
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def forward_kernel_table(flat, batch, S, math, ws, z, steps):
+    table = {}
+    for name in FWD_KERNELS:
+        ev = HipEvents(2 * 2 * SLOTS * steps)
+        per = 2 * 2 * SLOTS
+        for k in range(steps):
+            run = E.RunConfig(S, training=False, math=math, prof_kernel=KERNELS[name], prof_events=ev.ev[per * k: per * (k + 1)])
+            E.forward(flat, batch, run, ws, logits=z)
+        torch.cuda.synchronize()
+        ms = ev.recorded_ms()
+        ev.close()
+        if ms:
+            table[name] = {"ms_per_forward": round(sum(ms) / steps, 4), "launches_per_forward": len(ms) / steps}
+    return table
+
+
+def run_forward_shape(name, towers, nodes, S, args, dev):
+    """Inference forwards of one batch, x6 / x3 / h3 alternating; every round's ms per forward."""
+    raw = D.synthetic_towers_fast(towers, nodes, seed=1000 + 97 * nodes)
+    kw = {"nw_max": 16} if nodes <= 16 else {}
+    batch = TowerBatch.fully_connected((raw / D.RELATION_THRESHOLD).astype(np.float32), device=dev, **kw)
+    flat = P.to_flat(P.glorot_uniform(0), device=dev)
+    z = torch.empty(batch.n_nodes, dtype=torch.float32, device=dev)
+    runs = {m: E.RunConfig(S, training=False, math=m) for m in FWD_MATHS}
+    wss = {m: E.Workspace(dev) for m in FWD_MATHS}
+    for m in FWD_MATHS:
+        for _ in range(args.warmup):
+            E.forward(flat, batch, runs[m], wss[m], logits=z)
+    rounds = []
+    for _ in range(args.rounds):
+        rounds.append({m: round(forward_ms(flat, batch, runs[m], wss[m], z, args.steps), 4) for m in FWD_MATHS})
+        print(name, "forward", rounds[-1], flush=True)
+    ms = {m: [r[m] for r in rounds] for m in FWD_MATHS}
+    spread = max(ms["x6"]) - min(ms["x6"])
+    return {"towers": towers, "nodes_per_tower": nodes, "mp_steps": S, "n_nodes": batch.n_nodes, "n_eblocks": batch.n_eblocks,
+            "recv_blocks": bool(batch.flags & 1), "forwards_per_round_entry": args.steps, "rounds": rounds,
+            "min_ms": {m: min(ms[m]) for m in FWD_MATHS}, "max_ms": {m: max(ms[m]) for m in FWD_MATHS},
+            "x6_spread_ms": round(spread, 4),
+            "h3_faster_than_x6_every_round_by_more_than_x6_spread": max(ms["h3"]) + spread < min(ms["x6"]),
+            "kernels": {m: forward_kernel_table(flat, batch, S, m, wss[m], z, args.kernel_steps) for m in FWD_MATHS}}
+
+
 def run_shape(name, towers, args, dev):
     raw = D.synthetic_towers_fast(towers, 6, seed=1000 + 97 * 6)   # bench.py's towers
     batch = TowerBatch.fully_connected((raw / D.RELATION_THRESHOLD).astype(np.float32), device=dev, nw_max=16)
@@ -111,8 +171,9 @@ def run_shape(name, towers, args, dev):
            "min_ms": {m: min(ms[m]) for m in MATHS}, "max_ms": {m: max(ms[m]) for m in MATHS},
            "x6_spread_ms": round(max(ms["x6"]) - min(ms["x6"]), 4),
            "x3_faster_than_x6_every_round": max(ms["x3"]) < min(ms["x6"]),
+           "h3_faster_than_x6_every_round": max(ms["h3"]) < min(ms["x6"]),
            "fused_path": {m: E.fused_path(batch, trainers[m].run_config()) for m in MATHS},
-           "kernels": {m: kernel_table(trainers[m], batch, tgt, args.kernel_steps) for m in ("x6", "x3")}}
+           "kernels": {m: kernel_table(trainers[m], batch, tgt, args.kernel_steps) for m in ("x6", "x3", "h3")}}
     return res
 
 
@@ -124,6 +185,7 @@ def main():
     ap.add_argument("--kernel-steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--towers", type=int, default=65536)
+    ap.add_argument("--towers32", type=int, default=2048, help="towers of the 32-box forward-only shape (config 5: 8192)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None, choices=MATHS,
                     help="no timing: three headline steps in this math alone (the program of a "
@@ -143,8 +205,11 @@ def main():
         return
     res = {"tool": "math_bench", "device": torch.cuda.get_device_name(0),
            "mfma_products_per_fp32_product": {m: int(_lib.lib().spwgnn_math_products(E.MATH_MODES[m])) for m in MATHS},
+           "mfma_products_per_fp32_product_bwd": {m: int(_lib.lib().spwgnn_math_products_bwd(E.MATH_MODES[m])) for m in MATHS},
            "shapes": {"headline": run_shape("headline", args.towers, args, dev),
-                      "batch32": run_shape("batch32", 32, args, dev)}}
+                      "batch32": run_shape("batch32", 32, args, dev)},
+           "forward": {"headline": run_forward_shape("headline", args.towers, 6, 5, args, dev),
+                       "n32_s10_recv": run_forward_shape("n32_s10_recv", args.towers32, 32, 10, args, dev)}}
     line = json.dumps(res, indent=1)
     print(line)
     if args.out:
