@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense; spwgnn_clip, spwgnn_adam_clipped, spwgnn_adam_clipped_dev, spwgnn_adam_lr_decayed, spwgnn_adam_lr_table_decay); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
@@ -48,7 +48,7 @@ typedef struct spwgnn_param_info {
 int32_t spwgnn_version(void);
 /* sizeof the ABI structs as this library was compiled (bindings check their own layouts against it):
  * which = 0 spwgnn_batch, 1 spwgnn_run, 2 spwgnn_plan_sizes, 3 spwgnn_param_info,
- * 4 spwgnn_loss_weights, 6 spwgnn_plan_device; -1 otherwise (5 is not used and stays -1). */
+ * 4 spwgnn_loss_weights, 6 spwgnn_plan_device, 7 spwgnn_clip; -1 otherwise (5 is not used and stays -1). */
 int32_t spwgnn_struct_size(int32_t which);
 const char* spwgnn_strerror(int32_t status);
 int32_t spwgnn_param_tensor_count(void);
@@ -473,6 +473,61 @@ int32_t spwgnn_adam_lr_table(float lr, float beta1, float beta2, int32_t n, floa
 int32_t spwgnn_adam_dev(float* params, const float* grads, float* m, float* v, int64_t n, const int32_t* step_dev,
                         const float* lr_table, int32_t table_len, float beta1, float beta2, float eps, float l2,
                         float grad_scale, spwgnn_stream_t stream);
+
+/* clipnorm, clipvalue, decay and a non-finite guard for the Adam step (added within ABI 8: new symbols
+ * only; spwgnn_adam and spwgnn_adam_dev are unchanged). Keras 2.x Optimizer.get_gradients plus Adam's
+ * `decay` (Networks.py:101 spells decay=0.0 out), restated — unpinned like the rest:
+ *   g'   = grad_scale*grad + 2*l2*param                     (what spwgnn_adam forms; Keras's L2 is in its loss)
+ *   norm = sqrt(Σ g'^2) over the REAL parameters: the ranges of spwgnn_param_tensor. The 64-float
+ *          alignment padding between tensors is neither summed nor checked, whatever it holds.
+ *   clipnorm  c > 0 and norm >= c:  g' *= c / norm; otherwise the applied scale is exactly 1.0f
+ *   clipvalue v > 0:                g'  = clamp(g', -v, v), after clipnorm (a NaN stays a NaN)
+ *   m, v, p  updated from that g' with spwgnn_adam's expressions.
+ *   skip_nonfinite (not in Keras): when the computed Σ g'^2 is NaN or inf — a non-finite gradient, or a
+ *          sum that overflows fp32 (|g'| above ~1.8e19 does) — the step writes nothing to params, m
+ *          or v. The step COUNT is not held back: a replayed step advances its device step word in
+ *          the forward's first launch, before the gradient exists, and the host mirror cannot learn
+ *          of a skip without a sync; so a skipped step still uses up iteration t (bias correction and
+ *          decay move on). Without the flag non-finite values propagate as in Keras.
+ * `grads` is never modified. Two launches, one more than spwgnn_adam: 64 fixed blocks write partial
+ * sums of Σ g'^2 (a per-thread strided sum of 13 terms, then a 256-wide tree; no atomics), and
+ * every block of the update adds the 64 partials in the same order in double — the same bits in every
+ * block, on every run and every device — before it applies the scale. Capturable.
+ * out4 (device, required) = {norm, applied scale, skipped 0/1, clipped by norm 0/1 (0 on a skipped step)}.
+ * total4 (device fp64, optional): += {norm if not skipped, clipped, skipped, 1} in the same launch, as
+ * spwgnn_bce_accumulate does for the loss (model.fit's per-epoch sums without a host sync). */
+typedef struct spwgnn_clip {
+    float clipnorm;          /* c >= 0; 0 = off                                              */
+    float clipvalue;         /* v >= 0; 0 = off                                              */
+    int32_t skip_nonfinite;  /* 1: a step with a non-finite Σ g'^2 leaves params, m, v alone */
+    int32_t reserved;        /* 0                                                            */
+    float* out4;             /* device, 4 floats                                             */
+    double* total4;          /* device, 4 doubles; NULL = none                               */
+} spwgnn_clip;
+/* Device bytes of the partial sums (`scratch` below; 4-byte aligned). */
+int64_t spwgnn_clip_scratch_bytes(void);
+/* spwgnn_adam's arguments plus the options and the scratch. SPWGNN_E_ARG before any launch: a null
+ * pointer (clip, clip->out4 and scratch included), n != spwgnn_param_count() (the real ranges are the
+ * library's own table), step < 1, a negative or NaN clipnorm / clipvalue. `lr` is the step's own: a
+ * decayed one comes from spwgnn_adam_lr_decayed. */
+int32_t spwgnn_adam_clipped(float* params, const float* grads, float* m, float* v, int64_t n, int32_t step,
+                            float lr, float beta1, float beta2, float eps, float l2, float grad_scale,
+                            const spwgnn_clip* clip, void* scratch, spwgnn_stream_t stream);
+/* The same with spwgnn_adam_dev's step word and lr table (also E_ARG: step_dev / lr_table NULL,
+ * table_len < 2). With decay the table is spwgnn_adam_lr_table_decay's. */
+int32_t spwgnn_adam_clipped_dev(float* params, const float* grads, float* m, float* v, int64_t n,
+                                const int32_t* step_dev, const float* lr_table, int32_t table_len, float beta1,
+                                float beta2, float eps, float l2, float grad_scale, const spwgnn_clip* clip,
+                                void* scratch, spwgnn_stream_t stream);
+/* Keras 2.x Adam's decay (host): lr_eff = lr * 1/(1 + decay*iterations), evaluated in double and
+ * rounded to fp32 once; iterations = the steps already taken (0 at the first step, t - 1 at step t).
+ * decay <= 0 (or NaN) or iterations <= 0 returns lr itself. */
+float spwgnn_adam_lr_decayed(float lr, float decay, int64_t iterations);
+/* spwgnn_adam_lr_table with entry t built from spwgnn_adam_lr_decayed(lr, decay, t - 1): an eager step
+ * that passes that lr to spwgnn_adam(_clipped) and a replayed one agree bit for bit; decay = 0 gives
+ * spwgnn_adam_lr_table's bits. The device clamps the step at the table's last entry, so the decay
+ * FREEZES there (the Python layer's tables hold 2^20 steps). SPWGNN_E_ARG also for decay < 0 or NaN. */
+int32_t spwgnn_adam_lr_table_decay(float lr, float decay, float beta1, float beta2, int32_t n, float* out_host);
 
 /* Epoch sums of model.fit's progress line (main.py:92-98): total3[k] += (double)out3[k] * weights3[k]
  * for k < 3 (out3 = spwgnn_bce's [loss, correct, n]; weights (n, 1, 1) make Σ loss·n) — one launch,

@@ -66,6 +66,12 @@ class PlanDeviceC(C.Structure):
                 ("prof_events", C.c_void_p)]
 
 
+class ClipC(C.Structure):
+    """spwgnn_clip: the options and outputs of a clipped / guarded Adam step (added within ABI 8)."""
+    _fields_ = [("clipnorm", C.c_float), ("clipvalue", C.c_float), ("skip_nonfinite", C.c_int32),
+                ("reserved", C.c_int32), ("out4", C.c_void_p), ("total4", C.c_void_p)]
+
+
 K_EDGE_FWD, K_NODE_FWD, K_EDGE_BWD, K_NODE_BWD, K_ENC_EDGE, K_ENC_EDGE_BWD, K_WGRAD_W2, K_DA = 1, 2, 3, 4, 5, 6, 7, 8
 K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD, K_INPUT_BWD, K_PLAN_DEVICE, K_STATE = 9, 10, 11, 12, 13, 14
 MATH_F32, MATH_X6, MATH_BF16, MATH_X3, MATH_H3 = 0, 1, 2, 3, 4
@@ -119,6 +125,12 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_adam": (i32, [vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, f32, f32, vp]),
         "spwgnn_adam_dev": (i32, [vp, vp, vp, vp, i64, vp, vp, i32, f32, f32, f32, f32, f32, vp]),
         "spwgnn_adam_lr_table": (i32, [f32, f32, f32, i32, vp]),
+        "spwgnn_clip_scratch_bytes": (i64, []),
+        "spwgnn_adam_clipped": (i32, [vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, f32, f32, C.POINTER(ClipC), vp, vp]),
+        "spwgnn_adam_clipped_dev": (i32, [vp, vp, vp, vp, i64, vp, vp, i32, f32, f32, f32, f32, f32, C.POINTER(ClipC),
+                                          vp, vp]),
+        "spwgnn_adam_lr_decayed": (f32, [f32, f32, i64]),
+        "spwgnn_adam_lr_table_decay": (i32, [f32, f32, f32, f32, i32, vp]),
         "spwgnn_step_advance": (i32, [vp, vp, i32, C.c_uint64, i32, vp]),
         "spwgnn_sigmoid": (i32, [vp, vp, i64, vp]),
         "spwgnn_copy_in": (i32, [vp, vp, i64, vp]),
@@ -144,7 +156,8 @@ def lib() -> C.CDLL:
         if lib_.spwgnn_version() != ABI_VERSION:
             raise SpwgnnError(f"{path} implements ABI {lib_.spwgnn_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild with `python -m spwgnn_amd.build`")
-        for which, st in ((0, BatchC), (1, RunC), (2, PlanSizes), (3, ParamInfo), (4, LossWeightsC), (6, PlanDeviceC)):
+        for which, st in ((0, BatchC), (1, RunC), (2, PlanSizes), (3, ParamInfo), (4, LossWeightsC), (6, PlanDeviceC),
+                          (7, ClipC)):
             if lib_.spwgnn_struct_size(which) != C.sizeof(st):
                 raise SpwgnnError(f"{path} was built with a different {st.__name__} layout "
                                   f"({lib_.spwgnn_struct_size(which)} vs {C.sizeof(st)} bytes): rebuild it")

@@ -1717,6 +1717,76 @@ int32_t spwgnn_adam(float* params, const float* grads, float* m, float* v, int64
     return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
 }
 
+// ---- clipnorm / clipvalue / decay / the non-finite guard ----
+float spwgnn_adam_lr_decayed(float lr, float decay, int64_t iterations) {
+    if (!(decay > 0.f) || iterations <= 0) return lr;
+    return (float)((double)lr * (1.0 / (1.0 + (double)decay * (double)iterations)));
+}
+
+int32_t spwgnn_adam_lr_table_decay(float lr, float decay, float beta1, float beta2, int32_t n, float* out) {
+    if (!out || n < 2 || !(decay >= 0.f)) return SPWGNN_E_ARG;
+    out[0] = 0.f;   // step 0 never runs (steps count from 1)
+    for (int32_t t = 1; t < n; ++t)
+        out[t] = adam_lr_t(spwgnn_adam_lr_decayed(lr, decay, (int64_t)t - 1), beta1, beta2, (double)t);
+    return SPWGNN_OK;
+}
+
+int64_t spwgnn_clip_scratch_bytes(void) { return (int64_t)kClipBlocks * (int64_t)sizeof(float); }
+
+// the checks both entry points share and the arguments they have in common; nothing is launched on an error
+static int32_t clip_args(ClipArgs& c, float* params, const float* grads, float* m, float* v, int64_t n, float beta1,
+                         float beta2, float eps, float l2, float grad_scale, const spwgnn_clip* clip, void* scratch) {
+    if (!params || !grads || !m || !v || !clip || !scratch || !clip->out4) return SPWGNN_E_ARG;
+    const ParamTable& pt = param_table();
+    if (n != pt.total) return SPWGNN_E_ARG;
+    if (!(clip->clipnorm >= 0.f) || !(clip->clipvalue >= 0.f)) return SPWGNN_E_ARG;   // negative or NaN
+    c = ClipArgs{};
+    c.a.p = params;
+    c.a.g = grads;
+    c.a.m = m;
+    c.a.v = v;
+    c.a.n = n;
+    c.a.b1 = beta1;
+    c.a.b2 = beta2;
+    c.a.eps = eps;
+    c.a.l2 = l2;
+    c.a.gscale = grad_scale;
+    if (pt.total > (int64_t)kClipRounds * kClipBlocks * 256) return SPWGNN_E_SHAPE;   // k_grad_sumsq's rounds
+    for (int t = 0; t < kNumTensors; ++t) c.end[t] = (int32_t)(pt.t[t].offset + (int64_t)pt.t[t].rows * pt.t[t].cols);
+    c.partial = static_cast<float*>(scratch);
+    c.clipnorm = clip->clipnorm;
+    c.clipvalue = clip->clipvalue;
+    c.skip_nonfinite = clip->skip_nonfinite ? 1 : 0;
+    c.out4 = clip->out4;
+    c.tot4 = clip->total4;
+    return SPWGNN_OK;
+}
+
+int32_t spwgnn_adam_clipped(float* params, const float* grads, float* m, float* v, int64_t n, int32_t step, float lr,
+                            float beta1, float beta2, float eps, float l2, float grad_scale, const spwgnn_clip* clip,
+                            void* scratch, spwgnn_stream_t stream) {
+    if (step < 1) return SPWGNN_E_ARG;
+    ClipArgs c;
+    if (int32_t st = clip_args(c, params, grads, m, v, n, beta1, beta2, eps, l2, grad_scale, clip, scratch)) return st;
+    c.a.lr_t = adam_lr_t(lr, beta1, beta2, (double)step);
+    hipError_t e = launch_adam_clipped(c, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+}
+
+int32_t spwgnn_adam_clipped_dev(float* params, const float* grads, float* m, float* v, int64_t n,
+                                const int32_t* step_dev, const float* lr_table, int32_t table_len, float beta1,
+                                float beta2, float eps, float l2, float grad_scale, const spwgnn_clip* clip,
+                                void* scratch, spwgnn_stream_t stream) {
+    if (!step_dev || !lr_table || table_len < 2) return SPWGNN_E_ARG;
+    ClipArgs c;
+    if (int32_t st = clip_args(c, params, grads, m, v, n, beta1, beta2, eps, l2, grad_scale, clip, scratch)) return st;
+    c.a.step_dev = step_dev;
+    c.a.lr_table = lr_table;
+    c.a.table_len = table_len;
+    hipError_t e = launch_adam_clipped(c, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+}
+
 int32_t spwgnn_accumulate_out3(const float* out3, const double* weights3, double* total3, spwgnn_stream_t stream) {
     if (!out3 || !weights3 || !total3) return SPWGNN_E_ARG;
     hipError_t e = launch_accumulate_out3(out3, weights3, total3, static_cast<hipStream_t>(stream));

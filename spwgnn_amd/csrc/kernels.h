@@ -428,6 +428,22 @@ struct AdamArgs {
     const float* lr_table;
     int32_t table_len;
 };
+// spwgnn_adam_clipped: k_grad_sumsq then k_adam_clipped (kernels_misc.hip). The grid of
+// the partial sums is fixed — the same blocks, shares and order on every device — and small enough that
+// every block of the update re-adds the partials itself.
+constexpr int kClipBlocks = 64;
+constexpr int kClipRounds = 13;   // flat elements per thread: the padded buffer holds <= 13·64·256 = 212,992 floats (210,240)
+struct ClipArgs {
+    AdamArgs a;
+    int32_t end[kNumTensors];   // offset + rows·cols of each tensor (spwgnn_param_tensor): from there to the next
+                                // 64-float boundary lies alignment padding, which is neither summed nor checked
+    float* partial;             // [kClipBlocks] Σg'² per block of k_grad_sumsq
+    float clipnorm, clipvalue;  // 0 = off
+    int32_t skip_nonfinite;
+    float* out4;                // [norm, scale, skipped, clipped]
+    double* tot4;               // NULL, or += [norm if not skipped, clipped, skipped, 1]
+};
+hipError_t launch_adam_clipped(const ClipArgs& c, hipStream_t st);
 
 // Host launchers (defined next to their kernels; each returns hipGetLastError()).
 // packs and (x: non-null) the x6 images in one launch

@@ -1839,6 +1839,97 @@ __global__ void k_adam(AdamArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Keras 2.x Optimizer.get_gradients (clipnorm, then clipvalue) and a non-finite guard in front of
+// k_adam's update (spwgnn_adam_clipped). Two launches: the partial sums of Σg'², then
+// the update, whose every block re-adds the partials in the same order and so derives the same scale
+// and the same skip decision. k_adam itself is untouched: a step without these options runs it as before.
+
+// Block `blockIdx.x` of kClipBlocks: Σg'² over its share of the REAL parameters, g' = gscale·g + 2·l2·p
+// as k_adam forms it. Round k < kClipRounds, thread (b, t) takes flat element b·256 + t + k·16,384: all
+// kClipRounds loads of g and of p go out first (they depend on nothing), then at most 13 squares are
+// added in a row, then bce_block's LDS tree (8 levels). No atomics: the same bits on every run and device.
+// Which elements are real is decided per WAVE with scalar code: tensors start on 64-float boundaries,
+// so the 64 consecutive elements a wave covers in a round lie in one tensor's extent, and they are real
+// up to that tensor's end c.end[t] if it falls inside the chunk, else all of them. An element that is
+// off (padding, or past n) reads element 0 instead and adds a selected 0.f: whatever the padding holds
+// stays out. (A loop of its own per tensor made 22 dependent round trips to memory: 12 µs)
+__global__ __launch_bounds__(256) void k_grad_sumsq(ClipArgs c) {
+    __shared__ float ss[256];
+    const AdamArgs& a = c.a;
+    const int i0 = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    float gv[kClipRounds], pv[kClipRounds];
+    bool on[kClipRounds];
+#pragma unroll
+    for (int k = 0; k < kClipRounds; ++k) {
+        const int i = i0 + k * kClipBlocks * 256;
+        const int cb = __builtin_amdgcn_readfirstlane(i);   // lane 0's element: the wave's 64-aligned chunk
+        int limit = min(cb + 64, (int)a.n);
+#pragma unroll
+        for (int t = 0; t < kNumTensors; ++t) limit = (c.end[t] > cb && c.end[t] < limit) ? c.end[t] : limit;
+        on[k] = i < limit;
+        const int j = on[k] ? i : 0;
+        gv[k] = a.g[j];
+        pv[k] = a.p[j];
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < kClipRounds; ++k) {
+        const float gp = a.gscale * gv[k] + 2.f * a.l2 * pv[k];
+        s += on[k] ? gp * gp : 0.f;
+    }
+    ss[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) ss[threadIdx.x] += ss[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) c.partial[blockIdx.x] = ss[0];
+}
+
+// k_adam's update on g' · scale, clamped to ±clipvalue. Reads the partials, g, the step word and the lr
+// table; writes p, m, v (elementwise, each by its own thread) and — block 0, thread 0 — out4 / tot4:
+// nothing a block reads is written by another block of this launch.
+__global__ __launch_bounds__(256) void k_adam_clipped(ClipArgs c) {
+    __shared__ float sh[2];   // scale, skip
+    AdamArgs a = c.a;
+    if (threadIdx.x == 0) {
+        double sum = 0.0;
+        for (int b = 0; b < kClipBlocks; ++b) sum += (double)c.partial[b];
+        const float sumsq = (float)sum;   // inf where the fp32 sum overflows: that counts as not finite
+        const float norm = sqrtf(sumsq);
+        const bool finite = fabsf(sumsq) <= 3.402823466e38f;   // false for NaN and ±inf
+        const bool skip = c.skip_nonfinite && !finite;
+        const bool clip = c.clipnorm > 0.f && norm >= c.clipnorm;   // false for a NaN norm, as in Keras
+        const float scale = clip ? c.clipnorm / norm : 1.0f;
+        sh[0] = scale;
+        sh[1] = skip ? 1.f : 0.f;
+        if (blockIdx.x == 0) {
+            const float o[4] = {norm, scale, skip ? 1.f : 0.f, (clip && !skip) ? 1.f : 0.f};
+            const double t4[4] = {skip ? 0.0 : (double)norm, (double)o[3], (double)o[2], 1.0};
+            for (int k = 0; k < 4; ++k) {
+                c.out4[k] = o[k];
+                if (c.tot4) c.tot4[k] += t4[k];
+            }
+        }
+    }
+    __syncthreads();
+    if (sh[1] != 0.f) return;   // skipped: p, m and v keep their bits
+    const float scale = sh[0], cv = c.clipvalue;
+    if (a.step_dev) a.lr_t = a.lr_table[min(max(*a.step_dev, 0), a.table_len - 1)];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float p = a.p[i];
+        const float g0 = a.gscale * a.g[i] + 2.f * a.l2 * p;
+        float g = g0 * scale;   // scale == 1.0f: exact, k_adam's g
+        if (cv > 0.f) g = g > cv ? cv : (g < -cv ? -cv : g);   // selects: a NaN stays a NaN, as in Keras
+        const float m = a.b1 * a.m[i] + (1.f - a.b1) * g;
+        const float v = a.b2 * a.v[i] + (1.f - a.b2) * g * g;
+        a.m[i] = m;
+        a.v[i] = v;
+        a.p[i] = p - a.lr_t * m / (sqrtf(v) + a.eps);
+    }
+}
+
 // Start of a replayable training step (one thread, device_common.h step_advance_dev).
 __global__ void k_step_advance(uint64_t* key, int32_t* step, int mode, uint64_t seed, int32_t rank) {
     if (threadIdx.x == 0) step_advance_dev(key, step, mode, seed, rank);
@@ -2227,6 +2318,12 @@ hipError_t launch_bce(const BceArgs& a, hipStream_t st) {
 hipError_t launch_adam(const AdamArgs& a, hipStream_t st) {
     const int64_t blocks = std::min<int64_t>((a.n + 255) / 256, 2048);
     hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_adam_clipped(const ClipArgs& c, hipStream_t st) {
+    hipLaunchKernelGGL(k_grad_sumsq, dim3(kClipBlocks), dim3(256), 0, st, c);
+    const int64_t blocks = std::min<int64_t>((c.a.n + 255) / 256, 2048);   // k_adam's grid
+    hipLaunchKernelGGL(k_adam_clipped, dim3((unsigned)blocks), dim3(256), 0, st, c);
     return hipGetLastError();
 }
 hipError_t launch_step_advance(uint64_t* key, int32_t* step, int mode, uint64_t seed, int32_t rank, hipStream_t st) {

@@ -489,12 +489,91 @@ def adam_dev(params: torch.Tensor, grads: torch.Tensor, m: torch.Tensor, v: torc
     _lib.check(st, "spwgnn_adam_dev")
 
 
-def adam_lr_table(n: int, lr=5e-4, beta1=0.9, beta2=0.999, device="cuda") -> torch.Tensor:
-    """lr_t of steps 0..n-1 (host-built with spwgnn_adam's own expression), on the device."""
+def adam_lr_table(n: int, lr=5e-4, beta1=0.9, beta2=0.999, device="cuda", decay=0.0) -> torch.Tensor:
+    """lr_t of steps 0..n-1 (host-built with spwgnn_adam's own expression), on the device. `decay`
+    (Keras 2.x Adam's): entry t is built from lr / (1 + decay·(t − 1)) (spwgnn_adam_lr_table_decay); a
+    replayed step past the table's last entry keeps that entry, so the decay freezes there."""
     import numpy as np
     out = np.zeros(int(n), np.float32)
-    _lib.check(_lib.lib().spwgnn_adam_lr_table(lr, beta1, beta2, int(n), out.ctypes.data), "spwgnn_adam_lr_table")
+    if decay:
+        _lib.check(_lib.lib().spwgnn_adam_lr_table_decay(lr, decay, beta1, beta2, int(n), out.ctypes.data),
+                   "spwgnn_adam_lr_table_decay")
+    else:
+        _lib.check(_lib.lib().spwgnn_adam_lr_table(lr, beta1, beta2, int(n), out.ctypes.data), "spwgnn_adam_lr_table")
     return torch.from_numpy(out).to(device)
+
+
+def adam_lr_decayed(lr: float, decay: float, iterations: int) -> float:
+    """Keras 2.x Adam's decayed learning rate lr / (1 + decay·iterations) as the library rounds it to
+    fp32 (spwgnn_adam_lr_decayed); `iterations` = the steps already taken, 0 at the first."""
+    return float(_lib.lib().spwgnn_adam_lr_decayed(lr, decay, int(iterations)))
+
+
+def check_clip_options(clipnorm=0.0, clipvalue=0.0, decay=0.0) -> bool:
+    """Validates the optimizer options of the front ends (each >= 0 and not NaN; 0 = off). Returns
+    whether clipnorm or clipvalue is set."""
+    for name, val in (("clipnorm", clipnorm), ("clipvalue", clipvalue), ("decay", decay)):
+        if not float(val) >= 0.0:
+            raise ValueError(f"{name} must be >= 0 (got {val}); 0 turns it off")
+    return bool(clipnorm or clipvalue)
+
+
+class ClipScratch:
+    """Device buffers of a clipped Adam step: the partial sums of Σg'² (spwgnn_clip_scratch_bytes), the
+    step's out4 = [norm, scale, skipped, clipped] and, with `totals`, the fp64 sums total4 = [Σ norm over
+    the non-skipped steps, Σ clipped, Σ skipped, Σ steps] the update kernel adds to."""
+
+    def __init__(self, device, totals: bool = False):
+        n = int(_lib.lib().spwgnn_clip_scratch_bytes())
+        self.scratch = torch.empty(n, dtype=torch.uint8, device=device)
+        self.out4 = torch.zeros(4, dtype=torch.float32, device=device)
+        self.total4 = torch.zeros(4, dtype=torch.float64, device=device) if totals else None
+
+    def cstruct(self, clipnorm, clipvalue, skip_nonfinite, accumulate: bool) -> _lib.ClipC:
+        c = _lib.ClipC()
+        c.clipnorm, c.clipvalue = float(clipnorm), float(clipvalue)
+        c.skip_nonfinite = 1 if skip_nonfinite else 0
+        c.out4 = self.out4.data_ptr()
+        if accumulate:
+            if self.total4 is None:
+                raise ValueError("ClipScratch was built without totals")
+            c.total4 = self.total4.data_ptr()
+        return c
+
+
+def adam_clipped(params: torch.Tensor, grads: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int,
+                 clip: ClipScratch, lr=5e-4, beta1=0.9, beta2=0.999, eps=1e-7, l2=0.0, grad_scale=1.0,
+                 clipnorm=0.0, clipvalue=0.0, skip_nonfinite=False, accumulate=False) -> torch.Tensor:
+    """`adam` on g' clipped as Keras 2.x's Optimizer.get_gradients does (spwgnn_adam_clipped): by the
+    global norm of g' = grad_scale·grad + 2·l2·param over the real parameters (`clipnorm`), then by value
+    (`clipvalue`); `skip_nonfinite`: a step whose Σg'² is not finite leaves params, m and v untouched.
+    One launch more than `adam`; `grads` is not modified. `lr` is the step's own (a decayed one comes
+    from `adam_lr_decayed`). Returns clip.out4 = [norm, scale, skipped, clipped] (device);
+    `accumulate` also adds the step to clip.total4."""
+    _require_gpu(params, "params")
+    c = clip.cstruct(clipnorm, clipvalue, skip_nonfinite, accumulate)
+    st = _lib.lib().spwgnn_adam_clipped(params.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr(),
+                                        params.numel(), int(step), lr, beta1, beta2, eps, l2, grad_scale, C.byref(c),
+                                        clip.scratch.data_ptr(), _stream(params.device))
+    _lib.check(st, "spwgnn_adam_clipped")
+    return clip.out4
+
+
+def adam_clipped_dev(params: torch.Tensor, grads: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
+                     step_dev: torch.Tensor, lr_table: torch.Tensor, clip: ClipScratch, beta1=0.9, beta2=0.999,
+                     eps=1e-7, l2=0.0, grad_scale=1.0, clipnorm=0.0, clipvalue=0.0, skip_nonfinite=False,
+                     accumulate=False) -> torch.Tensor:
+    """`adam_clipped` with the step count read from `step_dev` and lr_t from `lr_table` (`adam_dev`'s
+    arguments): capturable into a replayed hipGraph. A skipped step still reads the advanced step word:
+    the iteration count moves on whether or not the update was applied."""
+    _require_gpu(params, "params")
+    c = clip.cstruct(clipnorm, clipvalue, skip_nonfinite, accumulate)
+    st = _lib.lib().spwgnn_adam_clipped_dev(params.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr(),
+                                            params.numel(), step_dev.data_ptr(), lr_table.data_ptr(),
+                                            lr_table.numel(), beta1, beta2, eps, l2, grad_scale, C.byref(c),
+                                            clip.scratch.data_ptr(), _stream(params.device))
+    _lib.check(st, "spwgnn_adam_clipped_dev")
+    return clip.out4
 
 
 def step_advance(key_dev: torch.Tensor, step_dev: torch.Tensor, mode: int = _lib.STEP_KEY_COUNTER, seed: int = 0,

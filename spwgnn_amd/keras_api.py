@@ -109,7 +109,8 @@ class KerasModel:
     """One compiled per-N model of the reference (Networks.py:99-104); weights shared via ``net``."""
 
     def __init__(self, net: GraphNetwork, n_objects: int, object_dim: int = 3, lr: float = 5e-4,
-                 l2: float = 0.0):
+                 l2: float = 0.0, clipnorm: float = 0.0, clipvalue: float = 0.0, decay: float = 0.0,
+                 skip_nonfinite: bool = False):
         if object_dim != 3:
             # Networks.py:70-73 + main.py:28-31/59-63: the object_dim=2 path of the reference is
             # broken (om gets 1 feature, boxes[...,2] is out of range); only the Jenga layout runs.
@@ -118,6 +119,12 @@ class KerasModel:
         self.n_objects = n_objects
         self.lr, self.l2 = lr, l2
         self.beta1, self.beta2, self.eps = 0.9, 0.999, 1e-7
+        # Keras 2.x Adam(lr, decay, clipnorm, clipvalue) and the non-finite guard (0 / False = off): with
+        # any of them set every step's update is engine.adam_clipped(_dev), one launch more
+        E.check_clip_options(clipnorm, clipvalue, decay)
+        self.clipnorm, self.clipvalue, self.decay = float(clipnorm), float(clipvalue), float(decay)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._clip: Optional[E.ClipScratch] = None
         dev = net.device
         self.m = torch.zeros_like(net.flat.data)
         self.v = torch.zeros_like(net.flat.data)
@@ -129,7 +136,7 @@ class KerasModel:
         # replayed fit steps (spwgnn_amd/replay.py): device step words, per-geometry graphs, epoch sums
         self._ctr: Optional[DeviceCounters] = None
         self._replays: Optional[ReplayCache] = None
-        self._replay_graph: Optional[tuple] = None   # (graph, weighted) of the cache in _replays
+        self._replay_graph: Optional[tuple] = None   # (graph, weighted, clip options) of the cache in _replays
         self._tot = torch.zeros(3, dtype=torch.float64, device=dev)
         self._w3: Dict[int, torch.Tensor] = {}
 
@@ -163,9 +170,28 @@ class KerasModel:
         out3, dz = E.bce(z, target, self._bce, node_weights=self._dev_weights(node_weights))
         E.backward(net.flat.data, batch, run, self._ws, dz, grads=self._grads)
         self.iterations += 1
-        E.adam(net.flat.data, self._grads, self.m, self.v, self.iterations, self.lr, self.beta1, self.beta2,
-               self.eps, self.l2)
+        if not self._clip_on():
+            E.adam(net.flat.data, self._grads, self.m, self.v, self.iterations, self.lr, self.beta1, self.beta2,
+                   self.eps, self.l2)
+            return out3
+        lr = E.adam_lr_decayed(self.lr, self.decay, self.iterations - 1) if self.decay else self.lr
+        E.adam_clipped(net.flat.data, self._grads, self.m, self.v, self.iterations, self._clip_scratch(), lr,
+                       self.beta1, self.beta2, self.eps, self.l2, 1.0, self.clipnorm, self.clipvalue,
+                       self.skip_nonfinite)
         return out3
+
+    def _clip_on(self) -> bool:
+        return bool(self.clipnorm or self.clipvalue or self.decay or self.skip_nonfinite)
+
+    def _clip_scratch(self) -> E.ClipScratch:
+        if self._clip is None:
+            self._clip = E.ClipScratch(self.net.device, totals=True)
+        return self._clip
+
+    @property
+    def clip_stats(self) -> Optional[torch.Tensor]:
+        """The last clipped step's [norm, scale, skipped, clipped] (device tensor), None before one."""
+        return None if self._clip is None else self._clip.out4
 
     def _dev_weights(self, node_weights) -> Optional[torch.Tensor]:
         if node_weights is None:
@@ -177,6 +203,7 @@ class KerasModel:
         (key + 1, forward, BCE, backward, Adam at the incremented step) with the per-step scalars
         read from the device, and the epoch sums accumulated on the device."""
         net, ctr = self.net, self._ctr
+        clip = self._clip_scratch() if self._clip_on() else None
 
         def body(batch, target, ws, bce, z, dz, pre=None, weights=None, norm=None):
             w3 = self._w3[batch.n_towers]        # created before the first (eager) run of a geometry
@@ -194,8 +221,13 @@ class KerasModel:
             # loss weights and their divisor, views of the step's static buffer
             E.bce_backward(net.flat.data, batch, run, ws, z, target, bce, dlogits=dz, total3=self._tot, weights3=w3,
                            grads=self._grads, node_weights=weights, norm=norm)
-            E.adam_dev(net.flat.data, self._grads, self.m, self.v, ctr.step, ctr.lr_table, self.beta1, self.beta2,
-                       self.eps, self.l2)
+            if clip is None:
+                E.adam_dev(net.flat.data, self._grads, self.m, self.v, ctr.step, ctr.lr_table, self.beta1, self.beta2,
+                           self.eps, self.l2)
+            else:   # the decay is in the lr table; the epoch's clip sums ride in the update launch
+                E.adam_clipped_dev(net.flat.data, self._grads, self.m, self.v, ctr.step, ctr.lr_table, clip,
+                                   self.beta1, self.beta2, self.eps, self.l2, 1.0, self.clipnorm, self.clipvalue,
+                                   self.skip_nonfinite, accumulate=True)
         return body
 
     def evaluate_batch(self, batch: TowerBatch, target: torch.Tensor, node_weights=None, norm=None):
@@ -223,7 +255,11 @@ class KerasModel:
         weights are all zero gives loss 0 and no gradient, where Keras gives NaN (0/0). The accuracies
         count the nodes with w ≠ 0 only — with zero weights a deviation from Keras, whose `metrics=` stay
         unweighted; with none it is Keras's. With neither argument the steps are exactly the unweighted
-        ones."""
+        ones.
+
+        With clipnorm, clipvalue, decay or skip_nonfinite set on the model the history gains, per epoch,
+        `grad_norm` (the mean global gradient norm over the epoch's non-skipped steps), `clipped_steps` and
+        `skipped_steps`, from one fp64 device accumulator read where the loss sums are read."""
         objects = np.asarray(x["objects"], np.float32)
         target = np.asarray(y["target"], np.float32).reshape(objects.shape[0], -1)
         B = objects.shape[0]
@@ -235,6 +271,10 @@ class KerasModel:
         rng = np.random.default_rng(seed)
         dev = self.net.device
         hist = {"loss": [], "binary_accuracy": []}
+        clip_on = self._clip_on()
+        if clip_on:
+            hist.update({"grad_norm": [], "clipped_steps": [], "skipped_steps": []})
+            clip = self._clip_scratch()
         if n_val:
             hist.update({"val_loss": [], "val_binary_accuracy": []})
             vbatch = ds.subset(np.arange(n_tr, B), dev)
@@ -245,23 +285,31 @@ class KerasModel:
         # eagerly); the device words start from the host counters and the host mirrors each step
         if self._ctr is None:
             self._ctr = DeviceCounters(dev, self.net._step_seed, self.iterations, self.lr, self.beta1,
-                                       self.beta2)
+                                       self.beta2, decay=self.decay)
         else:
             self._ctr.set(key=self.net._step_seed, step=self.iterations, lr=self.lr, beta1=self.beta1,
-                          beta2=self.beta2)
-        if self._replays is None or self._replay_graph != (graph, weighted):
+                          beta2=self.beta2, decay=self.decay)
+        # the clip options are baked into a geometry's launches (and its captured graph)
+        opts = (graph, weighted, self.clipnorm, self.clipvalue, self.skip_nonfinite, clip_on)
+        if self._replays is None or self._replay_graph != opts:
             self._replays = ReplayCache(dev, self._replay_body, graph=graph, weighted=weighted)
-            self._replay_graph = (graph, weighted)
+            self._replay_graph = opts
         # per-epoch sums stay on the device (stream-ordered copies) and are read once after the last
         # epoch — with verbose=0 the host never waits for the GPU between epochs (a sync per epoch
         # drained the pipeline: ≈ 8 µs per step at batch 32); verbose > 0 reads them per epoch to print
         ep_tot = torch.zeros(epochs, 3, dtype=torch.float64, device=dev)
         ep_val = torch.zeros(epochs, 3, dtype=torch.float32, device=dev)
+        ep_clip = torch.zeros(epochs, 4, dtype=torch.float64, device=dev) if clip_on else None
 
         def record(ep):
             tot_l, tot_c, tot_n = ep_tot[ep].tolist()
             hist["loss"].append(tot_l / max(n_tr, 1))
             hist["binary_accuracy"].append(tot_c / max(tot_n, 1))
+            if clip_on:
+                c_norm, c_clipped, c_skipped, c_steps = ep_clip[ep].tolist()
+                hist["grad_norm"].append(c_norm / max(c_steps - c_skipped, 1.0))
+                hist["clipped_steps"].append(int(c_clipped))
+                hist["skipped_steps"].append(int(c_skipped))
             if n_val:
                 vl, vc, vn = ep_val[ep].tolist()
                 hist["val_loss"].append(vl)
@@ -272,6 +320,8 @@ class KerasModel:
             # (Σ loss·batch, Σ correct, Σ nodes) on the device: no host sync per batch, so the host
             # builds the next batch while the GPU runs this one
             self._tot.zero_()
+            if clip_on:
+                clip.total4.zero_()
             for b0 in range(0, n_tr, batch_size):
                 idx = order[b0:b0 + batch_size]
                 if len(idx) not in self._w3:
@@ -280,6 +330,8 @@ class KerasModel:
                 self.net._step_seed += 1
                 self.iterations += 1
             ep_tot[ep].copy_(self._tot)
+            if clip_on:
+                ep_clip[ep].copy_(clip.total4)
             if n_val:
                 ep_val[ep].copy_(self.evaluate_batch(vbatch, vtgt, vw, vnorm))
             if verbose:
@@ -312,7 +364,11 @@ class PropagationNetwork:
     weights of the first one built (set_weights / reuse_model, Networks.py:40-56)."""
 
     def __init__(self, device="cuda", seed: int = 0, mp_steps: int = E.REF_MP_STEPS, dropout: float = E.REF_DROPOUT,
-                 math: str = "x6"):
+                 math: str = "x6", clipnorm: float = 0.0, clipvalue: float = 0.0, decay: float = 0.0,
+                 skip_nonfinite: bool = False):
+        # Networks.py:101 Adam(lr=0.0005, decay=0.0); clipnorm / clipvalue are Keras 2.x Optimizer kwargs
+        E.check_clip_options(clipnorm, clipvalue, decay)
+        self._opt = dict(clipnorm=clipnorm, clipvalue=clipvalue, decay=decay, skip_nonfinite=skip_nonfinite)
         if math not in E.MATH_MODES:
             raise ValueError(f"math must be one of {sorted(E.MATH_MODES)}")
         self._math = math   # every model's arithmetic (GraphNetwork.math); "x6": the fp32-class default
@@ -327,6 +383,6 @@ class PropagationNetwork:
         if not self.set_weights:
             self._net = GraphNetwork(self._mp, self._drop, self._seed, device=self._device, math=self._math)
             self.set_weights = True
-        model = KerasModel(self._net, n_objects, object_dim)
+        model = KerasModel(self._net, n_objects, object_dim, **self._opt)
         self.Nets[n_objects] = model
         return model

@@ -49,26 +49,28 @@ class DeviceCounters:
     """The device words a replayable step reads: the dropout key (int64) and the Adam step count
     (int32), with the lr table of the optimizer's (lr, β1, β2)."""
 
-    def __init__(self, device, key: int, step: int, lr: float, beta1: float, beta2: float):
+    def __init__(self, device, key: int, step: int, lr: float, beta1: float, beta2: float, decay: float = 0.0):
         self.device = torch.device(device)
         self.key = torch.tensor([_i64(key)], dtype=torch.int64, device=self.device)
         self.step = torch.tensor([int(step)], dtype=torch.int32, device=self.device)
-        self.lr_table = E.adam_lr_table(LR_TABLE_LEN, lr, beta1, beta2, self.device)
+        self.lr_table = E.adam_lr_table(LR_TABLE_LEN, lr, beta1, beta2, self.device, decay=decay)
         self.hyper = (float(lr), float(beta1), float(beta2))
+        self.decay = float(decay)   # Keras Adam's decay, folded into the table (it freezes at the last entry)
 
     def set(self, key: Optional[int] = None, step: Optional[int] = None, lr: Optional[float] = None,
-            beta1: Optional[float] = None, beta2: Optional[float] = None):
+            beta1: Optional[float] = None, beta2: Optional[float] = None, decay: Optional[float] = None):
         """Host values → device words (stream-ordered copies; outside any capture). A changed
-        (lr, β1, β2) rebuilds the lr table IN PLACE: captured graphs keep reading its address."""
+        (lr, β1, β2) or decay rebuilds the lr table IN PLACE: captured graphs keep reading its address."""
         if key is not None:
             self.key.fill_(_i64(key))
         if step is not None:
             self.step.fill_(int(step))
         hyper = (float(self.hyper[0] if lr is None else lr), float(self.hyper[1] if beta1 is None else beta1),
                  float(self.hyper[2] if beta2 is None else beta2))
-        if hyper != self.hyper:
-            self.lr_table.copy_(E.adam_lr_table(LR_TABLE_LEN, *hyper, self.device))
-            self.hyper = hyper
+        decay = self.decay if decay is None else float(decay)
+        if hyper != self.hyper or decay != self.decay:
+            self.lr_table.copy_(E.adam_lr_table(LR_TABLE_LEN, *hyper, self.device, decay=decay))
+            self.hyper, self.decay = hyper, decay
 
 
 def _mapped_device_ptr(host: torch.Tensor) -> int:

@@ -89,6 +89,18 @@ class HipEngine:
     def adam(self, params, grads, m, v, step, lr, b1, b2, eps, l2, gscale):
         E.adam(params, grads, m, v, step, lr, b1, b2, eps, l2, gscale)
 
+    def clip_scratch(self) -> "E.ClipScratch":
+        if getattr(self, "_clip", None) is None:
+            self._clip = E.ClipScratch(self.device)
+        return self._clip
+
+    def adam_clipped(self, params, grads, m, v, step, lr, b1, b2, eps, l2, gscale, clipnorm, clipvalue,
+                     skip_nonfinite):
+        """`adam` on the clipped gradient (engine.adam_clipped); returns out4 = [norm, scale, skipped,
+        clipped], a device tensor the next step overwrites."""
+        return E.adam_clipped(params, grads, m, v, step, self.clip_scratch(), lr, b1, b2, eps, l2, gscale,
+                              clipnorm, clipvalue, skip_nonfinite)
+
 
 class Trainer:
     """Keras-semantics training step (dropout 0.1, BCE, Adam lr=5e-4 eps=1e-7) with optional DP."""
@@ -96,9 +108,21 @@ class Trainer:
     def __init__(self, params: torch.Tensor, engine=None, mp_steps: int = E.REF_MP_STEPS,
                  dropout: float = E.REF_DROPOUT, seed: int = 0, lr: float = 5e-4, beta1: float = 0.9,
                  beta2: float = 0.999, eps: float = 1e-7, l2: float = 0.0, group=None, math: str = "x6",
-                 buckets: int = 1, overlap: bool = True):
+                 buckets: int = 1, overlap: bool = True, clipnorm: float = 0.0, clipvalue: float = 0.0,
+                 decay: float = 0.0, skip_nonfinite: bool = False):
+        # Keras 2.x optimizer arguments (0 = off) and the non-finite guard: with any of them set the
+        # update is engine.adam_clipped — the global norm of the all-reduced gradient, one launch more —
+        # instead of engine.adam; with none, exactly the launches of before
+        E.check_clip_options(clipnorm, clipvalue, decay)
+        self.clipnorm, self.clipvalue, self.decay = float(clipnorm), float(clipvalue), float(decay)
+        self.skip_nonfinite = bool(skip_nonfinite)
         self.params = params
         self.engine = engine if engine is not None else HipEngine(params.device)
+        if self._clip_on() and not hasattr(self.engine, "adam_clipped"):
+            raise ValueError("clipnorm / clipvalue / decay / skip_nonfinite need an engine with adam_clipped("
+                             "params, grads, m, v, step, lr, b1, b2, eps, l2, gscale, clipnorm, clipvalue, "
+                             "skip_nonfinite)")
+        self.clip_stats = None    # the last clipped step's [norm, scale, skipped, clipped] (device tensor)
         self.m = torch.zeros_like(params)
         self.v = torch.zeros_like(params)
         self.mp_steps, self.dropout, self.seed, self.math = mp_steps, dropout, seed, math
@@ -128,6 +152,21 @@ class Trainer:
         self._ctr_at = 0          # the host iteration count the device step word holds
         self._w3 = {}             # (n_nodes, 1, 1) fp64 weights of a micro-batch's [loss, correct, n]
 
+    def _clip_on(self) -> bool:
+        return bool(self.clipnorm or self.clipvalue or self.decay or self.skip_nonfinite)
+
+    def _adam(self, acc):
+        """The update of step `iterations` (already advanced) from the reduced gradient `acc`: after the
+        all-reduce, so every rank clips by the same norm and takes the same skip decision."""
+        if not self._clip_on():
+            self.engine.adam(self.params, acc, self.m, self.v, self.iterations, self.lr, self.b1, self.b2, self.eps,
+                             self.l2, 1.0)
+            return
+        lr = E.adam_lr_decayed(self.lr, self.decay, self.iterations - 1) if self.decay else self.lr
+        self.clip_stats = self.engine.adam_clipped(self.params, acc, self.m, self.v, self.iterations, lr, self.b1,
+                                                   self.b2, self.eps, self.l2, 1.0, self.clipnorm, self.clipvalue,
+                                                   self.skip_nonfinite)
+
     def _early(self, run):
         """Overlapped steps: the engine's early-gradient event, handed to the backward through `run`."""
         if not self._split():
@@ -143,13 +182,15 @@ class Trainer:
                            prof_kernel=self.prof_kernel, prof_events=self.prof_events)
 
     def _sync_counters(self):
-        """Device step word and lr table ← the host's iteration count and (lr, β1, β2), when they
-        differ (a step() or an lr change since the last replay)."""
+        """Device step word and lr table ← the host's iteration count and (lr, β1, β2, decay), when they
+        differ (a step() or an lr / decay change since the last replay)."""
         from .replay import DeviceCounters
         if self._ctr is None:
-            self._ctr = DeviceCounters(self.params.device, 0, self.iterations, self.lr, self.b1, self.b2)
-        elif self._ctr_at != self.iterations or self._ctr.hyper != (float(self.lr), float(self.b1), float(self.b2)):
-            self._ctr.set(step=self.iterations, lr=self.lr, beta1=self.b1, beta2=self.b2)
+            self._ctr = DeviceCounters(self.params.device, 0, self.iterations, self.lr, self.b1, self.b2,
+                                       decay=self.decay)
+        elif (self._ctr_at != self.iterations or self._ctr.hyper != (float(self.lr), float(self.b1), float(self.b2))
+              or self._ctr.decay != float(self.decay)):
+            self._ctr.set(step=self.iterations, lr=self.lr, beta1=self.b1, beta2=self.b2, decay=self.decay)
         self._ctr_at = self.iterations
 
     def replay_body(self, n_nodes: int, n_global: Optional[int] = None, weighted: bool = False):
@@ -175,6 +216,10 @@ class Trainer:
             raise ValueError("weighted replayed steps cover the whole batch (no n_global)")
         w = n_nodes / (n_global or n_nodes)
         grads = torch.empty_like(self.params)
+        E.check_clip_options(self.clipnorm, self.clipvalue, self.decay)
+        clip = self.engine.clip_scratch() if self._clip_on() else None
+        if clip is not None:
+            self.clip_stats = clip.out4
 
         def body(batch, target, ws, bce, z, dz, pre=None, weights=None, norm=None):
             # the key/step advance (and the replayed batch upload, `pre`) ride in the forward's first launch
@@ -193,8 +238,12 @@ class Trainer:
                            node_weights=weights, norm=norm)
             if w != 1.0:
                 grads.mul_(w)
-            E.adam_dev(self.params, grads, self.m, self.v, ctr.step, ctr.lr_table, self.b1, self.b2, self.eps,
-                       self.l2)
+            if clip is None:
+                E.adam_dev(self.params, grads, self.m, self.v, ctr.step, ctr.lr_table, self.b1, self.b2, self.eps,
+                           self.l2)
+            else:   # the decay is in the lr table (_sync_counters)
+                E.adam_clipped_dev(self.params, grads, self.m, self.v, ctr.step, ctr.lr_table, clip, self.b1, self.b2,
+                                   self.eps, self.l2, 1.0, self.clipnorm, self.clipvalue, self.skip_nonfinite)
         return body
 
     def bucket_bounds(self, n: int):
@@ -335,8 +384,7 @@ class Trainer:
                 if self.distributed:   # any process group (one rank: the identity, through the collective)
                     self.allreduce(acc)
             self.iterations += 1
-            self.engine.adam(self.params, acc, self.m, self.v, self.iterations, self.lr, self.b1, self.b2, self.eps,
-                             self.l2, 1.0)
+            self._adam(acc)
             return res.float() if res.dtype != torch.float32 else res
         for i, (b, tg) in enumerate(zip(batches, targets)):
             if i:
@@ -378,8 +426,7 @@ class Trainer:
         if self.distributed and not self._split():
             self.allreduce(acc)
         self.iterations += 1
-        self.engine.adam(self.params, acc, self.m, self.v, self.iterations, self.lr, self.b1, self.b2, self.eps,
-                         self.l2, 1.0)
+        self._adam(acc)
         # node-weighted mean loss of this rank's shard, total correct, total nodes (device, fp32)
         return torch.stack([tot3[0] / tot3[2], tot3[1], tot3[2]]).float()
 
@@ -421,6 +468,5 @@ class Trainer:
         if self.distributed and not self._split():
             self.allreduce(acc)
         self.iterations += 1
-        self.engine.adam(self.params, acc, self.m, self.v, self.iterations, self.lr, self.b1, self.b2, self.eps,
-                         self.l2, 1.0)
+        self._adam(acc)
         return torch.stack([tot3[0] / tot3[2].clamp(min=1.0), tot3[1], tot3[2]]).float()
