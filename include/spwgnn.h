@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense; spwgnn_clip, spwgnn_adam_clipped, spwgnn_adam_clipped_dev, spwgnn_adam_lr_decayed, spwgnn_adam_lr_table_decay); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense; spwgnn_clip, spwgnn_adam_clipped, spwgnn_adam_clipped_dev, spwgnn_adam_lr_decayed, spwgnn_adam_lr_table_decay; spwgnn_forward_steps, spwgnn_backward_steps, spwgnn_step_weights, spwgnn_bce_steps); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
@@ -48,7 +48,8 @@ typedef struct spwgnn_param_info {
 int32_t spwgnn_version(void);
 /* sizeof the ABI structs as this library was compiled (bindings check their own layouts against it):
  * which = 0 spwgnn_batch, 1 spwgnn_run, 2 spwgnn_plan_sizes, 3 spwgnn_param_info,
- * 4 spwgnn_loss_weights, 6 spwgnn_plan_device, 7 spwgnn_clip; -1 otherwise (5 is not used and stays -1). */
+ * 4 spwgnn_loss_weights, 6 spwgnn_plan_device, 7 spwgnn_clip, 9 spwgnn_step_weights; -1 otherwise (5 and 8
+ * are not used and stay -1). */
 int32_t spwgnn_struct_size(int32_t which);
 const char* spwgnn_strerror(int32_t status);
 int32_t spwgnn_param_tensor_count(void);
@@ -448,6 +449,57 @@ int32_t spwgnn_bce_backward_weighted(const float* params, const spwgnn_batch* ba
                                      const float* targets, int64_t n, float* out3, float* dlogits, void* bce_scratch,
                                      const double* weights3, double* total3, float* grads, float* dprop,
                                      const spwgnn_loss_weights* lw, spwgnn_stream_t stream);
+
+/* Per-step logits and their gradients: deep supervision over the S propagation steps (added within ABI
+ * 8: new symbols only, no existing struct or signature changed). Column 0 of the node
+ * MLP's output holds a stability logit at EVERY step (Networks.py:89-94); the model reads the last one.
+ * Step s's logit of an S-step run is the final logit of the same network run with s + 1 steps.
+ *
+ * spwgnn_forward_steps: spwgnn_forward_state, with every step's logit row instead of the last one's:
+ * step_logits [mp_steps][n_nodes] device fp32, row s = step s, nodes in the plan's order. Row
+ * mp_steps − 1 holds the bits spwgnn_forward writes (the last step keeps its shortcuts); the other rows
+ * are stores of values the step computed anyway. state_out as in spwgnn_forward_state (NULL = none).
+ * Training and inference, every math, every plan kind, every launch path (the fused small-batch loop
+ * forms row s from one stride); spwgnn_fused_path's answer holds. */
+int32_t spwgnn_forward_steps(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                             void* workspace, int64_t workspace_bytes, float* step_logits /* [mp_steps][n_nodes] */,
+                             float* state_out /* [n_nodes][100], or NULL */, spwgnn_stream_t stream);
+/* spwgnn_backward_steps: spwgnn_backward_state for Σ_s Σ_i dstep_logits[s][i]·z_s[i] (+ Σ dstate·P_S) in
+ * ONE pass over the step loop: step s's node backward puts row s into x' row 100 before dx' is stored
+ * and multiplied by Wo2'ᵀ; everything downstream (the omp.1 gradient, dA, the encoders, dprop,
+ * spwgnn_backward_inputs, grads_early_event) consumes what it consumed. dstep_logits [mp_steps][n_nodes]
+ * device fp32. The last step keeps its "dx' is the logit row alone" shortcut and the earlier steps run
+ * the products they always ran, so rows of +0 except the last give spwgnn_backward_state's bits.
+ * The forward on this workspace may have been any of spwgnn_forward / _state / _steps (dstate != NULL
+ * needs a state_out forward, as for spwgnn_backward_state). */
+int32_t spwgnn_backward_steps(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                              void* workspace, int64_t workspace_bytes, const float* dstep_logits /* [mp_steps][n_nodes] */,
+                              const float* dstate /* [n_nodes][100], or NULL */, float* grads, float* dprop,
+                              spwgnn_stream_t stream);
+
+/* The loss of all S rows against one target row: Σ_s λ_s·BCE(z_s, t). One launch (two when n > 256, as
+ * spwgnn_bce). The step weights travel by value in spwgnn_step_weights. lw == NULL: row s is spwgnn_bce's
+ * arithmetic; lw set: spwgnn_bce_weighted's (same struct, same rules). Outputs:
+ *   out3s   [S][3]  each step's {loss, correct, n} as the one-row call writes them (clip and divisor);
+ *   out3    [3]     {Σ_s λ_s·loss_s (added in double, step order, zero λ skipped), correct_{S−1}, n_{S−1}};
+ *   dlogits [S][n]  row s = λ_s · the one-row call's dlogits; λ_s == 0 writes +0 through a select, so a
+ *                   NaN logit in a step of zero weight stays out of the gradient. NULL = not written.
+ * With λ = (0, …, 0, 1) out3 and row S − 1 of dlogits are the bits of spwgnn_bce / spwgnn_bce_weighted.
+ * weights3 / total3 as in spwgnn_bce_accumulate (both or neither; applied to out3); total3s (NULL = none;
+ * needs weights3) [S][3] doubles: += out3s[s][k]·weights3[k] in the same launch — per-step epoch sums.
+ * Deterministic (ordered partial sums, no atomics). scratch >= spwgnn_bce_steps_scratch_bytes(n, S).
+ * SPWGNN_E_ARG: a null required pointer, n < 1, mp_steps outside 1..64, sw->count != mp_steps, a negative
+ * or non-finite λ, λ all zero, lw given but invalid, weights3 / total3 not paired, total3s without them. */
+typedef struct spwgnn_step_weights {
+    int32_t count;       /* = mp_steps */
+    int32_t reserved;    /* 0 */
+    float lambda[64];    /* λ_s >= 0 for s < count; the rest is ignored */
+} spwgnn_step_weights;
+int64_t spwgnn_bce_steps_scratch_bytes(int64_t n, int32_t mp_steps);
+int32_t spwgnn_bce_steps(const float* step_logits /* [mp_steps][n] */, const float* targets /* [n] */, int64_t n,
+                         int32_t mp_steps, const spwgnn_step_weights* sw, const spwgnn_loss_weights* lw,
+                         float* out3s, float* out3, float* dlogits, void* scratch, const double* weights3,
+                         double* total3, double* total3s, spwgnn_stream_t stream);
 
 /* Keras-2.x Adam (Networks.py:101: lr=5e-4, decay=0): in-place on the flat buffer.
  * g' = grad_scale*grad + 2*l2*param; lr_t = lr*sqrt(1-b2^t)/(1-b1^t);

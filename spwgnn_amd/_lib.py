@@ -72,6 +72,14 @@ class ClipC(C.Structure):
                 ("reserved", C.c_int32), ("out4", C.c_void_p), ("total4", C.c_void_p)]
 
 
+MAX_STEPS = 64   # mp_steps' bound (the library's validate) and spwgnn_step_weights' lambda slots
+
+
+class StepWeightsC(C.Structure):
+    """spwgnn_step_weights: the per-step loss weights of spwgnn_bce_steps, by value (added within ABI 8)."""
+    _fields_ = [("count", C.c_int32), ("reserved", C.c_int32), ("lam", C.c_float * MAX_STEPS)]
+
+
 K_EDGE_FWD, K_NODE_FWD, K_EDGE_BWD, K_NODE_BWD, K_ENC_EDGE, K_ENC_EDGE_BWD, K_WGRAD_W2, K_DA = 1, 2, 3, 4, 5, 6, 7, 8
 K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD, K_INPUT_BWD, K_PLAN_DEVICE, K_STATE = 9, 10, 11, 12, 13, 14
 MATH_F32, MATH_X6, MATH_BF16, MATH_X3, MATH_H3 = 0, 1, 2, 3, 4
@@ -112,6 +120,11 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_backward": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp, vp]),
         "spwgnn_forward_state": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp]),
         "spwgnn_backward_state": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp, vp, vp]),
+        "spwgnn_forward_steps": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp]),
+        "spwgnn_backward_steps": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp, vp, vp]),
+        "spwgnn_bce_steps_scratch_bytes": (i64, [i64, i32]),
+        "spwgnn_bce_steps": (i32, [vp, vp, i64, i32, C.POINTER(StepWeightsC), C.POINTER(LossWeightsC), vp, vp, vp, vp,
+                                   vp, vp, vp, vp]),
         "spwgnn_backward_inputs": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp]),
         "spwgnn_plan_device_positions": (i32, [C.POINTER(PlanDeviceC), vp, i32, f32, f32, vp]),
         "spwgnn_plan_device_dense": (i32, [C.POINTER(PlanDeviceC), vp, vp, i32, i32, vp]),
@@ -157,7 +170,7 @@ def lib() -> C.CDLL:
             raise SpwgnnError(f"{path} implements ABI {lib_.spwgnn_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild with `python -m spwgnn_amd.build`")
         for which, st in ((0, BatchC), (1, RunC), (2, PlanSizes), (3, ParamInfo), (4, LossWeightsC), (6, PlanDeviceC),
-                          (7, ClipC)):
+                          (7, ClipC), (9, StepWeightsC)):
             if lib_.spwgnn_struct_size(which) != C.sizeof(st):
                 raise SpwgnnError(f"{path} was built with a different {st.__name__} layout "
                                   f"({lib_.spwgnn_struct_size(which)} vs {C.sizeof(st)} bytes): rebuild it")

@@ -406,8 +406,12 @@ static bool wide_node_side(const spwgnn_run* r, const spwgnn_batch* b) {
 }
 
 // keep_state (spwgnn_forward_state with a buffer): the last step leaves P_S in P_at(S) on every path
+// logit_step (spwgnn_forward_steps): 0 = `logits` is the last step's row, the only one
+// stored; else `logits` is [S][logit_step] and step s stores its own row (every node forward stores
+// through NodeFwdArgs::logits when it is set; step S−1 keeps its `last` shortcut)
 static int32_t run_forward(const float* params, const spwgnn_batch* b, const spwgnn_run* r, const Ws& w,
-                           char* base, float* logits, hipStream_t st, bool keep_state = false) {
+                           char* base, float* logits, hipStream_t st, bool keep_state = false,
+                           int64_t logit_step = 0) {
     Ctx c{w, base};
     const bool zero_prop = b->prop == nullptr;   // 'propagation' = 0 (spwgnn.h): P0 = U0 = V0 = 0
     PrepArgs pa{};
@@ -563,7 +567,7 @@ static int32_t run_forward(const float* params, const spwgnn_batch* b, const spw
         nf.a_out = r->training ? c.f(w.a_at(s)) : nullptr;
         nf.o1_out = r->training ? c.f(w.o1_at(s)) : nullptr;
         nf.Pn = c.f(w.P_at(s + 1));
-        nf.logits = (s == S - 1) ? logits : nullptr;
+        nf.logits = (s == S - 1 || logit_step) ? logits + s * logit_step : nullptr;
         nf.U = (s + 1 < S) ? c.f(w.U_at(s + 1)) : nullptr;
         nf.V = (s + 1 < S) ? c.f(w.V_at(s + 1)) : nullptr;
         nf.w3a = c.pk(PK_W3A);
@@ -610,6 +614,7 @@ static int32_t run_forward(const float* params, const spwgnn_batch* b, const spw
         fa.m1_step = r->training ? w.m1_at(1) - w.m1_at(0) : 0;
         fa.m2_step = r->training ? w.m2_at(1) - w.m2_at(0) : 0;
         fa.logits = logits;
+        fa.logit_step = logit_step;
         // the encoders side by side in their own launch (a workgroup per block / node block) beat
         // running them one after the other inside each tile's workgroup
         fa.encoders = getenv_flag("SPWGNN_FUSED_ENC");
@@ -862,9 +867,11 @@ static void ws_group(WsBatch* wsb, int first, int n) {
 
 // dstate (spwgnn_backward_state): the cotangent of P_S, row-major; it enters the step loop as step
 // S−1's incoming dP (NodeBwdArgs::seeded), so the loop runs once for Σ dlogits·z + Σ dstate·P_S
+// dl_step (spwgnn_backward_steps): 0 = `dlogits` is the last step's cotangent, the only
+// one; else `dlogits` is [S][dl_step] and step s's node backward puts row s into x' row 100
 int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, char* base,
                      const float* dlogits, float* grads, float* dprop, hipStream_t st, const BceArgs* bce = nullptr,
-                     const float* dstate = nullptr) {
+                     const float* dstate = nullptr, int64_t dl_step = 0) {
     (void)params;  // the packed copies made by the forward on this workspace are used
     Ctx c{w, base};
     const int S = r->mp_steps;
@@ -902,7 +909,7 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
         nb.Pn = c.f(w.P_at(s + 1));
         nb.o1 = c.f(w.o1_at(s));
         nb.a = c.f(w.a_at(s));
-        nb.dlogits = dlogits;
+        nb.dlogits = (first || dl_step) ? dlogits + s * dl_step : nullptr;
         nb.dx = c.f(w.dx_at(s));
         nb.do1 = c.f(w.do1_at(s));
         nb.g = c.f(w.g_at(s));
@@ -1074,6 +1081,8 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
         // small batch: the step loop, dA and both encoder backwards in one launch (timed as the node backward)
         BwdFusedArgs fa{};
         fa.nb = node_args(0);
+        fa.nb.dlogits = dlogits;            // row 0; the loop forms each step's own from dl_step
+        fa.dl_step = dl_step;
         fa.nb.seeded = dstate != nullptr;   // step S−1's (the loop sets each step's own)
         fa.nb.dU = c.f(w.dU_at(1));   // step 0's incoming dU/dV (BwdFusedArgs)
         fa.nb.dV = c.f(w.dV_at(1));
@@ -1108,7 +1117,7 @@ int32_t run_backward(const float* params, const spwgnn_batch* b, const spwgnn_ru
         for (int s = S - 1; s >= 0; --s) {
             const NodeBwdArgs nb = node_args(s);
             SPW_CHECK(prof.before(SPWGNN_K_NODE_BWD));
-            SPW_CHECK(launch_node_bwd(nb, kmath(r, kX6NodeBwd), st));
+            SPW_CHECK(launch_node_bwd(nb, kmath(r, kX6NodeBwd), st, dl_step != 0));
             SPW_CHECK(prof.after(SPWGNN_K_NODE_BWD));
             if (s == 0 && skip_eb0) break;   // dU_0 / dV_0 stay unwritten: nothing reads them
             const EdgeBwdArgs eb = edge_args(s);
@@ -1444,6 +1453,41 @@ int32_t spwgnn_backward_state(const float* params, const spwgnn_batch* batch, co
                         static_cast<hipStream_t>(stream), nullptr, dstate);
 }
 
+// Per-step logits: the same launches as spwgnn_forward_state / spwgnn_backward_state,
+// each step's node side given its own row
+int32_t spwgnn_forward_steps(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                             int64_t workspace_bytes, float* step_logits, float* state_out, spwgnn_stream_t stream) {
+    int32_t stt = validate(batch, run);
+    if (stt) return stt;
+    if (!params || !workspace || !step_logits || reinterpret_cast<uintptr_t>(state_out) % 16) return SPWGNN_E_ARG;
+    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, run->training ? 1 : 0);
+    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    stt = run_forward(params, batch, run, w, static_cast<char*>(workspace), step_logits, st, state_out != nullptr,
+                      batch->n_nodes);
+    if (stt || !state_out) return stt;
+    const Ctx c{w, static_cast<char*>(workspace)};
+    const Prof prof{run, st};
+    SPW_CHECK(prof.before(SPWGNN_K_STATE));
+    SPW_CHECK(launch_state_export(c.f(w.P_at(run->mp_steps)), state_out, batch->n_nodes, st));
+    SPW_CHECK(prof.after(SPWGNN_K_STATE));
+    return SPWGNN_OK;
+}
+
+int32_t spwgnn_backward_steps(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                              int64_t workspace_bytes, const float* dstep_logits, const float* dstate, float* grads,
+                              float* dprop, spwgnn_stream_t stream) {
+    int32_t stt = validate(batch, run);
+    if (stt) return stt;
+    if (!run->training) return SPWGNN_E_NOTRAIN;
+    if (!params || !workspace || !dstep_logits || !grads || reinterpret_cast<uintptr_t>(dstate) % 16)
+        return SPWGNN_E_ARG;
+    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, 1);
+    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
+    return run_backward(params, batch, run, w, static_cast<char*>(workspace), dstep_logits, grads, dprop,
+                        static_cast<hipStream_t>(stream), nullptr, dstate, batch->n_nodes);
+}
+
 int32_t spwgnn_backward_inputs(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
                                int64_t workspace_bytes, float* dpos, spwgnn_stream_t stream) {
     int32_t stt = validate(batch, run);
@@ -1635,6 +1679,48 @@ int32_t spwgnn_bce_weighted(const float* logits, const float* targets, int64_t n
     if (!logits || !targets || !out3 || !scratch || n < 1) return SPWGNN_E_ARG;
     const BceArgs a = weighted_bce_args(logits, targets, n, out3, dlogits, scratch, weights3, total3, lw);
     hipError_t e = launch_bce(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+}
+
+int64_t spwgnn_bce_steps_scratch_bytes(int64_t n, int32_t mp_steps) {
+    (void)n;
+    if (mp_steps < 1 || mp_steps > kMaxSteps) return -1;
+    return (int64_t)mp_steps * 256 * 3 * sizeof(float);   // [S][blocks][3]
+}
+
+int32_t spwgnn_bce_steps(const float* step_logits, const float* targets, int64_t n, int32_t mp_steps,
+                         const spwgnn_step_weights* sw, const spwgnn_loss_weights* lw, float* out3s, float* out3,
+                         float* dlogits, void* scratch, const double* weights3, double* total3, double* total3s,
+                         spwgnn_stream_t stream) {
+    if (!step_logits || !targets || !out3s || !out3 || !scratch || !sw || n < 1) return SPWGNN_E_ARG;
+    if (mp_steps < 1 || mp_steps > kMaxSteps || sw->count != mp_steps) return SPWGNN_E_ARG;
+    if ((lw && !loss_weights_ok(lw)) || (!weights3) != (!total3) || (total3s && !weights3)) return SPWGNN_E_ARG;
+    bool any = false;
+    for (int s = 0; s < mp_steps; ++s) {
+        const float l = sw->lambda[s];
+        if (!std::isfinite(l) || l < 0.f) return SPWGNN_E_ARG;
+        any = any || l != 0.f;
+    }
+    if (!any) return SPWGNN_E_ARG;
+    BceStepsArgs a{};
+    if (lw) {
+        a.b = weighted_bce_args(step_logits, targets, n, out3, dlogits, scratch, weights3, total3, lw);
+    } else {   // as bce_launch builds it
+        a.b.w3 = weights3;
+        a.b.tot3 = total3;
+        a.b.logits = step_logits;
+        a.b.targets = targets;
+        a.b.n = n;
+        a.b.dlogits = dlogits;
+        a.b.partial = static_cast<float*>(scratch);
+        a.b.out3 = out3;
+        a.b.blocks = (int)std::min<int64_t>(256, (n + 255) / 256);
+    }
+    a.S = mp_steps;
+    a.out3s = out3s;
+    a.tot3s = total3s;
+    for (int s = 0; s < mp_steps; ++s) a.lambda[s] = sw->lambda[s];
+    hipError_t e = launch_bce_steps(a, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
 }
 

@@ -65,6 +65,7 @@ int32_t spwgnn_struct_size(int32_t which) {
         case 4: return (int32_t)sizeof(spwgnn_loss_weights);
         case 6: return (int32_t)sizeof(spwgnn_plan_device);   // 5 stays -1
         case 7: return (int32_t)sizeof(spwgnn_clip);
+        case 9: return (int32_t)sizeof(spwgnn_step_weights);   // 8 stays -1
         default: return -1;
     }
 }

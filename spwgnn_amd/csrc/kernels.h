@@ -199,13 +199,14 @@ struct NodeFwdArgs {
 
 struct NodeBwdArgs {
     int n_nodes;
-    int first;      // 1 for the last propagation step: dlogits go into x' row 100, no dU / dV (no step S)
+    int first;      // 1 for the last propagation step: no dU / dV (no step S)
     int seeded;     // first only: 1 = an incoming dP (the state cotangent, spwgnn_backward_state) is read
                     //   from dPin and P_S from Pn; 0 = the incoming dP is zero (dPin null, P_S unread)
     int tail;       // 1: only compute dP0 = dPpart + dU·W1bᵀ + dV·W1cᵀ into dprop (ld 100)
     const float *dPin, *dU, *dV;   // from step s+1 (dU, dV null when first; dPin null when first and not seeded)
     const float *Pn, *o1, *a;      // P_{s+1}, o1_s, a_s
-    const float* dlogits;
+    const float* dlogits;          // non-null: this step's logit cotangent goes into x' row 100 — the last step's
+                                   //   (first) for spwgnn_backward, every step's own row for spwgnn_backward_steps
     float *dx, *do1, *g, *G3, *dPout, *dco, *dprop;
     int dco_accumulate;
     int dco_sum;    // x6: no dco here; k_enc_node_bwd applies Wo1cᵀ once to Σ_s do1_s (linear)
@@ -405,6 +406,20 @@ __device__ __forceinline__ float bce_dlogit(float z0, float t, float inv_n) {
 __device__ __forceinline__ float bce_dlogit_w(float z0, float t, float w, float inv_norm) {
     return w != 0.f ? w * bce_dlogit(z0, t, inv_norm) : 0.f;
 }
+// spwgnn_bce_steps: the loss of every propagation step's logit row in one launch.
+// b is the one-row loss (b.w null or set, as spwgnn_bce / spwgnn_bce_weighted build it) with logits =
+// row 0 of [S][n], dlogits = row 0 of [S][n] (or null), out3 = the combined {Σ_s λ_s·loss_s,
+// correct_{S−1}, n_{S−1}} and partial = [S][blocks][3]; the step weights travel by value.
+constexpr int kMaxSteps = 64;   // validate()'s bound on mp_steps
+struct BceStepsArgs {
+    BceArgs b;
+    int S;
+    float* out3s;     // [S][3]: each step's {loss, correct, n} as the one-row loss writes them
+    double* tot3s;    // null, or [S][3]: += (double)out3s[s][k] · b.w3[k] (with b.tot3 for the combined row)
+    float lambda[kMaxSteps];
+};
+hipError_t launch_bce_steps(const BceStepsArgs& a, hipStream_t st);
+
 struct ReduceBatch {       // the weight gradients of one backward, reduced in one launch (blockIdx.y)
     ReduceArgs r[kMaxReduce];
     int n;
@@ -452,7 +467,7 @@ hipError_t launch_enc_node(const EncNodeArgs& a, int math, hipStream_t st);
 hipError_t launch_enc_edge(const EncEdgeArgs& a, int math, hipStream_t st);
 hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st);
 hipError_t launch_node_fwd(const NodeFwdArgs& a, int math, hipStream_t st);
-hipError_t launch_node_bwd(const NodeBwdArgs& a, int math, hipStream_t st);
+hipError_t launch_node_bwd(const NodeBwdArgs& a, int math, hipStream_t st, bool steps = false);
 hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st);
 hipError_t launch_enc_edge_bwd(const EncEdgeBwdArgs& a, int math, hipStream_t st);
 hipError_t launch_dA(const DaArgs& a, int math, hipStream_t st);
@@ -595,7 +610,9 @@ struct FwdFusedArgs {
     int encoders;             // 1: both encoders first, in this launch; 0: they ran before (k_enc_pair_team)
     int64_t rowsN, rowsE;     // floats per step of a 104- / 152-feature node array (RN·kRowN, RN·kRowE)
     int64_t m1_step, m2_step; // u32 words per step of mask1 / mask2
-    float* logits;
+    float* logits;            // the last step's row; with logit_step, row 0 of [S][logit_step]
+    int64_t logit_step;       // 0: only step S−1 stores its logit (spwgnn_forward); else step s stores to
+                              //   logits + s·logit_step (spwgnn_forward_steps)
 };
 bool fwd_fused_team(int n_wtiles, int nw_max, int n_eblocks, int n_nodes, int math);
 // ... and its backward up to the weight gradients (same batches): per wave-tile the S steps' node
@@ -612,6 +629,8 @@ struct BwdFusedArgs {
     int encoders;   // 1: dA rebuild and both encoder backwards in this launch; 0: k_bwd_enc_pair_team after it
     int dA_in_loop; // 1: this launch leaves dA (Σ_s dh1pre_s summed in LDS through the step loop)
     int64_t rowsN, rowsE, m1_step, m2_step;
+    int64_t dl_step;   // 0: nb.dlogits is step S−1's row, the other steps get none (spwgnn_backward); else step s
+                       //   reads nb.dlogits + s·dl_step (spwgnn_backward_steps)
 };
 hipError_t launch_fwd_fused_team(const FwdFusedArgs& a, int math, bool train, hipStream_t st);
 hipError_t launch_bwd_fused_team(const BwdFusedArgs& a, int math, hipStream_t st);

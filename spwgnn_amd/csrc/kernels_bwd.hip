@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     }
     // the residual path: dP_s gets dpre directly (Add()([prop_layer(x), prop]))
     store_cm<4>(a.dPout + bN, D, lane, valid);
-    if (a.first && h == 1) D[3][0] = valid ? a.dlogits[n] : 0.f;  // x' row 100 = logit
+    if (a.dlogits && h == 1) D[3][0] = valid ? a.dlogits[n] : 0.f;  // x' row 100 = logit (this step's cotangent)
     store_cm<4>(a.dx + bN, D, lane, valid);
 
     f32x16 G[4];
@@ -123,7 +123,10 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 // column tiles per wave (launched: NC = 1 at two waves per SIMD).
 // NW > 0: weight images shared by the workgroup's waves through an LDS ring (k_node_fwd_x6).
 // N16 (bf16 math, §3g node side): dU, dV, o1 read and dx, g stored as bf16
-template <int NC, int NP = 3, int NW = 0, bool N16 = false>
+// STEPS (spwgnn_backward_steps, §3zr): every step puts its own a.dlogits row into x' row 100, not only
+// the last one. A template parameter: tested at run time, the x3 form ran over its 256 registers into
+// scratch, so spwgnn_backward keeps the instantiations it had
+template <int NC, int NP = 3, int NW = 0, bool N16 = false, bool STEPS = false>
 __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_bwd_x6(NodeBwdArgs a) {
     const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
     const int nb0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * NC;
@@ -209,7 +212,7 @@ __global__ __launch_bounds__(256, NC == 1 ? 2 : 1) void k_node_bwd_x6(NodeBwdArg
         }
         // the residual path: dP_s gets dpre directly (Add()([prop_layer(x), prop]))
         if (dp_rmw && has[c]) store_cm<4>(a.dPout + bN(c), D[c], lane, valid[c]);
-        if (a.first && h == 1) D[c][3][0] = valid[c] ? a.dlogits[(nb0 + c) * 32 + j] : 0.f;  // x' row 100 = logit
+        if ((STEPS || a.first) && h == 1) D[c][3][0] = valid[c] ? a.dlogits[(nb0 + c) * 32 + j] : 0.f;  // x' row 100 = logit
         if (has[c]) {
             if constexpr (N16) store_cm_b16<4>(reinterpret_cast<uint16_t*>(a.dx) + bN(c), D[c], lane, valid[c]);
             else store_cm<4>(a.dx + bN(c), D[c], lane, valid[c]);
@@ -726,11 +729,21 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 }
 
 // ------------------------------------------------------------------------------------------------
-hipError_t launch_node_bwd(const NodeBwdArgs& a, int math, hipStream_t st) {
+// steps (spwgnn_backward_steps): a.dlogits is this step's own row on every step. k_node_bwd and the team
+// kernels read it whenever it is set (the caller leaves it null on the steps without one); the wide
+// split-bf16 kernel takes its STEPS instantiation
+hipError_t launch_node_bwd(const NodeBwdArgs& a, int math, hipStream_t st, bool steps) {
+    if (!a.tail && (steps || a.first) && !a.dlogits) return hipErrorInvalidValue;
     if ((math_split32(math) || math == MATH_BF16) && a.dco_sum && team_blocks((a.n_nodes + 31) / 32))
         return a.n16 ? hipErrorInvalidValue : launch_node_bwd_team(a, math, st);   // team kernels: fp32 arrays
     if (a.n16 && math != MATH_BF16) return hipErrorInvalidValue;
     if (math == MATH_BF16) {
+        const dim3 g(((a.n_nodes + 31) / 32 + 3) / 4), b(256);
+        if (steps && !a.tail) {
+            if (a.n16) hipLaunchKernelGGL((k_node_bwd_x6<1, 1, 4, true, true>), g, b, 0, st, a);
+            else hipLaunchKernelGGL((k_node_bwd_x6<1, 1, 4, false, true>), g, b, 0, st, a);
+            return hipGetLastError();
+        }
         const int w = (a.n_nodes + 31) / 32;
         if (a.n16) hipLaunchKernelGGL((k_node_bwd_x6<1, 1, 4, true>), dim3((w + 3) / 4), dim3(256), 0, st, a);
         else hipLaunchKernelGGL((k_node_bwd_x6<1, 1, 4>), dim3((w + 3) / 4), dim3(256), 0, st, a);
@@ -742,7 +755,10 @@ hipError_t launch_node_bwd(const NodeBwdArgs& a, int math, hipStream_t st) {
         // per-wave rings, 0.630 for that with the shared ring: 393K nodes)
         constexpr int NC = 1, NW = 4;
         const int w2 = ((a.n_nodes + 31) / 32 + NC - 1) / NC;
-        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_node_bwd_x6<NC, NP, NW>), dim3((w2 + 3) / 4), dim3(256), 0, st, a));
+        if (steps && !a.tail)
+            SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_node_bwd_x6<NC, NP, NW, false, true>), dim3((w2 + 3) / 4), dim3(256), 0, st, a));
+        else
+            SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_node_bwd_x6<NC, NP, NW>), dim3((w2 + 3) / 4), dim3(256), 0, st, a));
         return hipGetLastError();
     }
     const int waves = (a.n_nodes + 31) / 32;

@@ -1824,6 +1824,126 @@ __global__ void k_bce_final_w(BceArgs a) {
     bce_store_out3_w(a, (float)(ls / (double)bce_norm(a)), (float)cs, (float)ns);
 }
 
+// ------------------------------------------------------------------------------------------------
+// spwgnn_bce_steps: the loss of all S per-step logit rows [S][n] against one target
+// row. Row s is bce_block's (W = false) or bce_block_w's (W = true) arithmetic on row s — the same
+// expressions in the same order, the same 256-wide tree — so out3s[s] and, before the step weight,
+// dlogits[s] carry the one-row kernels' bits. dlogits[s][i] = λ_s ≠ 0 ? λ_s·d : +0: a select, so a NaN
+// logit under a zero step weight stays out (as a zero node weight does in bce_dlogit_w), and 1.0f·d = d.
+// The combined row is {Σ_{λ_s ≠ 0} λ_s·loss_s summed in double in step order, correct_{S−1}, n_{S−1}}:
+// with λ = e_{S−1} it is 0.0 + 1.0·loss_{S−1} = the one-row loss's bits. No atomics anywhere.
+// One thread block's sums of row s over its share of the nodes; thread 0 returns them in red[3].
+template <bool W>
+__device__ __forceinline__ void bce_steps_block(const BceStepsArgs& a, int s, int blk, float lam, float norm,
+                                                float (&red)[3]) {
+    __shared__ float sl[256], sc[256], sn[256];
+    const BceArgs& b = a.b;
+    const float* const z_row = b.logits + (int64_t)s * b.n;
+    float* const d_row = b.dlogits ? b.dlogits + (int64_t)s * b.n : nullptr;
+    float ls = 0.f, cs = 0.f, ns = 0.f;
+    const float inv_n = 1.0f / (float)norm;
+    for (int64_t i = (int64_t)blk * 256 + threadIdx.x; i < b.n; i += (int64_t)b.blocks * 256) {
+        const float z0 = z_row[i], t = b.targets[i];
+        const float z = fminf(fmaxf(z0, -kLogitClip), kLogitClip);
+        const float l = fmaxf(z, 0.f) - z * t + log1pf(expf(-fabsf(z)));
+        const float p = 1.f / (1.f + expf(-z0));
+        float d;
+        if constexpr (W) {
+            const float w = b.w[i];
+            const bool on = w != 0.f;
+            ls += on ? w * l : 0.f;
+            cs += (on && (p > 0.5f ? 1.f : 0.f) == t) ? 1.f : 0.f;
+            ns += on ? 1.f : 0.f;
+            d = bce_dlogit_w(z0, t, w, inv_n);
+        } else {
+            ls += l;
+            cs += ((p > 0.5f ? 1.f : 0.f) == t) ? 1.f : 0.f;
+            d = bce_dlogit(z0, t, inv_n);
+        }
+        if (d_row) d_row[i] = lam != 0.f ? lam * d : 0.f;
+    }
+    sl[threadIdx.x] = ls;
+    sc[threadIdx.x] = cs;
+    sn[threadIdx.x] = ns;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            sl[threadIdx.x] += sl[threadIdx.x + o];
+            sc[threadIdx.x] += sc[threadIdx.x + o];
+            sn[threadIdx.x] += sn[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    red[0] = sl[0];
+    red[1] = sc[0];
+    red[2] = sn[0];
+    __syncthreads();   // the next row of this block reuses the arrays
+}
+// Thread 0 only: row s's out3 from its sums (k_bce_final / k_bce_final_w's expressions), its share of the
+// combined loss into `comb`, and the combined row after the last step.
+template <bool W>
+__device__ __forceinline__ void bce_steps_store(const BceStepsArgs& a, int s, float lam, float norm, double ls,
+                                                double cs, double ns, double& comb) {
+    const BceArgs& b = a.b;
+    const double div = W ? (double)norm : (double)b.n;   // the weighted divisor is a float, the plain one n itself
+    const float o[3] = {(float)(ls / div), (float)cs, W ? (float)ns : (float)b.n};
+    for (int k = 0; k < 3; ++k) {
+        a.out3s[3 * s + k] = o[k];
+        if (a.tot3s) a.tot3s[3 * s + k] += (double)o[k] * b.w3[k];
+    }
+    if (lam != 0.f) comb += (double)lam * (double)o[0];
+    if (s == a.S - 1) {
+        const float c[3] = {(float)comb, o[1], o[2]};
+        for (int k = 0; k < 3; ++k) {
+            b.out3[k] = c[k];
+            if (b.tot3) b.tot3[k] += (double)c[k] * b.w3[k];
+        }
+    }
+}
+// b.blocks == 1 (n ≤ 256, the reference's batch 32): one workgroup walks the S rows and finishes
+template <bool W>
+__global__ __launch_bounds__(256) void k_bce_steps_one(BceStepsArgs a) {
+    const float norm = W ? bce_norm(a.b) : (float)a.b.n;
+    double comb = 0.0;
+    for (int s = 0; s < a.S; ++s) {
+        const float lam = a.lambda[s];
+        float red[3];
+        bce_steps_block<W>(a, s, 0, lam, norm, red);
+        if (threadIdx.x == 0)
+            bce_steps_store<W>(a, s, lam, W ? norm : 0.f, (double)red[0], (double)red[1], (double)red[2], comb);
+    }
+}
+// larger n: grid (blocks, S) of partial sums, then one thread adds each row's partials in block order
+template <bool W>
+__global__ __launch_bounds__(256) void k_bce_steps_partial(BceStepsArgs a) {
+    const int s = blockIdx.y;
+    const float norm = W ? bce_norm(a.b) : (float)a.b.n;
+    float red[3];
+    bce_steps_block<W>(a, s, blockIdx.x, a.lambda[s], norm, red);
+    if (threadIdx.x == 0) {
+        float* q = a.b.partial + ((int64_t)s * a.b.blocks + blockIdx.x) * 3;
+        q[0] = red[0];
+        q[1] = red[1];
+        q[2] = red[2];
+    }
+}
+template <bool W>
+__global__ void k_bce_steps_final(BceStepsArgs a) {
+    if (threadIdx.x != 0) return;
+    const float norm = W ? bce_norm(a.b) : 0.f;
+    double comb = 0.0;
+    for (int s = 0; s < a.S; ++s) {
+        double ls = 0.0, cs = 0.0, ns = 0.0;
+        const float* q = a.b.partial + (int64_t)s * a.b.blocks * 3;
+        for (int k = 0; k < a.b.blocks; ++k) {
+            ls += q[3 * k];
+            cs += q[3 * k + 1];
+            ns += q[3 * k + 2];
+        }
+        bce_steps_store<W>(a, s, a.lambda[s], norm, ls, cs, ns, comb);
+    }
+}
+
 __global__ void k_adam(AdamArgs a) {
     // replayable steps: the step count lives on the device; lr_t comes from the host-built table
     // (spwgnn_adam_lr_table: the same expression spwgnn_adam evaluates, so both paths agree bitwise)
@@ -2313,6 +2433,23 @@ hipError_t launch_bce(const BceArgs& a, hipStream_t st) {
     }
     hipLaunchKernelGGL(k_bce_partial<false>, dim3(a.blocks), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_bce_final, dim3(1), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_bce_steps(const BceStepsArgs& a, hipStream_t st) {
+    if (a.S < 1 || a.S > kMaxSteps || a.b.blocks < 1) return hipErrorInvalidValue;
+    if (a.b.blocks == 1) {
+        if (a.b.w) hipLaunchKernelGGL(k_bce_steps_one<true>, dim3(1), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_bce_steps_one<false>, dim3(1), dim3(256), 0, st, a);
+        return hipGetLastError();
+    }
+    const dim3 g(a.b.blocks, a.S);
+    if (a.b.w) {
+        hipLaunchKernelGGL(k_bce_steps_partial<true>, g, dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_bce_steps_final<true>, dim3(1), dim3(64), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(k_bce_steps_partial<false>, g, dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_bce_steps_final<false>, dim3(1), dim3(64), 0, st, a);
+    }
     return hipGetLastError();
 }
 hipError_t launch_adam(const AdamArgs& a, hipStream_t st) {

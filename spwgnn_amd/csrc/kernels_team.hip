@@ -691,7 +691,8 @@ __device__ __forceinline__ void node_bwd_team_body(const NodeBwdArgs& a, const T
         // the residual path: dP_s gets dpre directly (Add()([prop_layer(x), prop]))
         R.store<kKhN>(a.dPout, D, T);
         dP = D;
-        if (a.first && T == 3 && h == 1) {   // x' row 100 = logit
+        if (a.dlogits && T == 3 && h == 1) {   // x' row 100 = logit: the last step's cotangent, or every step's own
+            // (a.bce_logits only on the last step: the fused loop's inline loss is spwgnn_bce_backward's)
             if (a.bce_logits) {   // spwgnn_bce_backward: dL/dz here (spwgnn_bce's bits), also stored
                 const float dl = valid ? bce_dlogit(a.bce_logits[R.n], a.bce_targets[R.n], 1.0f / (float)a.bce_n) : 0.f;
                 if (valid) a.bce_dlogits[R.n] = dl;
@@ -1048,7 +1049,10 @@ __device__ __forceinline__ void opaque(T*& p) {
     asm volatile("" : "+s"(g));
     p = (T*)g;
 }
-template <bool TRAIN, Np NPT, bool AB16>
+// STEPS (spwgnn_forward_steps, §3zr): every step stores its logit row, step s at logits + s·logit_step.
+// A template parameter, like the backward's: the loops are at their register limit and sensitive to
+// what the step prologue computes (§3zl), so spwgnn_forward keeps the instantiations it had
+template <bool TRAIN, Np NPT, bool AB16, bool STEPS = false>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_fwd_fused_team(FwdFusedArgs a) {
     constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     __shared__ uint4 act_s[kTeamLdsU4<NP>];
@@ -1095,7 +1099,8 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_fwd_fused_team(FwdFusedArgs 
         if (nf.o1_out) nf.o1_out += (int64_t)s * a.rowsN;
         nf.cw_out = s == 0 ? a.nf.cw_out : nullptr;
         nf.cw_in = s > 0 ? a.nf.cw_out : nullptr;
-        nf.logits = s == a.S - 1 ? a.logits : nullptr;
+        if constexpr (STEPS) nf.logits = a.logits + s * a.logit_step;
+        else nf.logits = s == a.S - 1 ? a.logits : nullptr;
         const int64_t sE1 = (int64_t)(a.training ? s + 1 : 0) * a.rowsE;
         nf.U = s + 1 < a.S ? const_cast<float*>(a.ef.U) + sE1 : nullptr;   // the same workspace arrays
         nf.V = s + 1 < a.S ? const_cast<float*>(a.ef.V) + sE1 : nullptr;
@@ -1318,7 +1323,8 @@ static_assert(sizeof(uint4) * kTeamLdsU4<3> + sizeof(float) * kTeamDaBlocks * 5 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "libspwgnn_hip targets gfx950 (160 KiB LDS per CU): the fused small-batch backward needs it"
 #endif
-template <int NP, bool B16>
+// STEPS (spwgnn_backward_steps, §3zr): step s reads its own cotangent row nb.dlogits + s·dl_step
+template <int NP, bool B16, bool STEPS = false>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_bwd_fused_team(BwdFusedArgs a) {
     __shared__ uint4 act_s[kTeamLdsU4<NP>];
     __shared__ float dacc_s[kTeamDaBlocks * 5 * 16 * 64];   // 80 KiB: dA of ≤ 4 blocks across the steps
@@ -1338,6 +1344,8 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_bwd_fused_team(BwdFusedArgs 
         opaque(nb.x_wo1at);
         opaque(nb.x_w3t);
         nb.first = first;
+        if constexpr (STEPS) nb.dlogits = a.nb.dlogits + s * a.dl_step;
+        else nb.dlogits = first ? a.nb.dlogits : nullptr;   // read wherever it is set (node_bwd_team_body)
         nb.seeded = first && a.nb.seeded;   // the host's flag is step S−1's (§3zo)
         nb.dPin = first && !a.nb.seeded ? nullptr : dP0 + ((s + 1) & 1) * a.rowsN;
         nb.dU = first ? nullptr : a.nb.dU + sE;   // the host passes dU_at(1) / dV_at(1)
@@ -1518,6 +1526,20 @@ hipError_t launch_fwd_fused_team(const FwdFusedArgs& a, int math, bool train, hi
         a.nf.uv16 == kUvB16 || a.ef.uv16 == kUvB16)
         return hipErrorInvalidValue;
     const dim3 g(a.ef.n_wtiles), b(64 * kTeamEdge);
+    if (a.logit_step) {   // per-step logit rows: the STEPS instantiations
+        if (math == MATH_BF16) {
+            if (train && a.ee.b16) hipLaunchKernelGGL((k_fwd_fused_team<true, 1, true, true>), g, b, 0, st, a);
+            else if (train) hipLaunchKernelGGL((k_fwd_fused_team<true, 1, false, true>), g, b, 0, st, a);
+            else if (!a.ee.b16) hipLaunchKernelGGL((k_fwd_fused_team<false, 1, false, true>), g, b, 0, st, a);
+            else return hipErrorInvalidValue;
+        } else if (math_split32(math) && !a.ee.b16) {
+            if (train) SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_fwd_fused_team<true, NP, false, true>), g, b, 0, st, a));
+            else SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_fwd_fused_team<false, NP, false, true>), g, b, 0, st, a));
+        } else {
+            return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     if (math == MATH_BF16) {
         if (train && a.ee.b16) hipLaunchKernelGGL((k_fwd_fused_team<true, 1, true>), g, b, 0, st, a);
         else if (train) hipLaunchKernelGGL((k_fwd_fused_team<true, 1, false>), g, b, 0, st, a);
@@ -1536,6 +1558,14 @@ hipError_t launch_bwd_fused_team(const BwdFusedArgs& a, int math, hipStream_t st
         !a.nb.dco_sum || a.nb.n16 || a.eb.n16 || a.da.b16 != a.eeb.b16)
         return hipErrorInvalidValue;
     const dim3 g(a.eb.n_wtiles), b(64 * kTeamEdge);
+    if (!a.nb.dlogits || (a.dl_step && a.nb.bce_logits)) return hipErrorInvalidValue;
+    if (a.dl_step) {   // per-step cotangent rows: the STEPS instantiations
+        if (math == MATH_BF16 && a.da.b16) hipLaunchKernelGGL((k_bwd_fused_team<1, true, true>), g, b, 0, st, a);
+        else if (math == MATH_BF16) hipLaunchKernelGGL((k_bwd_fused_team<1, false, true>), g, b, 0, st, a);
+        else if (math_split32(math) && !a.da.b16) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_bwd_fused_team<NP, false, true>), g, b, 0, st, a));
+        else return hipErrorInvalidValue;
+        return hipGetLastError();
+    }
     if (math == MATH_BF16 && a.da.b16) hipLaunchKernelGGL((k_bwd_fused_team<1, true>), g, b, 0, st, a);
     else if (math == MATH_BF16) hipLaunchKernelGGL((k_bwd_fused_team<1, false>), g, b, 0, st, a);
     else if (math_split32(math) && !a.da.b16) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_bwd_fused_team<NP, false>), g, b, 0, st, a));

@@ -325,6 +325,81 @@ def backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: W
     return grads, dprop
 
 
+def forward_steps(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
+                  step_logits: Optional[torch.Tensor] = None, return_state: bool = False,
+                  state: Optional[torch.Tensor] = None):
+    """`forward` with every propagation step's logits (spwgnn_forward_steps): (mp_steps, n_nodes) fp32, row
+    s = the readout after step s + 1 steps, nodes in the plan's order; the last row holds `forward`'s
+    bits. ``step_logits`` / ``state``: the buffers to write to (a captured forward's static outputs).
+    With ``return_state`` returns ``(step_logits, state)``."""
+    _require_gpu(flat_params, "params")
+    if flat_params.dtype != torch.float32 or not flat_params.is_contiguous() or flat_params.numel() != P.flat_size():
+        raise ValueError("params must be a contiguous fp32 flat buffer of spwgnn_param_count() floats")
+    buf = ws.get(workspace_bytes(batch, run))
+    shape = (int(run.mp_steps), batch.n_nodes)
+    if step_logits is None:
+        step_logits = _poison(torch.empty(shape, dtype=torch.float32, device=batch.device))
+    else:
+        _require_gpu(step_logits, "step_logits")
+        if tuple(step_logits.shape) != shape or step_logits.dtype != torch.float32 or not step_logits.is_contiguous():
+            raise ValueError(f"step_logits must be a contiguous fp32 {shape} tensor")
+    if not return_state:
+        if state is not None:
+            raise ValueError("a state buffer goes with return_state=True")
+    elif state is None:
+        state = _poison(torch.empty(batch.n_nodes, STATE_WIDTH, dtype=torch.float32, device=batch.device))
+    else:
+        _require_gpu(state, "state")
+        if tuple(state.shape) != (batch.n_nodes, STATE_WIDTH) or state.dtype != torch.float32 or not state.is_contiguous():
+            raise ValueError(f"state must be a contiguous fp32 ({batch.n_nodes}, {STATE_WIDTH}) tensor")
+    b = batch.cstruct()
+    r = run.cstruct(with_prologue=True)
+    st = _lib.lib().spwgnn_forward_steps(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
+                                         step_logits.data_ptr(), state.data_ptr() if return_state else None,
+                                         _stream(batch.device))
+    ws.fwd_key = Workspace.key(batch, run) if st == 0 else None
+    ws.fwd_batch = weakref.ref(batch) if st == 0 else None
+    ws.bwd_key = None
+    ws.has_state = bool(return_state) and st == 0
+    _lib.check(st, "spwgnn_forward_steps")
+    return (step_logits, state) if return_state else step_logits
+
+
+def backward_steps(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
+                   dstep_logits: torch.Tensor, grads: Optional[torch.Tensor] = None, want_dprop: bool = False,
+                   dstate: Optional[torch.Tensor] = None):
+    """Gradients of Σ_s Σ_i dstep_logits[s, i]·z_s[i] (+ Σ dstate·P_S) in one pass over the step loop
+    (spwgnn_backward_steps): ``dstep_logits`` is (mp_steps, n_nodes) fp32 in the plan's node order, row s
+    the cotangent of step s's logits (`forward_steps`' rows). The forward on this workspace may be any of
+    `forward` / `forward_steps`; ``dstate`` needs ``return_state=True`` there. Returns (grads, dprop)."""
+    if not run.training:
+        raise _lib.SpwgnnError("backward needs a training forward on the same workspace")
+    if dstate is not None:
+        dstate = _check_dstate(ws, batch, dstate)
+    if not ws.holds(batch, run):
+        raise _lib.SpwgnnError("backward needs the training forward of the same batch and RunConfig "
+                               f"on this workspace (stored {ws.fwd_key}, asked {Workspace.key(batch, run)})")
+    shape = (int(run.mp_steps), batch.n_nodes)
+    if not isinstance(dstep_logits, torch.Tensor) or tuple(dstep_logits.shape) != shape:
+        raise ValueError(f"dstep_logits must be a {shape} tensor: one row of logit cotangents per propagation step "
+                         f"(got {tuple(getattr(dstep_logits, 'shape', ()))})")
+    _require_gpu(dstep_logits, "dstep_logits")
+    dstep_logits = dstep_logits.to(torch.float32).contiguous()
+    if grads is None:
+        grads = _poison(torch.empty_like(flat_params))
+    dprop = _poison(torch.empty(batch.n_nodes, 100, dtype=torch.float32, device=batch.device)) if want_dprop else None
+    b = batch.cstruct()
+    r = run.cstruct()
+    buf = ws.buf
+    st = _lib.lib().spwgnn_backward_steps(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
+                                          dstep_logits.data_ptr(), dstate.data_ptr() if dstate is not None else None,
+                                          grads.data_ptr(), dprop.data_ptr() if dprop is not None else None,
+                                          _stream(batch.device))
+    ws.bwd_key = ws.fwd_key if st == 0 else None
+    _lib.check(st, "spwgnn_backward_steps")
+    return grads, dprop
+
+
 def backward_inputs(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace) -> torch.Tensor:
     """d(loss)/d(objects) of the last `backward` / `bce_backward` on this workspace (spwgnn_backward_inputs,
     ABI 8): (n_nodes, 3) fp32 — d/d(x, y, width) of the objects rows as the batch holds them (already
@@ -470,6 +545,84 @@ def bce(logits: torch.Tensor, targets: torch.Tensor, scratch: BceScratch, dlogit
         st = _lib.lib().spwgnn_bce_accumulate(*args, weights3.data_ptr(), total3.data_ptr(), _stream(logits.device))
         _lib.check(st, "spwgnn_bce_accumulate")
     return scratch.out3, dlogits
+
+
+def check_step_weights(step_loss_weights, mp_steps: int):
+    """Validates per-step loss weights λ (deep supervision): ``mp_steps`` finite floats >= 0, not all zero
+    — the rules spwgnn_bce_steps refuses by. Returns them as a tuple of floats."""
+    import math
+    lam = tuple(float(x) for x in step_loss_weights)
+    if len(lam) != int(mp_steps):
+        raise ValueError(f"step_loss_weights needs one weight per propagation step ({mp_steps}), got {len(lam)}")
+    if any(not math.isfinite(x) or x < 0.0 for x in lam):
+        raise ValueError(f"step_loss_weights must be finite and >= 0 (got {lam})")
+    if not any(x != 0.0 for x in lam):
+        raise ValueError("step_loss_weights must not be all zero")
+    return lam
+
+
+class BceStepsScratch:
+    """Device buffers of `bce_steps` for ``mp_steps`` rows: the partial sums
+    (spwgnn_bce_steps_scratch_bytes), out3 (the combined row) and out3s (mp_steps, 3)."""
+
+    def __init__(self, device, mp_steps: int):
+        n = int(_lib.lib().spwgnn_bce_steps_scratch_bytes(1, int(mp_steps)))
+        if n < 0:
+            raise ValueError(f"mp_steps must be in 1..{_lib.MAX_STEPS} (got {mp_steps})")
+        self.mp_steps = int(mp_steps)
+        self.scratch = torch.empty(n, dtype=torch.uint8, device=device)
+        self.out3 = torch.empty(3, dtype=torch.float32, device=device)
+        self.out3s = torch.empty(self.mp_steps, 3, dtype=torch.float32, device=device)
+
+
+def bce_steps(step_logits: torch.Tensor, targets: torch.Tensor, step_weights, scratch: BceStepsScratch,
+              dlogits: Optional[torch.Tensor] = None, total3: Optional[torch.Tensor] = None,
+              weights3: Optional[torch.Tensor] = None, total3s: Optional[torch.Tensor] = None,
+              node_weights: Optional[torch.Tensor] = None, norm=None):
+    """The deep-supervision loss Σ_s λ_s·BCE(z_s, t) over the rows of `forward_steps` in one launch
+    (spwgnn_bce_steps). ``step_weights``: mp_steps floats λ_s >= 0, not all zero. Returns
+    ``(out3, out3s, dlogits)``: out3 = [Σ_s λ_s·loss_s, correct of the last step, n]; out3s (mp_steps, 3) =
+    each step's [loss, correct, n] as `bce` computes them; dlogits (mp_steps, n), row s = λ_s · `bce`'s
+    dlogits of row s (+0 where λ_s = 0, whatever the row holds) — what `backward_steps` takes. With
+    λ = (0, …, 0, 1) out3 and the last dlogits row are `bce`'s bits. ``node_weights`` / ``norm`` as in `bce`;
+    ``total3`` / ``weights3`` accumulate out3, ``total3s`` ((mp_steps, 3) float64, with them) out3s."""
+    _require_gpu(step_logits, "step_logits")
+    if step_logits.dim() != 2 or step_logits.dtype != torch.float32 or not step_logits.is_contiguous():
+        raise ValueError("step_logits must be a contiguous fp32 (mp_steps, n) tensor")
+    S, n = int(step_logits.shape[0]), int(step_logits.shape[1])
+    if S != scratch.mp_steps:
+        raise ValueError(f"the scratch was built for {scratch.mp_steps} steps, step_logits holds {S}")
+    sw = _lib.StepWeightsC()
+    lam = [float(x) for x in step_weights]
+    sw.count = len(lam)
+    for s, x in enumerate(lam[:_lib.MAX_STEPS]):
+        sw.lam[s] = x
+    targets = targets.reshape(-1).to(torch.float32).contiguous()
+    if targets.numel() != n:
+        raise ValueError(f"targets must hold one value per node ({n}), got {targets.numel()}")
+    if dlogits is None:
+        dlogits = _poison(torch.empty_like(step_logits))
+    elif tuple(dlogits.shape) != (S, n) or dlogits.dtype != torch.float32 or not dlogits.is_contiguous():
+        raise ValueError(f"dlogits must be a contiguous fp32 ({S}, {n}) tensor")
+    if (total3 is None) != (weights3 is None):
+        raise ValueError("total3 and weights3 go together")
+    if total3s is not None and total3 is None:
+        raise ValueError("total3s goes with total3 and weights3")
+    for t, shp in ((total3, (3,)), (weights3, (3,)), (total3s, (S, 3))):
+        if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != shp or not t.is_contiguous()):
+            raise ValueError(f"the epoch sums are contiguous float64 tensors of shape {shp}")
+    lw, _keep = (None, None)
+    if node_weights is not None:
+        lw, _keep = _loss_weights(node_weights, norm, step_logits[0])
+    elif norm is not None:
+        raise ValueError("norm goes with node_weights")
+    st = _lib.lib().spwgnn_bce_steps(
+        step_logits.data_ptr(), targets.data_ptr(), n, S, C.byref(sw), C.byref(lw) if lw is not None else None,
+        scratch.out3s.data_ptr(), scratch.out3.data_ptr(), dlogits.data_ptr(), scratch.scratch.data_ptr(),
+        weights3.data_ptr() if weights3 is not None else None, total3.data_ptr() if total3 is not None else None,
+        total3s.data_ptr() if total3s is not None else None, _stream(step_logits.device))
+    _lib.check(st, "spwgnn_bce_steps")
+    return scratch.out3, scratch.out3s, dlogits
 
 
 def adam(params: torch.Tensor, grads: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr=5e-4,

@@ -110,7 +110,7 @@ class KerasModel:
 
     def __init__(self, net: GraphNetwork, n_objects: int, object_dim: int = 3, lr: float = 5e-4,
                  l2: float = 0.0, clipnorm: float = 0.0, clipvalue: float = 0.0, decay: float = 0.0,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, step_loss_weights=None):
         if object_dim != 3:
             # Networks.py:70-73 + main.py:28-31/59-63: the object_dim=2 path of the reference is
             # broken (om gets 1 feature, boxes[...,2] is out of range); only the Jenga layout runs.
@@ -126,6 +126,13 @@ class KerasModel:
         self.skip_nonfinite = bool(skip_nonfinite)
         self._clip: Optional[E.ClipScratch] = None
         dev = net.device
+        # deep supervision: None (the reference's loss on the last step, exactly the launches of before) or
+        # mp_steps weights λ_s >= 0, not all zero — every step then trains on Σ_s λ_s·BCE(z_s, y)
+        # (engine.forward_steps / bce_steps / backward_steps)
+        self.step_loss_weights = None if step_loss_weights is None else \
+            E.check_step_weights(step_loss_weights, net.mp_steps)
+        self._bce_steps = None if step_loss_weights is None else E.BceStepsScratch(dev, net.mp_steps)
+        self._tot_s = None if step_loss_weights is None else torch.zeros(net.mp_steps, 3, dtype=torch.float64, device=dev)
         self.m = torch.zeros_like(net.flat.data)
         self.v = torch.zeros_like(net.flat.data)
         self.iterations = 0
@@ -141,10 +148,13 @@ class KerasModel:
         self._w3: Dict[int, torch.Tensor] = {}
 
     # ---------------------------------------------------------------- inference
-    def predict(self, x: Dict[str, np.ndarray], batch_size: int = 32768) -> np.ndarray:
+    def predict(self, x: Dict[str, np.ndarray], batch_size: int = 32768, return_steps: bool = False) -> np.ndarray:
+        """(B, N, 1) probabilities; ``return_steps``: (B, N, S), the probabilities read out after each of
+        the S propagation steps (the last column is the plain prediction)."""
         objects = np.asarray(x["objects"], np.float32)
         B, N = objects.shape[:2]
-        out = np.zeros((B, N, 1), np.float32)
+        S = self.net.mp_steps
+        out = np.zeros((B, N, S if return_steps else 1), np.float32)
         run = self.net.run_config()
         for b0 in range(0, B, batch_size):
             sl = slice(b0, min(B, b0 + batch_size))
@@ -153,6 +163,10 @@ class KerasModel:
                                           np.asarray(x["receiver_relations"])[sl],
                                           None if prop is None else np.asarray(prop)[sl], device=self.net.device)
             with torch.no_grad():
+                if return_steps:
+                    z = E.forward_steps(self.net.flat.detach(), batch, run, self._ws)
+                    out[sl] = E.sigmoid(z.reshape(-1)).reshape(S, -1, N).permute(1, 2, 0).cpu().numpy()
+                    continue
                 z = E.forward(self.net.flat.detach(), batch, run, self._ws)
                 p = E.sigmoid(z)
             out[sl, :, 0] = p.reshape(-1, N).cpu().numpy()
@@ -162,13 +176,20 @@ class KerasModel:
     def train_on_batch(self, batch: TowerBatch, target: torch.Tensor, node_weights=None):
         """One Keras step: forward (dropout on), BCE, backward, Adam. Returns out3 = [loss, correct, n]
         (device). `node_weights` (one per node, in the targets' order): the weighted loss of engine.bce
-        with the divisor max(#non-zero weights, 1) (one host sync to count them)."""
+        with the divisor max(#non-zero weights, 1) (one host sync to count them). With step_loss_weights
+        out3 = [Σ_s λ_s·loss_s, the last step's correct, n] and `step_out3` holds the (S, 3) per-step rows."""
         net = self.net
         net._step_seed += 1
         run = net.run_config(True, dropout=net.dropout, seed=net._step_seed)
-        z = E.forward(net.flat.data, batch, run, self._ws)
-        out3, dz = E.bce(z, target, self._bce, node_weights=self._dev_weights(node_weights))
-        E.backward(net.flat.data, batch, run, self._ws, dz, grads=self._grads)
+        if self.step_loss_weights is not None:
+            z = E.forward_steps(net.flat.data, batch, run, self._ws)
+            out3, self.step_out3, dz = E.bce_steps(z, target, self.step_loss_weights, self._bce_steps,
+                                                   node_weights=self._dev_weights(node_weights))
+            E.backward_steps(net.flat.data, batch, run, self._ws, dz, grads=self._grads)
+        else:
+            z = E.forward(net.flat.data, batch, run, self._ws)
+            out3, dz = E.bce(z, target, self._bce, node_weights=self._dev_weights(node_weights))
+            E.backward(net.flat.data, batch, run, self._ws, dz, grads=self._grads)
         self.iterations += 1
         if not self._clip_on():
             E.adam(net.flat.data, self._grads, self.m, self.v, self.iterations, self.lr, self.beta1, self.beta2,
@@ -204,6 +225,8 @@ class KerasModel:
         read from the device, and the epoch sums accumulated on the device."""
         net, ctr = self.net, self._ctr
         clip = self._clip_scratch() if self._clip_on() else None
+        lam = self.step_loss_weights
+        sbuf = {}   # deep supervision: this geometry's (S, n) rows and loss scratch, made by its first (eager) run
 
         def body(batch, target, ws, bce, z, dz, pre=None, weights=None, norm=None):
             w3 = self._w3[batch.n_towers]        # created before the first (eager) run of a geometry
@@ -215,12 +238,24 @@ class KerasModel:
             else:
                 E.step_advance(ctr.key, ctr.step, _lib.STEP_KEY_COUNTER)
             run = net.run_config(True, dropout=net.dropout, seed_dev=ctr.key, prologue=pro)
-            E.forward(net.flat.data, batch, run, ws, logits=z)
-            # loss + epoch sums and the backward in one call: on the fused small-batch loop the loss
-            # needs no launch of its own (spwgnn_bce_backward); weights / norm: a weighted fit's per-node
-            # loss weights and their divisor, views of the step's static buffer
-            E.bce_backward(net.flat.data, batch, run, ws, z, target, bce, dlogits=dz, total3=self._tot, weights3=w3,
-                           grads=self._grads, node_weights=weights, norm=norm)
+            if lam is not None:
+                # every step's logits, the step-weighted loss with the epoch sums (combined and per step) in
+                # its own launch, and one backward over the step loop with each step's cotangent row
+                if not sbuf:
+                    sbuf["z"] = torch.empty(net.mp_steps, batch.n_nodes, dtype=torch.float32, device=z.device)
+                    sbuf["dz"] = torch.empty_like(sbuf["z"])
+                    sbuf["bce"] = E.BceStepsScratch(z.device, net.mp_steps)
+                E.forward_steps(net.flat.data, batch, run, ws, step_logits=sbuf["z"])
+                E.bce_steps(sbuf["z"], target, lam, sbuf["bce"], dlogits=sbuf["dz"], total3=self._tot, weights3=w3,
+                            total3s=self._tot_s, node_weights=weights, norm=norm)
+                E.backward_steps(net.flat.data, batch, run, ws, sbuf["dz"], grads=self._grads)
+            else:
+                E.forward(net.flat.data, batch, run, ws, logits=z)
+                # loss + epoch sums and the backward in one call: on the fused small-batch loop the loss
+                # needs no launch of its own (spwgnn_bce_backward); weights / norm: a weighted fit's per-node
+                # loss weights and their divisor, views of the step's static buffer
+                E.bce_backward(net.flat.data, batch, run, ws, z, target, bce, dlogits=dz, total3=self._tot,
+                               weights3=w3, grads=self._grads, node_weights=weights, norm=norm)
             if clip is None:
                 E.adam_dev(net.flat.data, self._grads, self.m, self.v, ctr.step, ctr.lr_table, self.beta1, self.beta2,
                            self.eps, self.l2)
@@ -234,6 +269,11 @@ class KerasModel:
         """out3 = [loss, correct, n] of an inference forward; `node_weights` / `norm` as engine.bce takes
         them (norm None: the non-zero weights are counted, one host sync)."""
         run = self.net.run_config()
+        if self.step_loss_weights is not None:   # [Σ_s λ_s·loss_s, the last step's correct, n]
+            z = E.forward_steps(self.net.flat.data, batch, run, self._ws)
+            out3, self.step_out3, _ = E.bce_steps(z, target, self.step_loss_weights, self._bce_steps,
+                                                  node_weights=self._dev_weights(node_weights), norm=norm)
+            return out3
         z = E.forward(self.net.flat.data, batch, run, self._ws)
         out3, _ = E.bce(z, target, self._bce, node_weights=self._dev_weights(node_weights), norm=norm)
         return out3
@@ -259,7 +299,11 @@ class KerasModel:
 
         With clipnorm, clipvalue, decay or skip_nonfinite set on the model the history gains, per epoch,
         `grad_norm` (the mean global gradient norm over the epoch's non-skipped steps), `clipped_steps` and
-        `skipped_steps`, from one fp64 device accumulator read where the loss sums are read."""
+        `skipped_steps`, from one fp64 device accumulator read where the loss sums are read.
+
+        With step_loss_weights set on the model `loss` / `val_loss` are Σ_s λ_s·loss_s, `binary_accuracy` stays
+        the last step's, and the history gains `step_loss` and `step_binary_accuracy`: per epoch a list of S
+        values, each step's own loss and accuracy, summed on the device in the loss launch."""
         objects = np.asarray(x["objects"], np.float32)
         target = np.asarray(y["target"], np.float32).reshape(objects.shape[0], -1)
         B = objects.shape[0]
@@ -275,6 +319,9 @@ class KerasModel:
         if clip_on:
             hist.update({"grad_norm": [], "clipped_steps": [], "skipped_steps": []})
             clip = self._clip_scratch()
+        lam = self.step_loss_weights
+        if lam is not None:
+            hist.update({"step_loss": [], "step_binary_accuracy": []})
         if n_val:
             hist.update({"val_loss": [], "val_binary_accuracy": []})
             vbatch = ds.subset(np.arange(n_tr, B), dev)
@@ -291,6 +338,8 @@ class KerasModel:
                           beta2=self.beta2, decay=self.decay)
         # the clip options are baked into a geometry's launches (and its captured graph)
         opts = (graph, weighted, self.clipnorm, self.clipvalue, self.skip_nonfinite, clip_on)
+        if lam is not None:
+            opts += (lam,)
         if self._replays is None or self._replay_graph != opts:
             self._replays = ReplayCache(dev, self._replay_body, graph=graph, weighted=weighted)
             self._replay_graph = opts
@@ -300,11 +349,16 @@ class KerasModel:
         ep_tot = torch.zeros(epochs, 3, dtype=torch.float64, device=dev)
         ep_val = torch.zeros(epochs, 3, dtype=torch.float32, device=dev)
         ep_clip = torch.zeros(epochs, 4, dtype=torch.float64, device=dev) if clip_on else None
+        ep_steps = torch.zeros(epochs, len(lam), 3, dtype=torch.float64, device=dev) if lam is not None else None
 
         def record(ep):
             tot_l, tot_c, tot_n = ep_tot[ep].tolist()
             hist["loss"].append(tot_l / max(n_tr, 1))
             hist["binary_accuracy"].append(tot_c / max(tot_n, 1))
+            if lam is not None:
+                rows = ep_steps[ep].tolist()
+                hist["step_loss"].append([r[0] / max(n_tr, 1) for r in rows])
+                hist["step_binary_accuracy"].append([r[1] / max(r[2], 1) for r in rows])
             if clip_on:
                 c_norm, c_clipped, c_skipped, c_steps = ep_clip[ep].tolist()
                 hist["grad_norm"].append(c_norm / max(c_steps - c_skipped, 1.0))
@@ -320,6 +374,8 @@ class KerasModel:
             # (Σ loss·batch, Σ correct, Σ nodes) on the device: no host sync per batch, so the host
             # builds the next batch while the GPU runs this one
             self._tot.zero_()
+            if lam is not None:
+                self._tot_s.zero_()
             if clip_on:
                 clip.total4.zero_()
             for b0 in range(0, n_tr, batch_size):
@@ -330,6 +386,8 @@ class KerasModel:
                 self.net._step_seed += 1
                 self.iterations += 1
             ep_tot[ep].copy_(self._tot)
+            if lam is not None:
+                ep_steps[ep].copy_(self._tot_s)
             if clip_on:
                 ep_clip[ep].copy_(clip.total4)
             if n_val:
@@ -365,10 +423,13 @@ class PropagationNetwork:
 
     def __init__(self, device="cuda", seed: int = 0, mp_steps: int = E.REF_MP_STEPS, dropout: float = E.REF_DROPOUT,
                  math: str = "x6", clipnorm: float = 0.0, clipvalue: float = 0.0, decay: float = 0.0,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, step_loss_weights=None):
         # Networks.py:101 Adam(lr=0.0005, decay=0.0); clipnorm / clipvalue are Keras 2.x Optimizer kwargs
         E.check_clip_options(clipnorm, clipvalue, decay)
-        self._opt = dict(clipnorm=clipnorm, clipvalue=clipvalue, decay=decay, skip_nonfinite=skip_nonfinite)
+        if step_loss_weights is not None:   # deep supervision (KerasModel): one weight per propagation step
+            step_loss_weights = E.check_step_weights(step_loss_weights, mp_steps)
+        self._opt = dict(clipnorm=clipnorm, clipvalue=clipvalue, decay=decay, skip_nonfinite=skip_nonfinite,
+                         step_loss_weights=step_loss_weights)
         if math not in E.MATH_MODES:
             raise ValueError(f"math must be one of {sorted(E.MATH_MODES)}")
         self._math = math   # every model's arithmetic (GraphNetwork.math); "x6": the fp32-class default

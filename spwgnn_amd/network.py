@@ -21,17 +21,22 @@ class _PropagationFn(torch.autograd.Function):
     """Forward/backward of the whole graph through the C-ABI; gradients w.r.t. the flat parameter
     buffer, the propagation input and the objects (the (n_nodes, 3) rows in the plan's node order;
     the relation set is a constant of the graph and is not differentiated). With ``want_state`` a second
-    output, the final state (n_nodes, 100), whose gradient enters the same backward pass as ``dstate``."""
+    output, the final state (n_nodes, 100), whose gradient enters the same backward pass as ``dstate``.
+    With ``want_steps`` the first output is every step's logits (mp_steps, n_nodes) (`engine.forward_steps`)
+    and its gradient goes back through `engine.backward_steps`, still one pass over the step loop."""
 
     @staticmethod
     def forward(ctx, flat, prop_dummy, obj_dummy, batch: TowerBatch, run: E.RunConfig, ws: E.Workspace,
-                want_state: bool = False):
+                want_state: bool = False, want_steps: bool = False):
         ctx.batch, ctx.run, ctx.ws = batch, run, ws
         ctx.save_for_backward(flat)
         ctx.want_prop = prop_dummy.requires_grad
         ctx.want_obj = obj_dummy.requires_grad
         ctx.want_state = want_state
+        ctx.want_steps = want_steps
         ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None, not as zeros
+        if want_steps:
+            return E.forward_steps(flat, batch, run, ws, return_state=want_state)
         if want_state:
             return E.forward(flat, batch, run, ws, return_state=True)
         return E.forward(flat, batch, run, ws)
@@ -39,15 +44,24 @@ class _PropagationFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits, dstate=None):
         (flat,) = ctx.saved_tensors
+        if dstate is not None:
+            dstate = dstate.to(torch.float32).contiguous()
+        if ctx.want_steps:
+            if dlogits is None:
+                dlogits = torch.zeros(ctx.run.mp_steps, ctx.batch.n_nodes, dtype=torch.float32, device=flat.device)
+            grads, dprop = E.backward_steps(flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop,
+                                            dstate=dstate)
+            dobj = E.backward_inputs(flat, ctx.batch, ctx.run, ctx.ws) if ctx.want_obj else None
+            return grads, dprop, dobj, None, None, None, None, None
         if dlogits is None:   # a loss on the state alone: the library still takes a dlogits array
             dlogits = torch.zeros(ctx.batch.n_nodes, dtype=torch.float32, device=flat.device)
         if dstate is None:    # no loss on the state: the plain backward
             grads, dprop = E.backward(flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop)
         else:
             grads, dprop = E.backward(flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop,
-                                      dstate=dstate.to(torch.float32).contiguous())
+                                      dstate=dstate)
         dobj = E.backward_inputs(flat, ctx.batch, ctx.run, ctx.ws) if ctx.want_obj else None
-        return grads, dprop, dobj, None, None, None, None
+        return grads, dprop, dobj, None, None, None, None, None
 
 
 class GraphNetwork(nn.Module):
@@ -97,8 +111,15 @@ class GraphNetwork(nn.Module):
                            math=self.math)
 
     def forward_batch(self, batch: TowerBatch, prop: Optional[torch.Tensor] = None,
-                      objects: Optional[torch.Tensor] = None, return_state: bool = False):
+                      objects: Optional[torch.Tensor] = None, return_state: bool = False, return_steps: bool = False):
         """Logits (n_nodes,) for a compact batch (the reference returns sigmoid of these).
+
+        ``return_steps``: instead of the last step's logits, every step's, (mp_steps, n_nodes) — row s is
+        the readout after s + 1 propagation steps (the network's column 0 at that step, Networks.py:89-94),
+        the last row the logits this call returns otherwise, bit for bit. The rows are in the INPUT's node
+        order (a packed plan's rows are put back with `TowerBatch.to_input_order`; every other plan keeps
+        the input's order anyway). Differentiable in the weights, ``prop`` and ``objects`` like the logits:
+        a loss Σ_s λ_s·L(z_s) — deep supervision — takes one backward pass. Combines with ``return_state``.
 
         ``return_state``: return ``(logits, state)`` — state (n_nodes, 100) is the propagation state after
         the last step, P_S = tanh(x[:, 1:] + P_{S-1}) (Networks.py:91), in the plan's node order like the
@@ -128,6 +149,16 @@ class GraphNetwork(nn.Module):
             odummy = batch.to_plan_order(objects.reshape(batch.n_nodes, 3).to(self.device, torch.float32))
         else:
             odummy = dummy.new_zeros(0)
+        if return_steps:
+            if not run.training:
+                with torch.no_grad():
+                    out = E.forward_steps(self.flat.detach(), batch, run, ws, return_state=return_state)
+            else:
+                out = _PropagationFn.apply(self.flat, dummy, odummy, batch, run, ws, return_state, True)
+            steps = out[0] if return_state else out
+            if batch.node_perm is not None:   # rows of a packed plan back in the input's node order
+                steps = batch.to_input_order(steps.t()).t()
+            return (steps, out[1]) if return_state else steps
         if not run.training:
             with torch.no_grad():
                 return E.forward(self.flat.detach(), batch, run, ws, return_state=return_state)
@@ -165,8 +196,9 @@ class GraphNetwork(nn.Module):
         return TowerBatch.from_dense_device(objects, sender_relations, receiver_relations, propagation)
 
     def forward_logits(self, objects, sender_relations, receiver_relations, propagation=None,
-                       plan: str = "host", return_state: bool = False):
-        """(B, N) logits; with ``return_state`` ``(logits, state)``, state (B, N, 100) (see `forward_batch`). A torch ``objects`` that requires grad receives d/d objects (B, N, 3) on
+                       plan: str = "host", return_state: bool = False, return_steps: bool = False):
+        """``return_steps``: (S, B, N) — every step's logits (see `forward_batch`) in place of the last step's.
+        (B, N) logits; with ``return_state`` ``(logits, state)``, state (B, N, 100) (see `forward_batch`). A torch ``objects`` that requires grad receives d/d objects (B, N, 3) on
         backward (see `forward_batch`; the relations are constants).
         ``plan``: "host" converts the relation matrices on the host (`TowerBatch.from_dense`: a copy to
         the host, a C++ scan, an upload); "device" needs all inputs on the device and converts them there
@@ -178,18 +210,21 @@ class GraphNetwork(nn.Module):
         if propagation is not None:
             prop = torch.as_tensor(propagation, dtype=torch.float32, device=self.device).reshape(batch.n_nodes, 100)
         z = self.forward_batch(batch, prop, objects if isinstance(objects, torch.Tensor) else None,
-                               return_state=return_state)
+                               return_state=return_state, return_steps=return_steps)
+        shape = (self.mp_steps, *batch.node_shape) if return_steps else batch.node_shape
         if return_state:
             z, state = z
-            return z.reshape(batch.node_shape), state.reshape(*batch.node_shape, E.STATE_WIDTH)
-        return z.reshape(batch.node_shape)
+            return z.reshape(shape), state.reshape(*batch.node_shape, E.STATE_WIDTH)
+        return z.reshape(shape)
 
     def forward(self, objects, sender_relations, receiver_relations, propagation=None, plan: str = "host",
-                return_state: bool = False):
+                return_state: bool = False, return_steps: bool = False):
         """(B, N, 1) probabilities: sigmoid(x[:, :, :1]) of the last step (Networks.py:93-96);
         differentiable in a torch ``objects`` like `forward_logits` (``plan`` as there). With
-        ``return_state`` ``(probabilities, state)``, state (B, N, 100)."""
-        z = self.forward_logits(objects, sender_relations, receiver_relations, propagation, plan, return_state)
+        ``return_state`` ``(probabilities, state)``, state (B, N, 100). With ``return_steps`` the
+        probabilities of every step, (S, B, N, 1): how the predicted stabilities settle over the steps."""
+        z = self.forward_logits(objects, sender_relations, receiver_relations, propagation, plan, return_state,
+                                return_steps)
         if return_state:
             return torch.sigmoid(z[0])[..., None], z[1]
         return torch.sigmoid(z)[..., None]

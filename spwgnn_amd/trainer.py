@@ -61,19 +61,38 @@ class HipEngine:
         self.ws = E.Workspace(self.device)
         self.bce_scratch = E.BceScratch(self.device)
         self.grads: Optional[torch.Tensor] = None
+        # deep supervision (Trainer(step_loss_weights=)): with weights set, "logits" and "dlogits" below are
+        # the (mp_steps, n) rows of every step and the loss is Σ_s λ_s·BCE(z_s) (engine.bce_steps); the
+        # Trainer's control flow — scaling, all-reduce, the early-gradient event — only hands them through
+        self.step_loss_weights = None
+        self.steps_scratch: Optional[E.BceStepsScratch] = None
+        self.out3s = None     # the last loss's per-step [loss, correct, n] (device, (mp_steps, 3))
+
+    def set_step_loss_weights(self, lam, mp_steps: int):
+        self.step_loss_weights = None if lam is None else E.check_step_weights(lam, mp_steps)
+        self.steps_scratch = None if lam is None else E.BceStepsScratch(self.device, mp_steps)
 
     def forward(self, params, batch: TowerBatch, run: E.RunConfig):
+        if self.step_loss_weights is not None:
+            return E.forward_steps(params, batch, run, self.ws)
         return E.forward(params, batch, run, self.ws)
 
     def loss(self, logits, target):
-        return E.bce(logits, target, self.bce_scratch)
+        return self.loss_weighted(logits, target, None, None)
 
     def loss_weighted(self, logits, target, weights, norm):
+        if self.step_loss_weights is not None:
+            out3, self.out3s, dz = E.bce_steps(logits, target, self.step_loss_weights, self.steps_scratch,
+                                               node_weights=weights, norm=norm)
+            return out3, dz
         return E.bce(logits, target, self.bce_scratch, node_weights=weights, norm=norm)
 
     def backward(self, params, batch, run, dlogits):
         if self.grads is None or self.grads.numel() != params.numel():
             self.grads = torch.empty_like(params)
+        if self.step_loss_weights is not None:
+            g, _ = E.backward_steps(params, batch, run, self.ws, dlogits, grads=self.grads)
+            return g
         g, _ = E.backward(params, batch, run, self.ws, dlogits, grads=self.grads)
         return g
 
@@ -109,7 +128,10 @@ class Trainer:
                  dropout: float = E.REF_DROPOUT, seed: int = 0, lr: float = 5e-4, beta1: float = 0.9,
                  beta2: float = 0.999, eps: float = 1e-7, l2: float = 0.0, group=None, math: str = "x6",
                  buckets: int = 1, overlap: bool = True, clipnorm: float = 0.0, clipvalue: float = 0.0,
-                 decay: float = 0.0, skip_nonfinite: bool = False):
+                 decay: float = 0.0, skip_nonfinite: bool = False, step_loss_weights=None):
+        # step_loss_weights (None, or mp_steps floats >= 0, not all zero): deep supervision — the loss is
+        # Σ_s λ_s·BCE(z_s, y) over every propagation step's logits instead of the last step's BCE; `step`
+        # then returns [that sum, the last step's correct count, n]. None: exactly the steps of before.
         # Keras 2.x optimizer arguments (0 = off) and the non-finite guard: with any of them set the
         # update is engine.adam_clipped — the global norm of the all-reduced gradient, one launch more —
         # instead of engine.adam; with none, exactly the launches of before
@@ -122,6 +144,11 @@ class Trainer:
             raise ValueError("clipnorm / clipvalue / decay / skip_nonfinite need an engine with adam_clipped("
                              "params, grads, m, v, step, lr, b1, b2, eps, l2, gscale, clipnorm, clipvalue, "
                              "skip_nonfinite)")
+        self.step_loss_weights = None if step_loss_weights is None else E.check_step_weights(step_loss_weights, mp_steps)
+        if self.step_loss_weights is not None:
+            if not hasattr(self.engine, "set_step_loss_weights"):
+                raise ValueError("step_loss_weights needs an engine with set_step_loss_weights(weights, mp_steps)")
+            self.engine.set_step_loss_weights(self.step_loss_weights, mp_steps)
         self.clip_stats = None    # the last clipped step's [norm, scale, skipped, clipped] (device tensor)
         self.m = torch.zeros_like(params)
         self.v = torch.zeros_like(params)
@@ -220,6 +247,8 @@ class Trainer:
         clip = self.engine.clip_scratch() if self._clip_on() else None
         if clip is not None:
             self.clip_stats = clip.out4
+        lam = self.step_loss_weights
+        sbuf = {}   # deep supervision: this geometry's (mp_steps, n) rows and loss scratch, made by its first (eager) run
 
         def body(batch, target, ws, bce, z, dz, pre=None, weights=None, norm=None):
             # the key/step advance (and the replayed batch upload, `pre`) ride in the forward's first launch
@@ -231,11 +260,20 @@ class Trainer:
                 E.step_advance(ctr.key, ctr.step, _lib.STEP_KEY_SPLITMIX, self.seed, self.rank)
             run = E.RunConfig(self.mp_steps, training=True, dropout=self.dropout, math=self.math, seed_dev=ctr.key,
                               prologue=pro)
-            E.forward(self.params, batch, run, ws, logits=z)
-            # the loss and the backward in one call (spwgnn_bce_backward: no loss launch of its own on
-            # the fused small-batch loop; bit-identical to bce then backward)
-            E.bce_backward(self.params, batch, run, ws, z, target, bce, dlogits=dz, grads=grads,
-                           node_weights=weights, norm=norm)
+            if lam is not None:   # every step's logits, the step-weighted loss (its own launch), one backward
+                if not sbuf:
+                    sbuf["z"] = torch.empty(self.mp_steps, batch.n_nodes, dtype=torch.float32, device=z.device)
+                    sbuf["dz"] = torch.empty_like(sbuf["z"])
+                    sbuf["bce"] = E.BceStepsScratch(z.device, self.mp_steps)
+                E.forward_steps(self.params, batch, run, ws, step_logits=sbuf["z"])
+                E.bce_steps(sbuf["z"], target, lam, sbuf["bce"], dlogits=sbuf["dz"], node_weights=weights, norm=norm)
+                E.backward_steps(self.params, batch, run, ws, sbuf["dz"], grads=grads)
+            else:
+                E.forward(self.params, batch, run, ws, logits=z)
+                # the loss and the backward in one call (spwgnn_bce_backward: no loss launch of its own on
+                # the fused small-batch loop; bit-identical to bce then backward)
+                E.bce_backward(self.params, batch, run, ws, z, target, bce, dlogits=dz, grads=grads,
+                               node_weights=weights, norm=norm)
             if w != 1.0:
                 grads.mul_(w)
             if clip is None:
