@@ -408,7 +408,9 @@ int32_t spwgnn_bce_accumulate(const float* logits, const float* targets, int64_t
  * workspace). Where the backward runs its fused small-batch loop and the loss fits one workgroup
  * (n <= 256, the reference's batch 32), the loop computes dlogits itself (still stored to dlogits)
  * and the loss sums ride in the backward's last launch: a training step needs no loss launch of its
- * own (Keras fit, main.py:92-98). Replaces the Keras loss + autodiff pair of Networks.py:102. */
+ * own (Keras fit, main.py:92-98). Replaces the Keras loss + autodiff pair of Networks.py:102.
+ * SPWGNN_E_ARG unless n == batch->n_nodes (checked before any device work): the folded loss indexes
+ * logits, targets and dlogits by plan node. */
 int32_t spwgnn_bce_backward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
                             void* workspace, int64_t workspace_bytes, const float* logits,
                             const float* targets, int64_t n, float* out3, float* dlogits, void* bce_scratch,

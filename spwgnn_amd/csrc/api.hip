@@ -1598,6 +1598,8 @@ int32_t spwgnn_bce_backward(const float* params, const spwgnn_batch* batch, cons
     int32_t stt = validate(batch, run);
     if (stt) return stt;
     if (!run->training) return SPWGNN_E_NOTRAIN;
+    // the folded loss indexes logits, targets and dlogits by plan node: one entry per node, no fewer
+    if (n != batch->n_nodes) return SPWGNN_E_ARG;
     if (!params || !workspace || !grads || !logits || !targets || !out3 || !dlogits || !bce_scratch || n < 1 ||
         (!weights3) != (!total3))
         return SPWGNN_E_ARG;

@@ -250,6 +250,24 @@ def _check_dstate(ws: Workspace, batch: TowerBatch, dstate: torch.Tensor) -> tor
     return dstate.contiguous()
 
 
+def _out_buffer(t: torch.Tensor, shape: tuple, what: str) -> torch.Tensor:
+    """A caller's output buffer, validated as `forward` validates ``state``: on the GPU, fp32, contiguous,
+    of exactly `shape`."""
+    _require_gpu(t, what)
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous fp32 {tuple(shape)} tensor")
+    return t
+
+
+def _dprop_buffer(batch: TowerBatch, dprop: Optional[torch.Tensor], want_dprop: bool) -> Optional[torch.Tensor]:
+    """d/d'propagation' output: the caller's ``dprop`` (it implies want_dprop), a fresh one, or None."""
+    if dprop is not None:
+        return _out_buffer(dprop, (batch.n_nodes, STATE_WIDTH), "dprop")
+    if want_dprop:
+        return _poison(torch.empty(batch.n_nodes, STATE_WIDTH, dtype=torch.float32, device=batch.device))
+    return None
+
+
 def forward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
             logits: Optional[torch.Tensor] = None, return_state: bool = False,
             state: Optional[torch.Tensor] = None):
@@ -290,11 +308,13 @@ def forward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Wo
 
 
 def backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace, dlogits: torch.Tensor,
-             grads: Optional[torch.Tensor] = None, want_dprop: bool = False, dstate: Optional[torch.Tensor] = None):
+             grads: Optional[torch.Tensor] = None, want_dprop: bool = False, dstate: Optional[torch.Tensor] = None,
+             dprop: Optional[torch.Tensor] = None):
     """Gradients of Σ dlogits·z — and, with ``dstate`` ((n_nodes, 100) fp32 on the batch's device, plan node
     order), of Σ dlogits·z + Σ dstate·P_S in the same single pass (spwgnn_backward_state); the forward on
     this workspace must then have been ``forward(..., return_state=True)``. A caller with a loss on the
-    state alone passes zero ``dlogits``. Returns (grads, dprop)."""
+    state alone passes zero ``dlogits``. ``dprop``: the (n_nodes, 100) buffer to write d/d'propagation' to
+    (it implies ``want_dprop``). Returns (grads, dprop)."""
     if not run.training:
         raise _lib.SpwgnnError("backward needs a training forward on the same workspace")
     if dstate is not None:
@@ -308,7 +328,7 @@ def backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: W
     _require_gpu(dlogits, "dlogits")
     if grads is None:
         grads = _poison(torch.empty_like(flat_params))
-    dprop = _poison(torch.empty(batch.n_nodes, 100, dtype=torch.float32, device=batch.device)) if want_dprop else None
+    dprop = _dprop_buffer(batch, dprop, want_dprop)
     b = batch.cstruct()
     r = run.cstruct()
     buf = ws.buf
@@ -367,11 +387,12 @@ def forward_steps(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, 
 
 def backward_steps(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
                    dstep_logits: torch.Tensor, grads: Optional[torch.Tensor] = None, want_dprop: bool = False,
-                   dstate: Optional[torch.Tensor] = None):
+                   dstate: Optional[torch.Tensor] = None, dprop: Optional[torch.Tensor] = None):
     """Gradients of Σ_s Σ_i dstep_logits[s, i]·z_s[i] (+ Σ dstate·P_S) in one pass over the step loop
     (spwgnn_backward_steps): ``dstep_logits`` is (mp_steps, n_nodes) fp32 in the plan's node order, row s
     the cotangent of step s's logits (`forward_steps`' rows). The forward on this workspace may be any of
-    `forward` / `forward_steps`; ``dstate`` needs ``return_state=True`` there. Returns (grads, dprop)."""
+    `forward` / `forward_steps`; ``dstate`` needs ``return_state=True`` there. ``dprop`` as in `backward`.
+    Returns (grads, dprop)."""
     if not run.training:
         raise _lib.SpwgnnError("backward needs a training forward on the same workspace")
     if dstate is not None:
@@ -387,7 +408,7 @@ def backward_steps(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig,
     dstep_logits = dstep_logits.to(torch.float32).contiguous()
     if grads is None:
         grads = _poison(torch.empty_like(flat_params))
-    dprop = _poison(torch.empty(batch.n_nodes, 100, dtype=torch.float32, device=batch.device)) if want_dprop else None
+    dprop = _dprop_buffer(batch, dprop, want_dprop)
     b = batch.cstruct()
     r = run.cstruct()
     buf = ws.buf
@@ -400,19 +421,24 @@ def backward_steps(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig,
     return grads, dprop
 
 
-def backward_inputs(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace) -> torch.Tensor:
+def backward_inputs(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
+                    dpos: Optional[torch.Tensor] = None) -> torch.Tensor:
     """d(loss)/d(objects) of the last `backward` / `bce_backward` on this workspace (spwgnn_backward_inputs,
     ABI 8): (n_nodes, 3) fp32 — d/d(x, y, width) of the objects rows as the batch holds them (already
     /170) — in the plan's node order (`TowerBatch.to_input_order` for packed plans), a view of the
     library's (n_nodes, 4) output. One extra launch; the gradients `backward` returned are untouched.
-    The relation set (a thresholded one included) is a constant of the graph and is not differentiated."""
+    The relation set (a thresholded one included) is a constant of the graph and is not differentiated.
+    ``dpos``: the (n_nodes, 4) buffer the library writes to (the returned view is of it)."""
     if not run.training:
         _lib.check(_lib.E_NOTRAIN, "spwgnn_backward_inputs")
     if not ws.holds(batch, run) or ws.bwd_key != ws.fwd_key:
         raise _lib.SpwgnnError("backward_inputs needs the backward of the same batch and RunConfig on this workspace "
                                "(it reads what that backward left there; a new forward discards it)")
     _require_gpu(flat_params, "params")
-    dpos = _poison(torch.empty(batch.n_nodes, 4, dtype=torch.float32, device=batch.device))
+    if dpos is None:
+        dpos = _poison(torch.empty(batch.n_nodes, 4, dtype=torch.float32, device=batch.device))
+    else:
+        _out_buffer(dpos, (batch.n_nodes, 4), "dpos")
     b = batch.cstruct()
     r = run.cstruct()
     buf = ws.buf
@@ -426,13 +452,16 @@ def bce_backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, w
                  targets: torch.Tensor, scratch: "BceScratch", dlogits: Optional[torch.Tensor] = None,
                  total3: Optional[torch.Tensor] = None, weights3: Optional[torch.Tensor] = None,
                  grads: Optional[torch.Tensor] = None, want_dprop: bool = False,
-                 node_weights: Optional[torch.Tensor] = None, norm=None):
+                 node_weights: Optional[torch.Tensor] = None, norm=None, dprop: Optional[torch.Tensor] = None):
     """bce (or its accumulating form) then backward in one library call (spwgnn_bce_backward, ABI 6):
     bit-identical to the two calls; on the fused small-batch loop the loss needs no launch of its own.
     With `node_weights` / `norm` (see `bce`) the weighted loss (spwgnn_bce_backward_weighted), whose
-    loss launch always runs first. Returns (out3, dlogits, grads, dprop)."""
+    loss launch always runs first. ``logits`` holds one value per node of the batch (the folded loss indexes
+    it by plan node). ``dprop`` as in `backward`. Returns (out3, dlogits, grads, dprop)."""
     if not run.training:
         raise _lib.SpwgnnError("backward needs a training forward on the same workspace")
+    if logits.numel() != batch.n_nodes:
+        raise ValueError(f"logits must hold one value per node of the batch ({batch.n_nodes}), got {logits.numel()}")
     if not ws.holds(batch, run):
         raise _lib.SpwgnnError("backward needs the training forward of the same batch and RunConfig "
                                f"on this workspace (stored {ws.fwd_key}, asked {Workspace.key(batch, run)})")
@@ -446,7 +475,7 @@ def bce_backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, w
         raise ValueError("total3 and weights3 go together")
     if total3 is not None:
         assert total3.dtype == torch.float64 and weights3.dtype == torch.float64
-    dprop = _poison(torch.empty(batch.n_nodes, 100, dtype=torch.float32, device=batch.device)) if want_dprop else None
+    dprop = _dprop_buffer(batch, dprop, want_dprop)
     b = batch.cstruct()
     r = run.cstruct()
     buf = ws.buf
@@ -758,8 +787,12 @@ def copy_in(host: torch.Tensor, dev: torch.Tensor, nbytes: int, src_dev_ptr: Opt
     _lib.check(st, "spwgnn_copy_in")
 
 
-def sigmoid(logits: torch.Tensor) -> torch.Tensor:
-    out = torch.empty_like(logits)
+def sigmoid(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sigmoid(logits) (spwgnn_sigmoid); ``out``: the buffer to write to, of the logits' shape."""
+    if out is None:
+        out = torch.empty_like(logits)
+    else:
+        _out_buffer(out, tuple(logits.shape), "out")
     st = _lib.lib().spwgnn_sigmoid(logits.data_ptr(), out.data_ptr(), logits.numel(), _stream(logits.device))
     _lib.check(st, "spwgnn_sigmoid")
     return out
@@ -769,17 +802,21 @@ READOUT_MODES = {"sum_prob": _lib.READOUT_SUM_PROB, "mean_prob": _lib.READOUT_ME
                  "sum_logit": _lib.READOUT_SUM_LOGIT, "mean_logit": _lib.READOUT_MEAN_LOGIT}
 
 
-def tower_readout(logits: torch.Tensor, batch: TowerBatch, mode: str = "sum_prob") -> torch.Tensor:
+def tower_readout(logits: torch.Tensor, batch: TowerBatch, mode: str = "sum_prob",
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(T,) per-tower reduction of the node logits on device: "sum_prob" is the Σŷ stability score of
     JengaBuilder.remove_to_demolish (JengaBuilder.py:252-256); "mean_prob" the optional GlobalBlock
-    mean pool (not in the reference)."""
+    mean pool (not in the reference). ``out``: the (n_towers,) buffer to write to."""
     if mode not in READOUT_MODES:
         raise ValueError(f"readout mode must be one of {sorted(READOUT_MODES)}")
     _require_gpu(logits, "logits")
     logits = logits.reshape(-1).contiguous().to(torch.float32)
     if logits.numel() != batch.n_nodes:
         raise ValueError("logits must hold one value per node of the batch")
-    out = torch.empty(batch.n_towers, dtype=torch.float32, device=logits.device)
+    if out is None:
+        out = torch.empty(batch.n_towers, dtype=torch.float32, device=logits.device)
+    else:
+        _out_buffer(out, (batch.n_towers,), "out")
     st = _lib.lib().spwgnn_tower_readout(logits.data_ptr(), batch.tower_offsets.data_ptr(), batch.n_towers,
                                          READOUT_MODES[mode], out.data_ptr(), _stream(logits.device))
     _lib.check(st, "spwgnn_tower_readout")
