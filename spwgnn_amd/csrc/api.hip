@@ -1398,13 +1398,25 @@ int32_t spwgnn_math_products_bwd(int32_t math) {
     return math_products_bwd(math);
 }
 
+static int32_t status(hipError_t e) { return e == hipSuccess ? SPWGNN_OK : (int32_t)e; }
+static bool mis16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; }
+
+// The prologue of every workspace call, in the order the status codes keep: validate, E_NOTRAIN, the
+// call's own argument checks (args_ok: the caller evaluates it first, so it follows neither batch nor
+// run), E_WORKSPACE. Fills w on SPWGNN_OK.
+static int32_t enter(const spwgnn_batch* batch, const spwgnn_run* run, const void* workspace, int64_t bytes,
+                     bool need_training, bool args_ok, Ws& w) {
+    if (int32_t stt = validate(batch, run)) return stt;
+    if (need_training && !run->training) return SPWGNN_E_NOTRAIN;
+    if (!args_ok || !workspace) return SPWGNN_E_ARG;
+    w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, run->training ? 1 : 0);
+    return bytes < w.total ? SPWGNN_E_WORKSPACE : SPWGNN_OK;
+}
+
 int32_t spwgnn_forward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
                        int64_t workspace_bytes, float* logits, spwgnn_stream_t stream) {
-    int32_t stt = validate(batch, run);
-    if (stt) return stt;
-    if (!params || !workspace || !logits) return SPWGNN_E_ARG;
-    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, run->training ? 1 : 0);
-    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
+    Ws w;
+    if (int32_t stt = enter(batch, run, workspace, workspace_bytes, false, params && logits, w)) return stt;
     return run_forward(params, batch, run, w, static_cast<char*>(workspace), logits,
                        static_cast<hipStream_t>(stream));
 }
@@ -1412,25 +1424,23 @@ int32_t spwgnn_forward(const float* params, const spwgnn_batch* batch, const spw
 int32_t spwgnn_backward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
                         int64_t workspace_bytes, const float* dlogits, float* grads, float* dprop,
                         spwgnn_stream_t stream) {
-    int32_t stt = validate(batch, run);
-    if (stt) return stt;
-    if (!run->training) return SPWGNN_E_NOTRAIN;
-    if (!params || !workspace || !dlogits || !grads) return SPWGNN_E_ARG;
-    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, 1);
-    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
+    Ws w;
+    if (int32_t stt = enter(batch, run, workspace, workspace_bytes, true, params && dlogits && grads, w)) return stt;
     return run_backward(params, batch, run, w, static_cast<char*>(workspace), dlogits, grads, dprop,
                         static_cast<hipStream_t>(stream));
 }
 
-int32_t spwgnn_forward_state(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
-                             int64_t workspace_bytes, float* logits, float* state_out, spwgnn_stream_t stream) {
-    int32_t stt = validate(batch, run);
-    if (stt) return stt;
-    if (!params || !workspace || !logits || reinterpret_cast<uintptr_t>(state_out) % 16) return SPWGNN_E_ARG;
-    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, run->training ? 1 : 0);
-    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
+// spwgnn_forward_state (step_stride 0: one logit row) and spwgnn_forward_steps (step_stride n_nodes: each
+// step's node side given its own row): the forward, then the state's export
+static int32_t forward_state(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                             int64_t workspace_bytes, float* logits, float* state_out, bool steps,
+                             spwgnn_stream_t stream) {
+    Ws w;
+    if (int32_t stt = enter(batch, run, workspace, workspace_bytes, false, params && logits && !mis16(state_out), w))
+        return stt;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    stt = run_forward(params, batch, run, w, static_cast<char*>(workspace), logits, st, state_out != nullptr);
+    const int32_t stt = run_forward(params, batch, run, w, static_cast<char*>(workspace), logits, st,
+                                    state_out != nullptr, steps ? batch->n_nodes : 0);
     if (stt || !state_out) return stt;
     const Ctx c{w, static_cast<char*>(workspace)};
     const Prof prof{run, st};
@@ -1438,64 +1448,42 @@ int32_t spwgnn_forward_state(const float* params, const spwgnn_batch* batch, con
     SPW_CHECK(launch_state_export(c.f(w.P_at(run->mp_steps)), state_out, batch->n_nodes, st));
     SPW_CHECK(prof.after(SPWGNN_K_STATE));
     return SPWGNN_OK;
+}
+
+int32_t spwgnn_forward_state(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                             int64_t workspace_bytes, float* logits, float* state_out, spwgnn_stream_t stream) {
+    return forward_state(params, batch, run, workspace, workspace_bytes, logits, state_out, false, stream);
+}
+
+int32_t spwgnn_forward_steps(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                             int64_t workspace_bytes, float* step_logits, float* state_out, spwgnn_stream_t stream) {
+    return forward_state(params, batch, run, workspace, workspace_bytes, step_logits, state_out, true, stream);
 }
 
 int32_t spwgnn_backward_state(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
                               int64_t workspace_bytes, const float* dlogits, const float* dstate, float* grads,
                               float* dprop, spwgnn_stream_t stream) {
-    int32_t stt = validate(batch, run);
-    if (stt) return stt;
-    if (!run->training) return SPWGNN_E_NOTRAIN;
-    if (!params || !workspace || !dlogits || !grads || reinterpret_cast<uintptr_t>(dstate) % 16) return SPWGNN_E_ARG;
-    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, 1);
-    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
+    Ws w;
+    const bool ok = params && dlogits && grads && !mis16(dstate);
+    if (int32_t stt = enter(batch, run, workspace, workspace_bytes, true, ok, w)) return stt;
     return run_backward(params, batch, run, w, static_cast<char*>(workspace), dlogits, grads, dprop,
                         static_cast<hipStream_t>(stream), nullptr, dstate);
-}
-
-// Per-step logits: the same launches as spwgnn_forward_state / spwgnn_backward_state,
-// each step's node side given its own row
-int32_t spwgnn_forward_steps(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
-                             int64_t workspace_bytes, float* step_logits, float* state_out, spwgnn_stream_t stream) {
-    int32_t stt = validate(batch, run);
-    if (stt) return stt;
-    if (!params || !workspace || !step_logits || reinterpret_cast<uintptr_t>(state_out) % 16) return SPWGNN_E_ARG;
-    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, run->training ? 1 : 0);
-    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    stt = run_forward(params, batch, run, w, static_cast<char*>(workspace), step_logits, st, state_out != nullptr,
-                      batch->n_nodes);
-    if (stt || !state_out) return stt;
-    const Ctx c{w, static_cast<char*>(workspace)};
-    const Prof prof{run, st};
-    SPW_CHECK(prof.before(SPWGNN_K_STATE));
-    SPW_CHECK(launch_state_export(c.f(w.P_at(run->mp_steps)), state_out, batch->n_nodes, st));
-    SPW_CHECK(prof.after(SPWGNN_K_STATE));
-    return SPWGNN_OK;
 }
 
 int32_t spwgnn_backward_steps(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
                               int64_t workspace_bytes, const float* dstep_logits, const float* dstate, float* grads,
                               float* dprop, spwgnn_stream_t stream) {
-    int32_t stt = validate(batch, run);
-    if (stt) return stt;
-    if (!run->training) return SPWGNN_E_NOTRAIN;
-    if (!params || !workspace || !dstep_logits || !grads || reinterpret_cast<uintptr_t>(dstate) % 16)
-        return SPWGNN_E_ARG;
-    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, 1);
-    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
+    Ws w;
+    const bool ok = params && dstep_logits && grads && !mis16(dstate);
+    if (int32_t stt = enter(batch, run, workspace, workspace_bytes, true, ok, w)) return stt;
     return run_backward(params, batch, run, w, static_cast<char*>(workspace), dstep_logits, grads, dprop,
                         static_cast<hipStream_t>(stream), nullptr, dstate, batch->n_nodes);
 }
 
 int32_t spwgnn_backward_inputs(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
                                int64_t workspace_bytes, float* dpos, spwgnn_stream_t stream) {
-    int32_t stt = validate(batch, run);
-    if (stt) return stt;
-    if (!run->training) return SPWGNN_E_NOTRAIN;
-    if (!params || !workspace || !dpos || reinterpret_cast<uintptr_t>(dpos) % 16) return SPWGNN_E_ARG;
-    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, 1);
-    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
+    Ws w;
+    if (int32_t stt = enter(batch, run, workspace, workspace_bytes, true, params && dpos && !mis16(dpos), w)) return stt;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const Ctx c{w, static_cast<char*>(workspace)};
     const ParamTable& pt = param_table();
@@ -1591,42 +1579,13 @@ int32_t spwgnn_plan_device_dense(const spwgnn_plan_device* plan, const float* Rs
     return plan_device_launch(plan, a, true, static_cast<hipStream_t>(stream));
 }
 
-int32_t spwgnn_bce_backward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
-                            int64_t workspace_bytes, const float* logits, const float* targets, int64_t n,
-                            float* out3, float* dlogits, void* bce_scratch, const double* weights3, double* total3,
-                            float* grads, float* dprop, spwgnn_stream_t stream) {
-    int32_t stt = validate(batch, run);
-    if (stt) return stt;
-    if (!run->training) return SPWGNN_E_NOTRAIN;
-    // the folded loss indexes logits, targets and dlogits by plan node: one entry per node, no fewer
-    if (n != batch->n_nodes) return SPWGNN_E_ARG;
-    if (!params || !workspace || !grads || !logits || !targets || !out3 || !dlogits || !bce_scratch || n < 1 ||
-        (!weights3) != (!total3))
-        return SPWGNN_E_ARG;
-    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, 1);
-    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
-    BceArgs a{};   // as spwgnn_bce_accumulate builds it
-    a.w3 = weights3;
-    a.tot3 = total3;
-    a.logits = logits;
-    a.targets = targets;
-    a.n = n;
-    a.dlogits = dlogits;
-    a.partial = static_cast<float*>(bce_scratch);
-    a.out3 = out3;
-    a.blocks = (int)std::min<int64_t>(256, (n + 255) / 256);
-    return run_backward(params, batch, run, w, static_cast<char*>(workspace), dlogits, grads, dprop,
-                        static_cast<hipStream_t>(stream), &a);
+// spwgnn_loss_weights' own checks (no pointer followed past lw itself)
+static bool loss_weights_ok(const spwgnn_loss_weights* lw) {
+    return lw && lw->w && (lw->norm_dev || lw->norm > 0.0);
 }
-
-int64_t spwgnn_bce_scratch_bytes(int64_t n) {
-    (void)n;
-    return 256 * 3 * sizeof(float);   // [blocks][3] for the weighted loss; the unweighted one uses [blocks][2]
-}
-
-static int32_t bce_launch(const float* logits, const float* targets, int64_t n, float* out3, float* dlogits,
-                          void* scratch, const double* weights3, double* total3, spwgnn_stream_t stream) {
-    if (!logits || !targets || !out3 || !scratch || n < 1) return SPWGNN_E_ARG;
+// The one-row loss's arguments (lw null: unweighted); spwgnn_bce_steps' rows start at the same pointers.
+static BceArgs bce_args(const float* logits, const float* targets, int64_t n, float* out3, float* dlogits,
+                        void* scratch, const double* weights3, double* total3, const spwgnn_loss_weights* lw) {
     BceArgs a{};
     a.w3 = weights3;
     a.tot3 = total3;
@@ -1637,51 +1596,76 @@ static int32_t bce_launch(const float* logits, const float* targets, int64_t n, 
     a.partial = static_cast<float*>(scratch);
     a.out3 = out3;
     a.blocks = (int)std::min<int64_t>(256, (n + 255) / 256);
-    hipError_t e = launch_bce(a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+    if (lw) {
+        a.w = lw->w;
+        a.norm_dev = lw->norm_dev;
+        a.norm = lw->norm_dev ? 0.f : (float)lw->norm;
+    }
+    return a;
+}
+
+// spwgnn_bce_backward (weighted false, lw null) and spwgnn_bce_backward_weighted
+static int32_t bce_backward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                            int64_t workspace_bytes, const float* logits, const float* targets, int64_t n,
+                            float* out3, float* dlogits, void* bce_scratch, const double* weights3, double* total3,
+                            float* grads, float* dprop, const spwgnn_loss_weights* lw, bool weighted,
+                            spwgnn_stream_t stream) {
+    // the folded loss indexes logits, targets and dlogits by plan node: one entry per node, no fewer
+    const bool ok = batch && n == batch->n_nodes && params && grads && logits && targets && out3 && dlogits &&
+                    bce_scratch && n >= 1 && (!weights3) == (!total3) && (!weighted || loss_weights_ok(lw));
+    Ws w;
+    if (int32_t stt = enter(batch, run, workspace, workspace_bytes, true, ok, w)) return stt;
+    const BceArgs a = bce_args(logits, targets, n, out3, dlogits, bce_scratch, weights3, total3, lw);
+    return run_backward(params, batch, run, w, static_cast<char*>(workspace), dlogits, grads, dprop,
+                        static_cast<hipStream_t>(stream), &a);
+}
+
+int32_t spwgnn_bce_backward(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                            int64_t workspace_bytes, const float* logits, const float* targets, int64_t n,
+                            float* out3, float* dlogits, void* bce_scratch, const double* weights3, double* total3,
+                            float* grads, float* dprop, spwgnn_stream_t stream) {
+    return bce_backward(params, batch, run, workspace, workspace_bytes, logits, targets, n, out3, dlogits, bce_scratch,
+                        weights3, total3, grads, dprop, nullptr, false, stream);
+}
+
+int32_t spwgnn_bce_backward_weighted(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                                     void* workspace, int64_t workspace_bytes, const float* logits,
+                                     const float* targets, int64_t n, float* out3, float* dlogits, void* bce_scratch,
+                                     const double* weights3, double* total3, float* grads, float* dprop,
+                                     const spwgnn_loss_weights* lw, spwgnn_stream_t stream) {
+    return bce_backward(params, batch, run, workspace, workspace_bytes, logits, targets, n, out3, dlogits, bce_scratch,
+                        weights3, total3, grads, dprop, lw, true, stream);
+}
+
+int64_t spwgnn_bce_scratch_bytes(int64_t n) {
+    (void)n;
+    return 256 * 3 * sizeof(float);   // [blocks][3] for the weighted loss; the unweighted one uses [blocks][2]
+}
+
+static int32_t bce_launch(const float* logits, const float* targets, int64_t n, float* out3, float* dlogits,
+                          void* scratch, const double* weights3, double* total3, const spwgnn_loss_weights* lw,
+                          spwgnn_stream_t stream) {
+    if (!logits || !targets || !out3 || !scratch || n < 1) return SPWGNN_E_ARG;
+    const BceArgs a = bce_args(logits, targets, n, out3, dlogits, scratch, weights3, total3, lw);
+    return status(launch_bce(a, static_cast<hipStream_t>(stream)));
 }
 
 int32_t spwgnn_bce(const float* logits, const float* targets, int64_t n, float* out3, float* dlogits, void* scratch,
                    spwgnn_stream_t stream) {
-    return bce_launch(logits, targets, n, out3, dlogits, scratch, nullptr, nullptr, stream);
+    return bce_launch(logits, targets, n, out3, dlogits, scratch, nullptr, nullptr, nullptr, stream);
 }
 
 int32_t spwgnn_bce_accumulate(const float* logits, const float* targets, int64_t n, float* out3, float* dlogits,
                               void* scratch, const double* weights3, double* total3, spwgnn_stream_t stream) {
     if (!weights3 || !total3) return SPWGNN_E_ARG;
-    return bce_launch(logits, targets, n, out3, dlogits, scratch, weights3, total3, stream);
-}
-
-// spwgnn_loss_weights' own checks (no pointer followed past lw itself)
-static bool loss_weights_ok(const spwgnn_loss_weights* lw) {
-    return lw && lw->w && (lw->norm_dev || lw->norm > 0.0);
-}
-static BceArgs weighted_bce_args(const float* logits, const float* targets, int64_t n, float* out3, float* dlogits,
-                                 void* scratch, const double* weights3, double* total3, const spwgnn_loss_weights* lw) {
-    BceArgs a{};   // as bce_launch builds it, plus the weights
-    a.w3 = weights3;
-    a.tot3 = total3;
-    a.logits = logits;
-    a.targets = targets;
-    a.n = n;
-    a.dlogits = dlogits;
-    a.partial = static_cast<float*>(scratch);
-    a.out3 = out3;
-    a.blocks = (int)std::min<int64_t>(256, (n + 255) / 256);
-    a.w = lw->w;
-    a.norm_dev = lw->norm_dev;
-    a.norm = lw->norm_dev ? 0.f : (float)lw->norm;
-    return a;
+    return bce_launch(logits, targets, n, out3, dlogits, scratch, weights3, total3, nullptr, stream);
 }
 
 int32_t spwgnn_bce_weighted(const float* logits, const float* targets, int64_t n, const spwgnn_loss_weights* lw,
                             float* out3, float* dlogits, void* scratch, const double* weights3, double* total3,
                             spwgnn_stream_t stream) {
     if (!loss_weights_ok(lw) || (!weights3) != (!total3)) return SPWGNN_E_ARG;
-    if (!logits || !targets || !out3 || !scratch || n < 1) return SPWGNN_E_ARG;
-    const BceArgs a = weighted_bce_args(logits, targets, n, out3, dlogits, scratch, weights3, total3, lw);
-    hipError_t e = launch_bce(a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+    return bce_launch(logits, targets, n, out3, dlogits, scratch, weights3, total3, lw, stream);
 }
 
 int64_t spwgnn_bce_steps_scratch_bytes(int64_t n, int32_t mp_steps) {
@@ -1705,44 +1689,12 @@ int32_t spwgnn_bce_steps(const float* step_logits, const float* targets, int64_t
     }
     if (!any) return SPWGNN_E_ARG;
     BceStepsArgs a{};
-    if (lw) {
-        a.b = weighted_bce_args(step_logits, targets, n, out3, dlogits, scratch, weights3, total3, lw);
-    } else {   // as bce_launch builds it
-        a.b.w3 = weights3;
-        a.b.tot3 = total3;
-        a.b.logits = step_logits;
-        a.b.targets = targets;
-        a.b.n = n;
-        a.b.dlogits = dlogits;
-        a.b.partial = static_cast<float*>(scratch);
-        a.b.out3 = out3;
-        a.b.blocks = (int)std::min<int64_t>(256, (n + 255) / 256);
-    }
+    a.b = bce_args(step_logits, targets, n, out3, dlogits, scratch, weights3, total3, lw);
     a.S = mp_steps;
     a.out3s = out3s;
     a.tot3s = total3s;
     for (int s = 0; s < mp_steps; ++s) a.lambda[s] = sw->lambda[s];
-    hipError_t e = launch_bce_steps(a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
-}
-
-int32_t spwgnn_bce_backward_weighted(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
-                                     void* workspace, int64_t workspace_bytes, const float* logits,
-                                     const float* targets, int64_t n, float* out3, float* dlogits, void* bce_scratch,
-                                     const double* weights3, double* total3, float* grads, float* dprop,
-                                     const spwgnn_loss_weights* lw, spwgnn_stream_t stream) {
-    int32_t stt = validate(batch, run);
-    if (stt) return stt;
-    if (!run->training) return SPWGNN_E_NOTRAIN;
-    if (!loss_weights_ok(lw) || n != batch->n_nodes) return SPWGNN_E_ARG;
-    if (!params || !workspace || !grads || !logits || !targets || !out3 || !dlogits || !bce_scratch || n < 1 ||
-        (!weights3) != (!total3))
-        return SPWGNN_E_ARG;
-    Ws w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, 1);
-    if (workspace_bytes < w.total) return SPWGNN_E_WORKSPACE;
-    const BceArgs a = weighted_bce_args(logits, targets, n, out3, dlogits, bce_scratch, weights3, total3, lw);
-    return run_backward(params, batch, run, w, static_cast<char*>(workspace), dlogits, grads, dprop,
-                        static_cast<hipStream_t>(stream), &a);
+    return status(launch_bce_steps(a, static_cast<hipStream_t>(stream)));
 }
 
 static float adam_lr_t(float lr, float beta1, float beta2, double t) {
@@ -1756,53 +1708,46 @@ int32_t spwgnn_adam_lr_table(float lr, float beta1, float beta2, int32_t n, floa
     return SPWGNN_OK;
 }
 
-int32_t spwgnn_adam_dev(float* params, const float* grads, float* m, float* v, int64_t n, const int32_t* step_dev,
-                        const float* lr_table, int32_t table_len, float beta1, float beta2, float eps, float l2,
-                        float grad_scale, spwgnn_stream_t stream) {
-    if (!params || !grads || !m || !v || n < 1 || !step_dev || !lr_table || table_len < 2) return SPWGNN_E_ARG;
+// what every Adam step shares; the caller adds lr_t (a host step count) or the device step word and table
+static AdamArgs adam_args(float* params, const float* grads, float* m, float* v, int64_t n, float beta1, float beta2,
+                          float eps, float l2, float grad_scale) {
     AdamArgs a{};
     a.p = params;
     a.g = grads;
     a.m = m;
     a.v = v;
     a.n = n;
-    a.step_dev = step_dev;
-    a.lr_table = lr_table;
-    a.table_len = table_len;
     a.b1 = beta1;
     a.b2 = beta2;
     a.eps = eps;
     a.l2 = l2;
     a.gscale = grad_scale;
-    hipError_t e = launch_adam(a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+    return a;
+}
+
+int32_t spwgnn_adam_dev(float* params, const float* grads, float* m, float* v, int64_t n, const int32_t* step_dev,
+                        const float* lr_table, int32_t table_len, float beta1, float beta2, float eps, float l2,
+                        float grad_scale, spwgnn_stream_t stream) {
+    if (!params || !grads || !m || !v || n < 1 || !step_dev || !lr_table || table_len < 2) return SPWGNN_E_ARG;
+    AdamArgs a = adam_args(params, grads, m, v, n, beta1, beta2, eps, l2, grad_scale);
+    a.step_dev = step_dev;
+    a.lr_table = lr_table;
+    a.table_len = table_len;
+    return status(launch_adam(a, static_cast<hipStream_t>(stream)));
 }
 
 int32_t spwgnn_step_advance(uint64_t* key_dev, int32_t* step_dev, int32_t mode, uint64_t seed, int32_t rank,
                             spwgnn_stream_t stream) {
     if (!key_dev || !step_dev || mode < SPWGNN_STEP_KEY_COUNTER || mode > SPWGNN_STEP_KEY_SPLITMIX) return SPWGNN_E_ARG;
-    hipError_t e = launch_step_advance(key_dev, step_dev, mode, seed, rank, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+    return status(launch_step_advance(key_dev, step_dev, mode, seed, rank, static_cast<hipStream_t>(stream)));
 }
 
 int32_t spwgnn_adam(float* params, const float* grads, float* m, float* v, int64_t n, int32_t step, float lr,
                     float beta1, float beta2, float eps, float l2, float grad_scale, spwgnn_stream_t stream) {
     if (!params || !grads || !m || !v || n < 1 || step < 1) return SPWGNN_E_ARG;
-    AdamArgs a{};
-    a.p = params;
-    a.g = grads;
-    a.m = m;
-    a.v = v;
-    a.n = n;
-    const double t = step;
-    a.lr_t = adam_lr_t(lr, beta1, beta2, t);
-    a.b1 = beta1;
-    a.b2 = beta2;
-    a.eps = eps;
-    a.l2 = l2;
-    a.gscale = grad_scale;
-    hipError_t e = launch_adam(a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+    AdamArgs a = adam_args(params, grads, m, v, n, beta1, beta2, eps, l2, grad_scale);
+    a.lr_t = adam_lr_t(lr, beta1, beta2, (double)step);
+    return status(launch_adam(a, static_cast<hipStream_t>(stream)));
 }
 
 // ---- clipnorm / clipvalue / decay / the non-finite guard ----
@@ -1829,16 +1774,7 @@ static int32_t clip_args(ClipArgs& c, float* params, const float* grads, float* 
     if (n != pt.total) return SPWGNN_E_ARG;
     if (!(clip->clipnorm >= 0.f) || !(clip->clipvalue >= 0.f)) return SPWGNN_E_ARG;   // negative or NaN
     c = ClipArgs{};
-    c.a.p = params;
-    c.a.g = grads;
-    c.a.m = m;
-    c.a.v = v;
-    c.a.n = n;
-    c.a.b1 = beta1;
-    c.a.b2 = beta2;
-    c.a.eps = eps;
-    c.a.l2 = l2;
-    c.a.gscale = grad_scale;
+    c.a = adam_args(params, grads, m, v, n, beta1, beta2, eps, l2, grad_scale);
     if (pt.total > (int64_t)kClipRounds * kClipBlocks * 256) return SPWGNN_E_SHAPE;   // k_grad_sumsq's rounds
     for (int t = 0; t < kNumTensors; ++t) c.end[t] = (int32_t)(pt.t[t].offset + (int64_t)pt.t[t].rows * pt.t[t].cols);
     c.partial = static_cast<float*>(scratch);
@@ -1857,8 +1793,7 @@ int32_t spwgnn_adam_clipped(float* params, const float* grads, float* m, float* 
     ClipArgs c;
     if (int32_t st = clip_args(c, params, grads, m, v, n, beta1, beta2, eps, l2, grad_scale, clip, scratch)) return st;
     c.a.lr_t = adam_lr_t(lr, beta1, beta2, (double)step);
-    hipError_t e = launch_adam_clipped(c, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+    return status(launch_adam_clipped(c, static_cast<hipStream_t>(stream)));
 }
 
 int32_t spwgnn_adam_clipped_dev(float* params, const float* grads, float* m, float* v, int64_t n,
@@ -1871,14 +1806,12 @@ int32_t spwgnn_adam_clipped_dev(float* params, const float* grads, float* m, flo
     c.a.step_dev = step_dev;
     c.a.lr_table = lr_table;
     c.a.table_len = table_len;
-    hipError_t e = launch_adam_clipped(c, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+    return status(launch_adam_clipped(c, static_cast<hipStream_t>(stream)));
 }
 
 int32_t spwgnn_accumulate_out3(const float* out3, const double* weights3, double* total3, spwgnn_stream_t stream) {
     if (!out3 || !weights3 || !total3) return SPWGNN_E_ARG;
-    hipError_t e = launch_accumulate_out3(out3, weights3, total3, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+    return status(launch_accumulate_out3(out3, weights3, total3, static_cast<hipStream_t>(stream)));
 }
 
 int32_t spwgnn_copy_in(const void* host, void* dev, int64_t bytes, spwgnn_stream_t stream) {
@@ -1886,14 +1819,12 @@ int32_t spwgnn_copy_in(const void* host, void* dev, int64_t bytes, spwgnn_stream
         reinterpret_cast<uintptr_t>(dev) % 16)
         return SPWGNN_E_ARG;
     if (bytes == 0) return SPWGNN_OK;
-    hipError_t e = launch_copy_in(host, dev, bytes / 16, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+    return status(launch_copy_in(host, dev, bytes / 16, static_cast<hipStream_t>(stream)));
 }
 
 int32_t spwgnn_sigmoid(const float* logits, float* probs, int64_t n, spwgnn_stream_t stream) {
     if (!logits || !probs || n < 1) return SPWGNN_E_ARG;
-    hipError_t e = launch_sigmoid(logits, probs, n, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+    return status(launch_sigmoid(logits, probs, n, static_cast<hipStream_t>(stream)));
 }
 
 int32_t spwgnn_tower_readout(const float* logits, const int32_t* tower_offsets, int32_t n_towers, int32_t mode,
@@ -1901,8 +1832,7 @@ int32_t spwgnn_tower_readout(const float* logits, const int32_t* tower_offsets, 
     if (!logits || !tower_offsets || !out || n_towers < 1 || mode < SPWGNN_READOUT_SUM_PROB ||
         mode > SPWGNN_READOUT_MEAN_LOGIT)
         return SPWGNN_E_ARG;
-    hipError_t e = launch_tower_readout(logits, tower_offsets, n_towers, mode, out, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? SPWGNN_OK : (int32_t)e;
+    return status(launch_tower_readout(logits, tower_offsets, n_towers, mode, out, static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

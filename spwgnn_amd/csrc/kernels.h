@@ -7,6 +7,7 @@
 #define SPWGNN_ONEHOT_BPERM 1
 #endif
 #include "gemm_blocks.h"
+#include "loss_blocks.h"
 
 namespace spw {
 
@@ -215,7 +216,7 @@ struct NodeBwdArgs {
     const uint4 *xh_w1bt, *xh_w1ct, *xh_wo2t, *xh_wo1ct, *xh_wo1at, *xh_wo1pt;      // half-tile forms (§3w)
     int n16;        // bf16 math (training, wide kernels): dU, dV, o1 read and dx, g stored as bf16 (§3g)
     // spwgnn_bce_backward on the fused small-batch loop: the first step computes dlogits from the
-    // logits and targets itself (k_bce_partial's expression, also stored to bce_dlogits) instead of
+    // logits and targets itself (bce_dlogit, also stored to bce_dlogits) instead of
     // reading dlogits
     const float *bce_logits, *bce_targets;
     float* bce_dlogits;
@@ -378,34 +379,6 @@ struct WsBatch {           // the k_wgrad_ws gradients of one backward (k_wgrad_
 
 constexpr int kMaxReduce = 16;
 constexpr int kMaxZero = 48;
-struct BceArgs {
-    const float *logits, *targets;
-    int64_t n;
-    float* dlogits;
-    float* partial;   // [blocks][2]
-    float* out3;
-    int blocks;
-    const double* w3;   // non-null: tot3[k] += (double)out3[k] * w3[k] by the thread that writes out3
-    double* tot3;
-    // per-node loss weights (spwgnn_bce_weighted; null w: the unweighted kernels, `partial` [blocks][2]).
-    // loss = Σ w_i·bce_i / norm, dlogits_i = w_i ≠ 0 ? w_i·bce_dlogit(z_i, t_i, 1/norm) : 0, out3 =
-    // {loss, correct among w ≠ 0, #{w ≠ 0}}; `partial` is [blocks][3]. norm = *norm_dev when set.
-    const float* w;
-    const float* norm_dev;
-    float norm;
-};
-__device__ __forceinline__ float bce_norm(const BceArgs& a) { return a.norm_dev ? *a.norm_dev : a.norm; }
-// Keras binary_crossentropy (Networks.py:102): clip(ŷ, 1e-7, 1-1e-7) ≡ clamp(z, ±ln((1-ε)/ε)).
-constexpr float kLogitClip = 16.11809565f;
-// dL/dz of one node (k_bce_partial's expression; the fused backward's inline form uses it too)
-__device__ __forceinline__ float bce_dlogit(float z0, float t, float inv_n) {
-    const float p = 1.f / (1.f + expf(-z0));
-    return fabsf(z0) < kLogitClip ? (p - t) * inv_n : 0.f;
-}
-// the weighted form: a zero weight is a mask (a select — a NaN target or logit under it stays out)
-__device__ __forceinline__ float bce_dlogit_w(float z0, float t, float w, float inv_norm) {
-    return w != 0.f ? w * bce_dlogit(z0, t, inv_norm) : 0.f;
-}
 // spwgnn_bce_steps: the loss of every propagation step's logit row in one launch.
 // b is the one-row loss (b.w null or set, as spwgnn_bce / spwgnn_bce_weighted build it) with logits =
 // row 0 of [S][n], dlogits = row 0 of [S][n] (or null), out3 = the combined {Σ_s λ_s·loss_s,
@@ -423,7 +396,7 @@ hipError_t launch_bce_steps(const BceStepsArgs& a, hipStream_t st);
 struct ReduceBatch {       // the weight gradients of one backward, reduced in one launch (blockIdx.y)
     ReduceArgs r[kMaxReduce];
     int n;
-    // 1: the launch's last row (its first workgroup) is k_bce_partial<true> on `bce` (one workgroup's
+    // 1: the launch's last row (its first workgroup) is the unweighted loss row of `bce` (one workgroup's
     // loss / accuracy sums: spwgnn_bce_backward's loss, off the backward's critical path)
     int bce_row;
     BceArgs bce;
@@ -443,7 +416,7 @@ struct AdamArgs {
     const float* lr_table;
     int32_t table_len;
 };
-// spwgnn_adam_clipped: k_grad_sumsq then k_adam_clipped (kernels_misc.hip). The grid of
+// spwgnn_adam_clipped: k_grad_sumsq then k_adam_clipped (kernels_loss.hip). The grid of
 // the partial sums is fixed — the same blocks, shares and order on every device — and small enough that
 // every block of the update re-adds the partials itself.
 constexpr int kClipBlocks = 64;

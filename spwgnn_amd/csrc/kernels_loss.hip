@@ -1,0 +1,351 @@
+// Keras BCE loss (one row and per step), Keras Adam and its clipped form, the step counter, the
+// read-outs, the replayed step's copy-in and the state layout kernels.
+#include "kernels.h"
+#include "loss_blocks.h"
+#include <cstdlib>
+
+namespace spw {
+
+// ------------------------------------------------------------------------------------------------
+// The one-row loss (launch_bce): thin kernels around loss_blocks.h. (Run as S = 1 of the per-step kernels
+// below it gives the same bits, but their final sum took 27 µs against 18 µs here: DESIGN.md §3zt.)
+template <bool W, bool FINAL>
+__global__ __launch_bounds__(256) void k_bce_partial(BceArgs a) {
+    bce_one_row<W, FINAL>(a, blockIdx.x);
+}
+template <bool W>
+__global__ void k_bce_final(BceArgs a) {
+    if (threadIdx.x != 0) return;
+    constexpr int P = W ? 3 : 2;
+    double ls = 0.0, cs = 0.0, ns = 0.0;
+    for (int b = 0; b < a.blocks; ++b) {
+        ls += a.partial[P * b];
+        cs += a.partial[P * b + 1];
+        if constexpr (W) ns += a.partial[P * b + 2];
+    }
+    float o[3];
+    bce_row_store<W>(a.out3, a.tot3, a.w3, ls, cs, ns, W ? bce_norm(a) : 0.f, a.n, o);
+}
+
+// The per-step loss: all S logit rows [S][n] against one target row, each row
+// loss_blocks.h's bce_row_block / bce_row_store. The combined row is {Σ_{λ_s ≠ 0} λ_s·loss_s summed in
+// double in step order, correct_{S−1}, n_{S−1}}: with λ = e_{S−1} it is 0.0 + 1.0·loss_{S−1}, the
+// one-row loss's bits.
+template <bool W>
+__device__ __forceinline__ void bce_steps_block(const BceStepsArgs& a, int s, int blk, float norm, float (&red)[3]) {
+    const BceArgs& b = a.b;
+    bce_row_block<W>(b.logits + (int64_t)s * b.n, b.dlogits ? b.dlogits + (int64_t)s * b.n : nullptr, b.targets, b.w,
+                     b.n, b.blocks, blk, a.lambda[s], norm, red);
+}
+// Thread 0 only: row s's out3 from its sums, its share of the combined loss into `comb`, and the
+// combined row after the last step.
+template <bool W>
+__device__ __forceinline__ void bce_steps_store(const BceStepsArgs& a, int s, float norm, double ls, double cs,
+                                                double ns, double& comb) {
+    const BceArgs& b = a.b;
+    const float lam = a.lambda[s];
+    float o[3];
+    bce_row_store<W>(a.out3s + 3 * s, a.tot3s ? a.tot3s + 3 * s : nullptr, b.w3, ls, cs, ns, norm, b.n, o);
+    if (lam != 0.f) comb += (double)lam * (double)o[0];
+    if (s == a.S - 1) {
+        const float c[3] = {(float)comb, o[1], o[2]};
+        bce_put3(b.out3, b.tot3, b.w3, c);
+    }
+}
+// b.blocks == 1 (n ≤ 256, the reference's batch 32): one workgroup walks the S rows and finishes
+template <bool W>
+__global__ __launch_bounds__(256) void k_bce_steps_one(BceStepsArgs a) {
+    const float norm = W ? bce_norm(a.b) : (float)a.b.n;
+    double comb = 0.0;
+    for (int s = 0; s < a.S; ++s) {
+        float red[3];
+        bce_steps_block<W>(a, s, 0, norm, red);
+        if (threadIdx.x == 0) bce_steps_store<W>(a, s, norm, (double)red[0], (double)red[1], W ? (double)red[2] : 0.0, comb);
+    }
+}
+// larger n: grid (blocks, S) of partial sums, then one thread adds each row's partials in block order
+template <bool W>
+__global__ __launch_bounds__(256) void k_bce_steps_partial(BceStepsArgs a) {
+    const int s = blockIdx.y;
+    const float norm = W ? bce_norm(a.b) : (float)a.b.n;
+    float red[3];
+    bce_steps_block<W>(a, s, blockIdx.x, norm, red);
+    if (threadIdx.x == 0) {
+        float* q = a.b.partial + ((int64_t)s * a.b.blocks + blockIdx.x) * 3;
+        q[0] = red[0];
+        q[1] = red[1];
+        if constexpr (W) q[2] = red[2];
+    }
+}
+template <bool W>
+__global__ void k_bce_steps_final(BceStepsArgs a) {
+    if (threadIdx.x != 0) return;
+    const float norm = W ? bce_norm(a.b) : 0.f;
+    double comb = 0.0;
+    for (int s = 0; s < a.S; ++s) {
+        double ls = 0.0, cs = 0.0, ns = 0.0;
+        const float* q = a.b.partial + (int64_t)s * a.b.blocks * 3;
+        for (int k = 0; k < a.b.blocks; ++k) {
+            ls += q[3 * k];
+            cs += q[3 * k + 1];
+            if constexpr (W) ns += q[3 * k + 2];
+        }
+        bce_steps_store<W>(a, s, norm, ls, cs, ns, comb);
+    }
+}
+
+__global__ void k_adam(AdamArgs a) {
+    // replayable steps: the step count lives on the device; lr_t comes from the host-built table
+    // (spwgnn_adam_lr_table: the same expression spwgnn_adam evaluates, so both paths agree bitwise)
+    if (a.step_dev) a.lr_t = a.lr_table[min(max(*a.step_dev, 0), a.table_len - 1)];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float p = a.p[i];
+        const float g = a.gscale * a.g[i] + 2.f * a.l2 * p;
+        const float m = a.b1 * a.m[i] + (1.f - a.b1) * g;
+        const float v = a.b2 * a.v[i] + (1.f - a.b2) * g * g;
+        a.m[i] = m;
+        a.v[i] = v;
+        a.p[i] = p - a.lr_t * m / (sqrtf(v) + a.eps);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Keras 2.x Optimizer.get_gradients (clipnorm, then clipvalue) and a non-finite guard in front of
+// k_adam's update (spwgnn_adam_clipped). Two launches: the partial sums of Σg'², then
+// the update, whose every block re-adds the partials in the same order and so derives the same scale
+// and the same skip decision. k_adam itself is untouched: a step without these options runs it as before.
+
+// Block `blockIdx.x` of kClipBlocks: Σg'² over its share of the REAL parameters, g' = gscale·g + 2·l2·p
+// as k_adam forms it. Round k < kClipRounds, thread (b, t) takes flat element b·256 + t + k·16,384: all
+// kClipRounds loads of g and of p go out first (they depend on nothing), then at most 13 squares are
+// added in a row, then bce_row_block's LDS tree (8 levels). No atomics: the same bits on every run and device.
+// Which elements are real is decided per WAVE with scalar code: tensors start on 64-float boundaries,
+// so the 64 consecutive elements a wave covers in a round lie in one tensor's extent, and they are real
+// up to that tensor's end c.end[t] if it falls inside the chunk, else all of them. An element that is
+// off (padding, or past n) reads element 0 instead and adds a selected 0.f: whatever the padding holds
+// stays out. (A loop of its own per tensor made 22 dependent round trips to memory: 12 µs)
+__global__ __launch_bounds__(256) void k_grad_sumsq(ClipArgs c) {
+    __shared__ float ss[256];
+    const AdamArgs& a = c.a;
+    const int i0 = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    float gv[kClipRounds], pv[kClipRounds];
+    bool on[kClipRounds];
+#pragma unroll
+    for (int k = 0; k < kClipRounds; ++k) {
+        const int i = i0 + k * kClipBlocks * 256;
+        const int cb = __builtin_amdgcn_readfirstlane(i);   // lane 0's element: the wave's 64-aligned chunk
+        int limit = min(cb + 64, (int)a.n);
+#pragma unroll
+        for (int t = 0; t < kNumTensors; ++t) limit = (c.end[t] > cb && c.end[t] < limit) ? c.end[t] : limit;
+        on[k] = i < limit;
+        const int j = on[k] ? i : 0;
+        gv[k] = a.g[j];
+        pv[k] = a.p[j];
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < kClipRounds; ++k) {
+        const float gp = a.gscale * gv[k] + 2.f * a.l2 * pv[k];
+        s += on[k] ? gp * gp : 0.f;
+    }
+    ss[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) ss[threadIdx.x] += ss[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) c.partial[blockIdx.x] = ss[0];
+}
+
+// k_adam's update on g' · scale, clamped to ±clipvalue. Reads the partials, g, the step word and the lr
+// table; writes p, m, v (elementwise, each by its own thread) and — block 0, thread 0 — out4 / tot4:
+// nothing a block reads is written by another block of this launch.
+__global__ __launch_bounds__(256) void k_adam_clipped(ClipArgs c) {
+    __shared__ float sh[2];   // scale, skip
+    AdamArgs a = c.a;
+    if (threadIdx.x == 0) {
+        double sum = 0.0;
+        for (int b = 0; b < kClipBlocks; ++b) sum += (double)c.partial[b];
+        const float sumsq = (float)sum;   // inf where the fp32 sum overflows: that counts as not finite
+        const float norm = sqrtf(sumsq);
+        const bool finite = fabsf(sumsq) <= 3.402823466e38f;   // false for NaN and ±inf
+        const bool skip = c.skip_nonfinite && !finite;
+        const bool clip = c.clipnorm > 0.f && norm >= c.clipnorm;   // false for a NaN norm, as in Keras
+        const float scale = clip ? c.clipnorm / norm : 1.0f;
+        sh[0] = scale;
+        sh[1] = skip ? 1.f : 0.f;
+        if (blockIdx.x == 0) {
+            const float o[4] = {norm, scale, skip ? 1.f : 0.f, (clip && !skip) ? 1.f : 0.f};
+            const double t4[4] = {skip ? 0.0 : (double)norm, (double)o[3], (double)o[2], 1.0};
+            for (int k = 0; k < 4; ++k) {
+                c.out4[k] = o[k];
+                if (c.tot4) c.tot4[k] += t4[k];
+            }
+        }
+    }
+    __syncthreads();
+    if (sh[1] != 0.f) return;   // skipped: p, m and v keep their bits
+    const float scale = sh[0], cv = c.clipvalue;
+    if (a.step_dev) a.lr_t = a.lr_table[min(max(*a.step_dev, 0), a.table_len - 1)];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float p = a.p[i];
+        const float g0 = a.gscale * a.g[i] + 2.f * a.l2 * p;
+        float g = g0 * scale;   // scale == 1.0f: exact, k_adam's g
+        if (cv > 0.f) g = g > cv ? cv : (g < -cv ? -cv : g);   // selects: a NaN stays a NaN, as in Keras
+        const float m = a.b1 * a.m[i] + (1.f - a.b1) * g;
+        const float v = a.b2 * a.v[i] + (1.f - a.b2) * g * g;
+        a.m[i] = m;
+        a.v[i] = v;
+        a.p[i] = p - a.lr_t * m / (sqrtf(v) + a.eps);
+    }
+}
+
+// Start of a replayable training step (one thread, device_common.h step_advance_dev).
+__global__ void k_step_advance(uint64_t* key, int32_t* step, int mode, uint64_t seed, int32_t rank) {
+    if (threadIdx.x == 0) step_advance_dev(key, step, mode, seed, rank);
+}
+
+__global__ void k_sigmoid(const float* z, float* p, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        p[i] = 1.f / (1.f + expf(-z[i]));
+}
+
+// per-tower readout (one thread per tower, node order): modes as SPWGNN_READOUT_*
+__global__ void k_tower_readout(const float* __restrict__ z, const int32_t* __restrict__ off, int n_towers, int mode,
+                                float* __restrict__ out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_towers) return;
+    const int b = off[t], e = off[t + 1];
+    float s = 0.f;
+    for (int n = b; n < e; ++n) s += (mode <= 1) ? 1.f / (1.f + expf(-z[n])) : z[n];
+    out[t] = ((mode & 1) && e > b) ? s / (float)(e - b) : s;
+}
+
+hipError_t launch_bce(const BceArgs& a, hipStream_t st) {
+    const dim3 g(a.blocks), b(256);
+    if (a.blocks == 1) {   // one launch
+        if (a.w) hipLaunchKernelGGL((k_bce_partial<true, true>), g, b, 0, st, a);
+        else hipLaunchKernelGGL((k_bce_partial<false, true>), g, b, 0, st, a);
+    } else if (a.w) {
+        hipLaunchKernelGGL((k_bce_partial<true, false>), g, b, 0, st, a);
+        hipLaunchKernelGGL(k_bce_final<true>, dim3(1), dim3(64), 0, st, a);
+    } else {
+        hipLaunchKernelGGL((k_bce_partial<false, false>), g, b, 0, st, a);
+        hipLaunchKernelGGL(k_bce_final<false>, dim3(1), dim3(64), 0, st, a);
+    }
+    return hipGetLastError();
+}
+hipError_t launch_bce_steps(const BceStepsArgs& a, hipStream_t st) {
+    if (a.S < 1 || a.S > kMaxSteps || a.b.blocks < 1) return hipErrorInvalidValue;
+    if (a.b.blocks == 1) {
+        if (a.b.w) hipLaunchKernelGGL(k_bce_steps_one<true>, dim3(1), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_bce_steps_one<false>, dim3(1), dim3(256), 0, st, a);
+        return hipGetLastError();
+    }
+    const dim3 g(a.b.blocks, a.S);
+    if (a.b.w) {
+        hipLaunchKernelGGL(k_bce_steps_partial<true>, g, dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_bce_steps_final<true>, dim3(1), dim3(64), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(k_bce_steps_partial<false>, g, dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_bce_steps_final<false>, dim3(1), dim3(64), 0, st, a);
+    }
+    return hipGetLastError();
+}
+hipError_t launch_adam(const AdamArgs& a, hipStream_t st) {
+    const int64_t blocks = std::min<int64_t>((a.n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_adam_clipped(const ClipArgs& c, hipStream_t st) {
+    hipLaunchKernelGGL(k_grad_sumsq, dim3(kClipBlocks), dim3(256), 0, st, c);
+    const int64_t blocks = std::min<int64_t>((c.a.n + 255) / 256, 2048);   // k_adam's grid
+    hipLaunchKernelGGL(k_adam_clipped, dim3((unsigned)blocks), dim3(256), 0, st, c);
+    return hipGetLastError();
+}
+hipError_t launch_step_advance(uint64_t* key, int32_t* step, int mode, uint64_t seed, int32_t rank, hipStream_t st) {
+    hipLaunchKernelGGL(k_step_advance, dim3(1), dim3(64), 0, st, key, step, mode, seed, rank);
+    return hipGetLastError();
+}
+hipError_t launch_tower_readout(const float* z, const int32_t* off, int n_towers, int mode, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_tower_readout, dim3((n_towers + 255) / 256), dim3(256), 0, st, z, off, n_towers, mode, out);
+    return hipGetLastError();
+}
+// A replayed small-batch step's batch arrays, pinned (device-mapped) host staging → the static device
+// buffer, as the step's first kernel: the loads cross PCIe once, all in flight together (a few µs),
+// where a DMA copy between two replays left the GPU idle for ≈ 26 µs.
+__global__ __launch_bounds__(256) void k_copy_in(const uint4* __restrict__ src, uint4* __restrict__ dst, int64_t n16) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256)
+        dst[i] = ld_sys_u4(src + i);   // host staging the host rewrites between replays: system-coherent reads
+}
+hipError_t launch_copy_in(const void* src, void* dst, int64_t n16, hipStream_t st) {
+    const int wgs = (int)std::min<int64_t>(64, (n16 + 1023) / 1024);   // ≤ 4 pieces per thread
+    hipLaunchKernelGGL(k_copy_in, dim3(std::max(wgs, 1)), dim3(256), 0, st, static_cast<const uint4*>(src),
+                       static_cast<uint4*>(dst), n16);
+    return hipGetLastError();
+}
+
+__global__ void k_accumulate_out3(const float* out3, const double* w, double* tot) {
+    const int k = threadIdx.x;
+    if (k < 3) tot[k] += (double)out3[k] * w[k];
+}
+hipError_t launch_accumulate_out3(const float* out3, const double* w, double* tot, hipStream_t st) {
+    hipLaunchKernelGGL(k_accumulate_out3, dim3(1), dim3(64), 0, st, out3, w, tot);
+    return hipGetLastError();
+}
+hipError_t launch_sigmoid(const float* z, float* p, int64_t n, hipStream_t st) {
+    const int64_t blocks = std::min<int64_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_sigmoid, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, st, z, p, n);
+    return hipGetLastError();
+}
+
+// ---- the propagation state at the library's edge ----
+// A 32-node block of a chunk-major 104-feature array is 26 slots of [node i < 32][4 floats]: slot
+// 2q + h holds features 52h + 4q .. +3 (cm_offk<kKhN>), so thread (block, slot, i) owns the 16-byte
+// piece at float 4·(its index) of the chunk-major array — that side is one contiguous stream — and
+// the 16-byte piece 13h + q of row-major row 32·block + i (400-byte rows: every piece is aligned).
+// Piece 25 is the chunk-major padding (features 100..103), not part of a row. Pure copies, one owner
+// per piece: the same bits on every run.
+constexpr int kStateSlots = 2 * (kKhN / 4);   // 26
+static_assert(kStateSlots * 32 * 4 == kCmBlkN && cm_offk<kKhN>(0, kKhN) == 128, "chunk-major node block");
+__device__ __forceinline__ bool state_piece(int64_t idx, int n_nodes, int64_t& n, int& piece) {
+    const int i = (int)(idx & 31), slot = (int)((idx >> 5) % kStateSlots);
+    n = (idx >> 5) / kStateSlots * 32 + i;
+    piece = (slot >> 1) + (slot & 1) * (kKhN / 4);
+    return n < n_nodes;
+}
+// P_S → state_out: rows < n_nodes only, 25 pieces each
+__global__ __launch_bounds__(256) void k_state_export(const float4* __restrict__ P_cm, float4* __restrict__ state,
+                                                      int n_nodes, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    int64_t n;
+    int piece;
+    if (state_piece(idx, n_nodes, n, piece) && piece < kFN / 4) state[n * (kFN / 4) + piece] = P_cm[idx];
+}
+// dstate → the dP_S slot: rows < n_nodes from the cotangent; the padding piece and the last block's
+// rows past n_nodes are zero, as store_cm leaves them in every other dP (the array is RN rows long)
+__global__ __launch_bounds__(256) void k_state_import(const float4* __restrict__ dstate, float4* __restrict__ dP_cm,
+                                                      int n_nodes, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    int64_t n;
+    int piece;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (state_piece(idx, n_nodes, n, piece) && piece < kFN / 4) v = dstate[n * (kFN / 4) + piece];
+    dP_cm[idx] = v;
+}
+hipError_t launch_state_export(const float* P_cm, float* state, int n_nodes, hipStream_t st) {
+    const int64_t total = (int64_t)((n_nodes + 31) / 32) * kStateSlots * 32;
+    hipLaunchKernelGGL(k_state_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const float4*>(P_cm), reinterpret_cast<float4*>(state), n_nodes, total);
+    return hipGetLastError();
+}
+hipError_t launch_state_import(const float* dstate, float* dP_cm, int n_nodes, hipStream_t st) {
+    const int64_t total = (int64_t)((n_nodes + 31) / 32) * kStateSlots * 32;
+    hipLaunchKernelGGL(k_state_import, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const float4*>(dstate), reinterpret_cast<float4*>(dP_cm), n_nodes, total);
+    return hipGetLastError();
+}
+
+}  // namespace spw
