@@ -388,28 +388,29 @@ __host__ __device__ __forceinline__ bool drop_keep(uint32_t rowkey, uint32_t fea
 }
 
 // ---------------------------------------------------------------------------------------------
-// Packed (zero-padded) weight copies built by k_prep at the start of every call.
+// Packed (zero-padded) weight copies built by k_prep at the start of every call. Their dimensions and
+// sources: the one table of weights.h (kPacks, host only), in this order.
 enum PackId : int {
-    PK_RM1 = 0, PK_RM2, PK_RM3, PK_W1A,       // [160][160] [in][out]
-    PK_OM1,                                    // [128][128]
-    PK_W1B, PK_W1C,                            // [128][160] [P feature][U/V feature]
-    PK_W2,                                     // [160][160] rmp.1 [in][out]
-    PK_W3A,                                    // [160][128] rmp.2 rows 0..149, row 150 = rmp.2 bias
-    PK_WO1C, PK_WO1A, PK_WO1P,                 // [128][128] omp.0 rows 0-99 / 100-199 / 200-299
-    PK_WO2,                                    // [128][128] omp.1 with permuted columns (x' order)
-    PK_W2T,                                    // [160][160] W2T[k][j] = W2[j][k]
-    PK_W1BT, PK_W1CT,                          // [160][128] W1bT[k][p] = W1b[p][k]
-    PK_WO2T,                                   // [128][128] Wo2pT[k][i] = Wo2p[i][k]
-    PK_WO1CT, PK_WO1AT, PK_WO1PT,              // [128][128] Wo1T_p[k][i] = Wo1[off_p+i][k]
-    PK_W3T,                                    // [128][160] W3T[k][i] = W3[i][k]
-    PK_W1AT, PK_RM3T, PK_RM2T, PK_RM1T,        // [160][160] transposes
-    PK_OM1T,                                   // [128][128]
+    PK_RM1 = 0, PK_RM2, PK_RM3, PK_W1A,       // [in][out]
+    PK_OM1,
+    PK_W1B, PK_W1C,                            // [P feature][U/V feature]
+    PK_W2,                                     // rmp.1 [in][out]
+    PK_W3A,                                    // rmp.2 rows 0..149, row 150 = rmp.2 bias
+    PK_WO1C, PK_WO1A, PK_WO1P,                 // omp.0 rows 0-99 / 100-199 / 200-299
+    PK_WO2,                                    // omp.1 with permuted columns (x' order)
+    PK_W2T,                                    // W2T[k][j] = W2[j][k]
+    PK_W1BT, PK_W1CT,                          // W1bT[k][p] = W1b[p][k]
+    PK_WO2T,                                   // Wo2pT[k][i] = Wo2p[i][k]
+    PK_WO1CT, PK_WO1AT, PK_WO1PT,              // Wo1T_p[k][i] = Wo1[off_p+i][k]
+    PK_W3T,                                    // W3T[k][i] = W3[i][k]
+    PK_W1AT, PK_RM3T, PK_RM2T, PK_RM1T,        // transposes
+    PK_OM1T,
     // biases, padded vectors
-    PB_RM1, PB_RM2, PB_RM3, PB_W1A, PB_W2,     // [160]
-    PB_OM1, PB_O1, PB_O2P,                     // [128]  (PB_O2P permuted like PK_WO2)
-    PK_RM0,                                    // [2][160] rm.0 kernel
-    PK_OM0,                                    // [2][128] om.0 kernel
-    PB_RM0, PB_OM0,                            // [160], [128]
+    PB_RM1, PB_RM2, PB_RM3, PB_W1A, PB_W2,
+    PB_OM1, PB_O1, PB_O2P,                     // (PB_O2P permuted like PK_WO2)
+    PK_RM0,                                    // rm.0 kernel
+    PK_OM0,                                    // om.0 kernel
+    PB_RM0, PB_OM0,
     PK_COUNT
 };
 
@@ -417,32 +418,6 @@ struct PackSlots {
     int64_t off[PK_COUNT];
     int64_t total;
 };
-
-__host__ __device__ inline int pack_rows(int id) {
-    switch (id) {
-        case PK_RM1: case PK_RM2: case PK_RM3: case PK_W1A: case PK_W2: case PK_W2T:
-        case PK_W1AT: case PK_RM3T: case PK_RM2T: case PK_RM1T: case PK_W3A: case PK_W1BT: case PK_W1CT:
-            return 160;
-        case PB_RM1: case PB_RM2: case PB_RM3: case PB_W1A: case PB_W2: case PB_OM1: case PB_O1: case PB_O2P:
-        case PB_RM0: case PB_OM0:
-            return 1;
-        case PK_RM0: case PK_OM0:
-            return 2;
-        default:
-            return 128;
-    }
-}
-__host__ __device__ inline int pack_cols(int id) {
-    switch (id) {
-        case PK_RM1: case PK_RM2: case PK_RM3: case PK_W1A: case PK_W2: case PK_W2T:
-        case PK_W1AT: case PK_RM3T: case PK_RM2T: case PK_RM1T: case PK_W1B: case PK_W1C: case PK_W3T:
-        case PB_RM1: case PB_RM2: case PB_RM3: case PB_W1A: case PB_W2:
-        case PK_RM0: case PB_RM0:
-            return 160;
-        default:
-            return 128;
-    }
-}
 
 // x' (permuted omp.1 output) column f' ↔ Keras column: state f' < 100 ↔ col f'+1, logit ↔ col 0.
 __host__ __device__ __forceinline__ int wo2_perm(int fp) { return fp < 100 ? fp + 1 : (fp == 100 ? 0 : -1); }

@@ -59,29 +59,11 @@ enum X6Id : int {
     X6_W1BT, X6_W1CT, X6_WO2T, X6_WO1PT, X6_WO1CT, X6_WO1AT, X6_W3T,   // its backward
     X6_OM1,                                       // object encoder
     X6_OM1T,                                      // its backward
-    // half-tile forms of the 4-tile images (the chain kernels; the fused team kernels read the above)
+    // half-tile forms of the 4-tile images (the chain kernels; the fused team kernels read the above);
+    // what each image holds: weights.h kX6Rows
     X6_W3A_H, X6_WO1C_H, X6_WO1A_H, X6_WO1P_H, X6_WO2_H,
     X6_W1BT_H, X6_W1CT_H, X6_WO2T_H, X6_WO1PT_H, X6_WO1CT_H, X6_WO1AT_H, X6_OM1_H, X6_OM1T_H,
     X6_COUNT
-};
-// (image, fp32 pack, output tiles, k-blocks, kh, ht) — the images every x6 run builds
-struct X6Spec { int id, pack, nt_out, nkb, kh, ht = 0; };
-constexpr X6Spec kX6Specs[X6_COUNT] = {
-    {X6_RM1, PK_RM1, 5, 10, 0},    {X6_RM2, PK_RM2, 5, 10, 0},    {X6_RM3, PK_RM3, 5, 10, 0},
-    {X6_W1A, PK_W1A, 5, 10, 0},    {X6_W1AT, PK_W1AT, 5, 10, kKhE}, {X6_RM3T, PK_RM3T, 5, 10, 0},
-    {X6_RM2T, PK_RM2T, 5, 10, 0},  {X6_RM1T, PK_RM1T, 5, 10, 0},  {X6_W2, PK_W2, 5, 10, kKhE},
-    {X6_W2T, PK_W2T, 5, 10, kKhE}, {X6_W3A, PK_W3A, 4, 10, kKhE}, {X6_WO1C, PK_WO1C, 4, 7, kKhN},
-    {X6_WO1A, PK_WO1A, 4, 7, 0},   {X6_WO1P, PK_WO1P, 4, 7, kKhN}, {X6_WO2, PK_WO2, 4, 7, 0},
-    {X6_W1B, PK_W1B, 5, 7, 0},     {X6_W1C, PK_W1C, 5, 7, 0},
-    {X6_W1BT, PK_W1BT, 4, 10, kKhE}, {X6_W1CT, PK_W1CT, 4, 10, kKhE}, {X6_WO2T, PK_WO2T, 4, 7, 0},
-    {X6_WO1PT, PK_WO1PT, 4, 7, 0}, {X6_WO1CT, PK_WO1CT, 4, 7, 0}, {X6_WO1AT, PK_WO1AT, 4, 7, 0},
-    {X6_W3T, PK_W3T, 5, 7, 0},     {X6_OM1, PK_OM1, 4, 7, 0},
-    {X6_OM1T, PK_OM1T, 4, 7, 0},
-    {X6_W3A_H, PK_W3A, 4, 10, kKhE, 1}, {X6_WO1C_H, PK_WO1C, 4, 7, kKhN, 1}, {X6_WO1A_H, PK_WO1A, 4, 7, 0, 1},
-    {X6_WO1P_H, PK_WO1P, 4, 7, kKhN, 1}, {X6_WO2_H, PK_WO2, 4, 7, 0, 1},
-    {X6_W1BT_H, PK_W1BT, 4, 10, kKhE, 1}, {X6_W1CT_H, PK_W1CT, 4, 10, kKhE, 1}, {X6_WO2T_H, PK_WO2T, 4, 7, 0, 1},
-    {X6_WO1PT_H, PK_WO1PT, 4, 7, 0, 1}, {X6_WO1CT_H, PK_WO1CT, 4, 7, 0, 1}, {X6_WO1AT_H, PK_WO1AT, 4, 7, 0, 1},
-    {X6_OM1_H, PK_OM1, 4, 7, 0, 1},     {X6_OM1T_H, PK_OM1T, 4, 7, 0, 1},
 };
 // The half-tile form is a build option (-DSPWGNN_HT=1): measured −0.5 % at the
 // headline, and it ends the bitwise equality of the chain and team kernels. Off, its images are empty.
@@ -89,22 +71,11 @@ constexpr X6Spec kX6Specs[X6_COUNT] = {
 #define SPWGNN_HT 0
 #endif
 constexpr bool kHT = SPWGNN_HT != 0;
-// an image that a forward kernel reads (h3: built as f16 parts); no backward kernel reads one of these
-inline bool x6_forward_image(int pack) {
-    switch (pack) {
-        case PK_RM1: case PK_RM2: case PK_RM3: case PK_W1A: case PK_W2: case PK_W3A: case PK_WO1C: case PK_WO1A:
-        case PK_WO1P: case PK_WO2: case PK_W1B: case PK_W1C: case PK_OM1:
-            return true;
-        default:
-            return false;
-    }
-}
-inline int x6_nkb(const X6Spec& s) { return s.ht && !kHT ? 0 : s.nkb; }
 struct X6Desc {
     int32_t pack;       // source fp32 pack (PackId): element (k, col) of it
     int32_t nt_out, nkb;
     int32_t kh, ht;
-    int32_t f16;        // h3 math, an image a forward kernel reads: parts h, m as IEEE halves (x6_forward_image)
+    int32_t f16;        // h3 math, an image a forward kernel reads: parts h, m as IEEE halves (weights.h: fwd)
     int64_t dst;        // uint4 offset into the image buffer
 };
 // the images k_prep builds: the half-tile forms only in kHT builds (kernel-argument space)

@@ -14,7 +14,7 @@ towers (padding edges with index −1, blocks with few real edges), 3 towers of 
 path, which keeps the pointer form in the edge forward / backward). S = 1 makes every U / V gather of
 the W2 gradient a zero-length-descriptor one; bf16 math covers the 2-byte U / V offsets.
 
-The range guard's host function (api.hip: gather_desc_fits) has no entry point reachable without a
+The range guard's host function (path.hip: gather_desc_fits) has no entry point reachable without a
 device; it is covered by reading (one comparison of RN · 152 · 4 against 2^31).
 """
 import functools

@@ -139,7 +139,7 @@ def test_shared_weight_ring_partial_workgroups(T, N):
 @pytest.mark.parametrize("math", ["x6", "f32", "bf16"])
 @pytest.mark.parametrize("n_towers", [8, 3000])   # team kernels / wide kernels
 def test_backward_writes_every_gradient(math, n_towers):
-    """Nothing of the caller's `grads` buffer survives a backward (api.hip run_backward clears it, then
+    """Nothing of the caller's `grads` buffer survives a backward (backward.hip run_backward clears it, then
     the reductions write the 22 Keras tensors): a NaN-filled buffer must come out bitwise equal to a
     zero-filled one. Without the clear, 739 floats stayed NaN (measured on the GPU)."""
     params = O.random_params(seed=13)
