@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense; spwgnn_clip, spwgnn_adam_clipped, spwgnn_adam_clipped_dev, spwgnn_adam_lr_decayed, spwgnn_adam_lr_table_decay; spwgnn_forward_steps, spwgnn_backward_steps, spwgnn_step_weights, spwgnn_bce_steps); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense; spwgnn_clip, spwgnn_adam_clipped, spwgnn_adam_clipped_dev, spwgnn_adam_lr_decayed, spwgnn_adam_lr_table_decay; spwgnn_forward_steps, spwgnn_backward_steps, spwgnn_step_weights, spwgnn_bce_steps; spwgnn_eval, spwgnn_eval_metrics); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
@@ -48,8 +48,8 @@ typedef struct spwgnn_param_info {
 int32_t spwgnn_version(void);
 /* sizeof the ABI structs as this library was compiled (bindings check their own layouts against it):
  * which = 0 spwgnn_batch, 1 spwgnn_run, 2 spwgnn_plan_sizes, 3 spwgnn_param_info,
- * 4 spwgnn_loss_weights, 6 spwgnn_plan_device, 7 spwgnn_clip, 9 spwgnn_step_weights; -1 otherwise (5 and 8
- * are not used and stay -1). */
+ * 4 spwgnn_loss_weights, 6 spwgnn_plan_device, 7 spwgnn_clip, 9 spwgnn_step_weights, 10 spwgnn_eval; -1
+ * otherwise (5 and 8 are not used and stay -1). */
 int32_t spwgnn_struct_size(int32_t which);
 const char* spwgnn_strerror(int32_t status);
 int32_t spwgnn_param_tensor_count(void);
@@ -615,6 +615,49 @@ enum {
 };
 int32_t spwgnn_tower_readout(const float* logits, const int32_t* tower_offsets, int32_t n_towers, int32_t mode,
                              float* out, spwgnn_stream_t stream);
+
+/* Evaluation tables (added within ABI 8: new symbols only). model.evaluate's counts on
+ * the device: the node confusion of (s > 0.5) == c (JengaBuilder.py:333-346), the per-tower and
+ * per-tower-size confusions the paper tabulates and a logit histogram per class for ROC
+ * curves. Every table is caller-zeroed int64 device memory, 8-byte aligned, and is ADDED TO: a data set
+ * evaluated in batches is read once at the end, ranks combine tables by an integer sum. One launch, no
+ * allocation, no synchronisation, no scratch; capturable. Integer sums: the same bits on every run.
+ *
+ * Row r, node i counted (w == NULL or w[i] != 0), z = logits[r][i], t = targets[i]:
+ *   p = 1.f / (1.f + expf(-z))  (spwgnn_bce's expression);  pred = p > threshold (false for a NaN);
+ *   ok = (pred ? 1.f : 0.f) == t;  the cell is TP (pred, ok), FP (pred, !ok), TN (!pred, ok), FN (!pred, !ok)
+ *   — targets are 0 or 1; any other value counts as a wrong prediction on the predicted side.
+ *   With threshold 0.5, TP + TN = out3[1] and the cell sum = out3[2] of spwgnn_bce / spwgnn_bce_weighted.
+ *   bin = isnan(z) ? 0 : (int)floorf((fminf(fmaxf(z, -16.f), 15.9375f) + 16.f) * 8.f): 1/8-logit bins over
+ *   [-16, 16) with the ends clamped; hist[r][t == 1.f][bin] += 1.
+ * Tower u = nodes [tower_offsets[u], tower_offsets[u+1]) (every range is clamped to [0, n) before it is
+ * walked; the offsets are the caller's contract: nondecreasing, from 0 to n). A tower with no counted node
+ * is skipped. Otherwise exact = every counted node ok, pstable = every counted node pred, astable = every
+ * counted t == 1.f; tower6 gets the tower, exact and the (pstable, astable) cell; by_size[r][k], k =
+ * the tower's node count when that is 1..32 and 0 for any other size, gets the tower's node cells, the
+ * tower and exact.
+ * SPWGNN_E_ARG before any device work: a null logits, targets, ev or node4; n < 1; rows outside 1..64; a
+ * threshold that is NaN or outside (0, 1); reserved != 0; n_towers < 0; n_towers > 0 without tower_offsets
+ * or with neither tower6 nor by_size; n_towers == 0 with any of those three set; a table that is not
+ * 8-byte aligned. */
+#define SPWGNN_EVAL_BINS 256
+#define SPWGNN_EVAL_SIZES 33           /* bucket k = towers of k nodes, 1..32; bucket 0 = any other size */
+typedef struct spwgnn_eval {
+    int32_t rows;        /* R in 1..64 logit rows scored against ONE target row: 1, or mp_steps for the
+                            rows of spwgnn_forward_steps */
+    int32_t n_towers;    /* 0 = node tables only */
+    float threshold;     /* tau, finite, 0 < tau < 1; 0.5 is the reference's (JengaBuilder.py:343) */
+    int32_t reserved;    /* 0 */
+    const float* w;              /* [n] per-node weights or NULL; w == 0 masks the node out of EVERY table
+                                    (a select, as in spwgnn_bce_weighted: NaN under it stays out) */
+    const int32_t* tower_offsets;/* [n_towers+1], as spwgnn_tower_readout takes them */
+    int64_t* node4;      /* [R][4]      += TP, TN, FP, FN                       (required)  */
+    int64_t* tower6;     /* [R][6]      += towers, exact, tTP, tTN, tFP, tFN    (NULL = none) */
+    int64_t* by_size;    /* [R][33][6]  += TP, TN, FP, FN, towers, exact        (NULL = none) */
+    int64_t* hist;       /* [R][2][256] += logit histogram per class            (NULL = none) */
+} spwgnn_eval;
+int32_t spwgnn_eval_metrics(const float* logits /* [R][n] */, const float* targets /* [n] */, int64_t n,
+                            const spwgnn_eval* ev, spwgnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -8,5 +8,6 @@ from .batch import TowerBatch
 from .engine import RunConfig
 from .network import GraphNetwork
 from .keras_api import PropagationNetwork, KerasModel
+from . import metrics
 
-__all__ = ["TowerBatch", "RunConfig", "GraphNetwork", "PropagationNetwork", "KerasModel"]
+__all__ = ["TowerBatch", "RunConfig", "GraphNetwork", "PropagationNetwork", "KerasModel", "metrics"]

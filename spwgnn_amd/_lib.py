@@ -80,6 +80,17 @@ class StepWeightsC(C.Structure):
     _fields_ = [("count", C.c_int32), ("reserved", C.c_int32), ("lam", C.c_float * MAX_STEPS)]
 
 
+EVAL_BINS = 256    # SPWGNN_EVAL_BINS: 1/8-logit histogram bins over [-16, 16), the ends clamped
+EVAL_SIZES = 33    # SPWGNN_EVAL_SIZES: tower-size buckets 1..32; bucket 0 = any other size
+
+
+class EvalC(C.Structure):
+    """spwgnn_eval: the options, inputs and int64 tables of spwgnn_eval_metrics (added within ABI 8)."""
+    _fields_ = [("rows", C.c_int32), ("n_towers", C.c_int32), ("threshold", C.c_float), ("reserved", C.c_int32),
+                ("w", C.c_void_p), ("tower_offsets", C.c_void_p), ("node4", C.c_void_p), ("tower6", C.c_void_p),
+                ("by_size", C.c_void_p), ("hist", C.c_void_p)]
+
+
 K_EDGE_FWD, K_NODE_FWD, K_EDGE_BWD, K_NODE_BWD, K_ENC_EDGE, K_ENC_EDGE_BWD, K_WGRAD_W2, K_DA = 1, 2, 3, 4, 5, 6, 7, 8
 K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD, K_INPUT_BWD, K_PLAN_DEVICE, K_STATE = 9, 10, 11, 12, 13, 14
 MATH_F32, MATH_X6, MATH_BF16, MATH_X3, MATH_H3 = 0, 1, 2, 3, 4
@@ -149,6 +160,7 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_copy_in": (i32, [vp, vp, i64, vp]),
         "spwgnn_accumulate_out3": (i32, [vp, vp, vp, vp]),
         "spwgnn_tower_readout": (i32, [vp, vp, i32, i32, vp, vp]),
+        "spwgnn_eval_metrics": (i32, [vp, vp, i64, C.POINTER(EvalC), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -170,7 +182,7 @@ def lib() -> C.CDLL:
             raise SpwgnnError(f"{path} implements ABI {lib_.spwgnn_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild with `python -m spwgnn_amd.build`")
         for which, st in ((0, BatchC), (1, RunC), (2, PlanSizes), (3, ParamInfo), (4, LossWeightsC), (6, PlanDeviceC),
-                          (7, ClipC), (9, StepWeightsC)):
+                          (7, ClipC), (9, StepWeightsC), (10, EvalC)):
             if lib_.spwgnn_struct_size(which) != C.sizeof(st):
                 raise SpwgnnError(f"{path} was built with a different {st.__name__} layout "
                                   f"({lib_.spwgnn_struct_size(which)} vs {C.sizeof(st)} bytes): rebuild it")

@@ -487,4 +487,25 @@ int32_t spwgnn_tower_readout(const float* logits, const int32_t* tower_offsets, 
     return status(launch_tower_readout(logits, tower_offsets, n_towers, mode, out, static_cast<hipStream_t>(stream)));
 }
 
+static_assert(SPWGNN_EVAL_BINS == kEvalBins && SPWGNN_EVAL_SIZES == kEvalSizes, "evaluation table shapes");
+int32_t spwgnn_eval_metrics(const float* logits, const float* targets, int64_t n, const spwgnn_eval* ev,
+                            spwgnn_stream_t stream) {
+    if (int32_t stt = eval_check(logits, targets, n, ev)) return stt;
+    const auto u64 = [](int64_t* t) { return reinterpret_cast<unsigned long long*>(t); };
+    EvalArgs a{};
+    a.logits = logits;
+    a.targets = targets;
+    a.w = ev->w;
+    a.off = ev->tower_offsets;
+    a.n = n;
+    a.R = ev->rows;
+    a.n_towers = ev->n_towers;
+    a.tau = ev->threshold;
+    a.node4 = u64(ev->node4);
+    a.tower6 = u64(ev->tower6);
+    a.by_size = u64(ev->by_size);
+    a.hist = u64(ev->hist);
+    return status(launch_eval_metrics(a, static_cast<hipStream_t>(stream)));
+}
+
 }  // extern "C"

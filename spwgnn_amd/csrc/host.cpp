@@ -48,6 +48,19 @@ const ParamTable& param_table() {
     return t;
 }
 
+// spwgnn_eval_metrics' argument checks (spwgnn.h lists them): no pointer is followed past ev itself,
+// so the CPU suite calls them with addresses that are never read
+int32_t eval_check(const float* logits, const float* targets, int64_t n, const spwgnn_eval* ev) {
+    if (!logits || !targets || !ev || !ev->node4 || n < 1) return SPWGNN_E_ARG;
+    if (ev->rows < 1 || ev->rows > 64 || ev->reserved != 0 || ev->n_towers < 0) return SPWGNN_E_ARG;
+    if (!(ev->threshold > 0.f && ev->threshold < 1.f)) return SPWGNN_E_ARG;   // NaN fails both comparisons
+    const bool tower_tables = ev->tower6 || ev->by_size;
+    if (ev->n_towers > 0 ? (!ev->tower_offsets || !tower_tables) : (ev->tower_offsets || tower_tables)) return SPWGNN_E_ARG;
+    for (const int64_t* t : {ev->node4, ev->tower6, ev->by_size, ev->hist})
+        if (reinterpret_cast<uintptr_t>(t) % 8 != 0) return SPWGNN_E_ARG;
+    return SPWGNN_OK;
+}
+
 }  // namespace spw
 
 using namespace spw;
@@ -66,6 +79,7 @@ int32_t spwgnn_struct_size(int32_t which) {
         case 6: return (int32_t)sizeof(spwgnn_plan_device);   // 5 stays -1
         case 7: return (int32_t)sizeof(spwgnn_clip);
         case 9: return (int32_t)sizeof(spwgnn_step_weights);   // 8 stays -1
+        case 10: return (int32_t)sizeof(spwgnn_eval);
         default: return -1;
     }
 }

@@ -481,6 +481,21 @@ hipError_t launch_sigmoid(const float* z, float* p, int64_t n, hipStream_t st);
 hipError_t launch_accumulate_out3(const float* out3, const double* w, double* tot, hipStream_t st);
 hipError_t launch_copy_in(const void* src, void* dst, int64_t n16, hipStream_t st);
 hipError_t launch_tower_readout(const float* z, const int32_t* off, int n_towers, int mode, float* out, hipStream_t st);
+// k_eval_metrics (kernels_eval.hip; spwgnn_eval_metrics): integer evaluation tables of R logit
+// rows against one target row, added to the caller's int64 tables in one launch
+constexpr int kEvalBins = 256;    // = SPWGNN_EVAL_BINS: 1/8-logit bins over [-16, 16)
+constexpr int kEvalSizes = 33;    // = SPWGNN_EVAL_SIZES: tower-size buckets 1..32, bucket 0 for any other size
+struct EvalArgs {
+    const float *logits, *targets;   // [R][n], [n]
+    const float* w;                  // [n] per-node weights (0 masks the node), or null
+    const int32_t* off;              // [n_towers + 1] tower offsets, or null (n_towers == 0)
+    int64_t n;
+    int R, n_towers;
+    float tau;
+    int node_blocks;                 // workgroups [0, node_blocks) stream the nodes, the rest walk the towers
+    unsigned long long *node4, *tower6, *by_size, *hist;   // [R][4], [R][6], [R][33][6], [R][2][256]; all but node4 may be null
+};
+hipError_t launch_eval_metrics(const EvalArgs& a, hipStream_t st);
 // The propagation state at the library's edge (spwgnn_forward_state / spwgnn_backward_state): P_S in
 // chunk-major node blocks → row-major [n_nodes][100], and a row-major cotangent → the chunk-major dP_S slot
 hipError_t launch_state_export(const float* P_cm, float* state, int n_nodes, hipStream_t st);

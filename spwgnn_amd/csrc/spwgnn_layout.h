@@ -4,7 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
+struct spwgnn_eval;   // include/spwgnn.h
+
 namespace spw {
+
+// spwgnn_eval_metrics' argument checks (host.cpp): SPWGNN_OK, or the status to return before any device work
+int32_t eval_check(const float* logits, const float* targets, int64_t n, const spwgnn_eval* ev);
 
 // ---- model widths (Networks.py:29,46-50) ----
 constexpr int kFE = 150;    // relation widths (rm hidden/out, rmp hidden)

@@ -821,3 +821,113 @@ def tower_readout(logits: torch.Tensor, batch: TowerBatch, mode: str = "sum_prob
                                          READOUT_MODES[mode], out.data_ptr(), _stream(logits.device))
     _lib.check(st, "spwgnn_tower_readout")
     return out
+
+
+class EvalTables:
+    """The int64 tables spwgnn_eval_metrics adds to (include/spwgnn.h), as views of ONE flat buffer — a
+    data-parallel run sums them over the ranks with one all-reduce of `flat`:
+      node4   (rows, 4)        TP, TN, FP, FN over the counted nodes
+      tower6  (rows, 6)        towers, exact, tTP, tTN, tFP, tFN          (``towers``)
+      by_size (rows, 33, 6)    TP, TN, FP, FN, towers, exact per tower size (``towers``)
+      hist    (rows, 2, 256)   the logit histogram per class               (``hist``)
+    ``rows``: 1, or mp_steps for the rows of `forward_steps`. Any device (the oracle engines of the CPU
+    suite keep theirs on the host)."""
+
+    def __init__(self, device, rows: int = 1, towers: bool = True, hist: bool = True):
+        if not 1 <= int(rows) <= _lib.MAX_STEPS:
+            raise ValueError(f"rows must be in 1..{_lib.MAX_STEPS} (got {rows})")
+        self.rows, self.towers, self.has_hist = int(rows), bool(towers), bool(hist)
+        shapes = {"node4": (self.rows, 4)}
+        if self.towers:
+            shapes.update(tower6=(self.rows, 6), by_size=(self.rows, _lib.EVAL_SIZES, 6))
+        if self.has_hist:
+            shapes["hist"] = (self.rows, 2, _lib.EVAL_BINS)
+        sizes = {k: int(torch.Size(s).numel()) for k, s in shapes.items()}
+        self.flat = torch.zeros(sum(sizes.values()), dtype=torch.int64, device=device)
+        self.tables, at = {}, 0
+        for k, s in shapes.items():
+            self.tables[k] = self.flat[at:at + sizes[k]].view(s)
+            at += sizes[k]
+        self.node4 = self.tables["node4"]
+        self.tower6, self.by_size, self.hist = (self.tables.get(k) for k in ("tower6", "by_size", "hist"))
+
+    def zero_(self) -> "EvalTables":
+        self.flat.zero_()
+        return self
+
+    def add_(self, other: "EvalTables") -> "EvalTables":
+        if (other.rows, other.towers, other.has_hist) != (self.rows, self.towers, self.has_hist):
+            raise ValueError("add_ needs tables of the same rows and parts")
+        self.flat.add_(other.flat.to(self.flat.device))
+        return self
+
+    def cpu(self) -> dict:
+        """{name: numpy int64 array} of the tables held (one device read)."""
+        return self.split(self.flat.cpu())
+
+    def split(self, host: torch.Tensor) -> dict:
+        """`cpu()` of a host copy of `flat` the caller made (together with other results, in one read)."""
+        out, at = {}, 0
+        for k, t in self.tables.items():
+            out[k] = host[at:at + t.numel()].view(t.shape).numpy().copy()
+            at += t.numel()
+        return out
+
+
+def check_threshold(threshold) -> float:
+    """The decision threshold of the evaluation calls: a finite float with 0 < tau < 1."""
+    tau = float(threshold)
+    if not 0.0 < tau < 1.0:   # False for a NaN
+        raise ValueError(f"threshold must lie strictly between 0 and 1 (got {threshold})")
+    return tau
+
+
+def eval_metrics(logits: torch.Tensor, targets: torch.Tensor, tables: EvalTables, batch: Optional[TowerBatch] = None,
+                 node_weights: Optional[torch.Tensor] = None, threshold: float = 0.5) -> EvalTables:
+    """Adds the evaluation counts of ``logits`` against ``targets`` to ``tables`` on the device, in one launch
+    and without a host sync (spwgnn_eval_metrics). ``logits``: (n,) or (R, n) contiguous fp32, R =
+    tables.rows (the rows of `forward_steps`); ``targets``: one 0/1 value per node, in the logits' order
+    (for packed plans the plan's: `TowerBatch.to_plan_order`). ``batch`` gives the tower offsets and is
+    required when the tables hold the tower parts. ``node_weights``: one weight per node; a zero masks
+    the node out of every table. ``threshold``: the node is predicted stable when sigmoid(z) > threshold."""
+    _require_gpu(logits, "logits")
+    if logits.dim() not in (1, 2) or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("logits must be a contiguous fp32 (n,) or (rows, n) tensor")
+    R, n = (1, int(logits.shape[0])) if logits.dim() == 1 else (int(logits.shape[0]), int(logits.shape[1]))
+    if not isinstance(tables, EvalTables) or tables.rows != R:
+        raise ValueError(f"tables must be EvalTables built for {R} row(s)")
+    if tables.flat.device != logits.device:
+        raise ValueError(f"the tables must be on the logits' device {logits.device} (got {tables.flat.device})")
+    if n < 1:
+        raise ValueError("logits holds no node")
+    tau = check_threshold(threshold)
+    targets = targets.reshape(-1).to(torch.float32).contiguous()
+    if targets.numel() != n or targets.device != logits.device:
+        raise ValueError(f"targets must hold one value per node ({n}) on {logits.device}, got {targets.numel()} on "
+                         f"{targets.device}")
+    ev = _lib.EvalC()
+    ev.rows, ev.threshold = R, tau
+    w = None
+    if node_weights is not None:
+        _require_gpu(node_weights, "node_weights")
+        w = node_weights.reshape(-1).to(torch.float32).contiguous()
+        if w.numel() != n or w.device != logits.device:
+            raise ValueError(f"node_weights must hold one weight per node ({n}) on {logits.device}")
+        ev.w = w.data_ptr()
+    off = None
+    if tables.towers:
+        if batch is None:
+            raise ValueError("tables with the tower parts need the batch (its tower offsets)")
+        if batch.n_nodes != n:
+            raise ValueError(f"the batch holds {batch.n_nodes} nodes, the logits {n}")
+        off = batch.tower_offsets
+        if off.device != logits.device or off.dtype != torch.int32 or off.numel() != batch.n_towers + 1:
+            raise ValueError("the batch's tower offsets must be (n_towers + 1,) int32 on the logits' device")
+        ev.n_towers, ev.tower_offsets = int(batch.n_towers), off.data_ptr()
+        ev.tower6, ev.by_size = tables.tower6.data_ptr(), tables.by_size.data_ptr()
+    ev.node4 = tables.node4.data_ptr()
+    if tables.has_hist:
+        ev.hist = tables.hist.data_ptr()
+    st = _lib.lib().spwgnn_eval_metrics(logits.data_ptr(), targets.data_ptr(), n, C.byref(ev), _stream(logits.device))
+    _lib.check(st, "spwgnn_eval_metrics")
+    return tables

@@ -278,6 +278,77 @@ class KerasModel:
         out3, _ = E.bce(z, target, self._bce, node_weights=self._dev_weights(node_weights), norm=norm)
         return out3
 
+    def evaluate(self, x: Dict[str, np.ndarray], y, batch_size: int = 32768, sample_weight=None,
+                 threshold: float = 0.5, return_dict: bool = False, return_steps: bool = False):
+        """Keras evaluate: ``[loss, binary_accuracy]`` of the model on (x, y) — y the fit's {'target': ...} or
+        the array itself — counted on the device (engine.eval_metrics): per batch the inference forward, the
+        accumulating loss (fp64 sums with weights (towers of the batch, 1, 1), fit's convention: the loss
+        is the tower-weighted mean of the batch losses) and the metrics launch; the host reads the device
+        once, after the last batch.
+
+        ``return_dict``: metrics.summarize of the tables (node, tower and per-tower-size confusion, ROC area,
+        average precision, best threshold) plus ``loss``. ``threshold``: a node is predicted stable when its
+        probability exceeds it (0.5: the reference's, JengaBuilder.py:343); the loss does not depend on it.
+        ``sample_weight`` ((B,) or (B, N)) as in `fit`: the loss is weighted per batch by Σ w·bce / #{w ≠ 0} and
+        a zero weight masks its node out of every count. ``return_steps``: a list of mp_steps summaries, the
+        logits read out after each propagation step scored against the same targets (with or without
+        step_loss_weights); entry s carries that step's own ``loss``, and the last entry is the plain summary.
+        With step_loss_weights the model's loss is Σ_s λ_s·loss_s, as in `fit`: it is the last entry's ``loss``,
+        and every entry carries its own as ``step_loss``."""
+        from . import metrics as M
+        objects = np.asarray(x["objects"], np.float32)
+        B = objects.shape[0]
+        target = np.asarray(y["target"] if isinstance(y, dict) else y, np.float32).reshape(B, -1)
+        tau = E.check_threshold(threshold)
+        W = node_weights(target, sample_weight) if sample_weight is not None else None
+        Rs, Rr, prop = np.asarray(x["sender_relations"]), np.asarray(x["receiver_relations"]), x.get("propagation")
+        dev, net, S = self.net.device, self.net, self.net.mp_steps
+        lam = self.step_loss_weights
+        by_steps = return_steps or lam is not None
+        if by_steps:   # every step's loss rides in the one loss launch; λ = e_{S−1} gives the plain loss's bits
+            lam_eval = lam if lam is not None else (0.0,) * (S - 1) + (1.0,)
+            steps_scratch = self._bce_steps if self._bce_steps is not None else E.BceStepsScratch(dev, S)
+            tot_s = torch.zeros(S, 3, dtype=torch.float64, device=dev)
+        tables = E.EvalTables(dev, rows=S if return_steps else 1)
+        tot = torch.zeros(3, dtype=torch.float64, device=dev)
+        run = net.run_config()
+        for b0 in range(0, B, batch_size):
+            idx = slice(b0, min(B, b0 + batch_size))
+            batch = TowerBatch.from_dense(objects[idx], Rs[idx], Rr[idx], None if prop is None else np.asarray(prop)[idx],
+                                          device=dev)   # predict's batches: the plan fit's validation batch has
+            tgt = torch.as_tensor(target[idx], device=dev).reshape(-1).contiguous()
+            w = self._dev_weights(W[idx]) if W is not None else None
+            norm = max(int(np.count_nonzero(W[idx])), 1) if W is not None else None   # counted on the host
+            if batch.n_towers not in self._w3:
+                self._w3[batch.n_towers] = torch.tensor([float(batch.n_towers), 1.0, 1.0], dtype=torch.float64, device=dev)
+            w3 = self._w3[batch.n_towers]
+            if by_steps:
+                z = E.forward_steps(net.flat.data, batch, run, self._ws)
+                E.bce_steps(z, tgt, lam_eval, steps_scratch, total3=tot, weights3=w3, total3s=tot_s, node_weights=w,
+                            norm=norm)
+                if not return_steps:
+                    z = z[S - 1]
+            else:
+                z = E.forward(net.flat.data, batch, run, self._ws)
+                E.bce(z, tgt, self._bce, total3=tot, weights3=w3, node_weights=w, norm=norm)
+            E.eval_metrics(z, tgt, tables, batch=batch, node_weights=w, threshold=tau)
+        # the one device read: the integer tables and the bits of the fp64 loss sums in one copy
+        sums = [tot.view(torch.int64)] + ([tot_s.reshape(-1).view(torch.int64)] if by_steps else [])
+        host = torch.cat([tables.flat] + sums).cpu()
+        nt = tables.flat.numel()
+        counts = tables.split(host[:nt])
+        loss = float(host[nt:nt + 3].view(torch.float64)[0]) / max(B, 1)
+        if not return_steps:
+            out = dict(M.summarize(counts), loss=loss)
+            return out if return_dict else [loss, out["binary_accuracy"]]
+        step_loss = (host[nt + 3:].view(torch.float64).reshape(S, 3)[:, 0] / max(B, 1)).tolist()
+        outs = [dict(M.summarize(counts, row=s), loss=step_loss[s]) for s in range(S)]
+        if lam is not None:
+            for s in range(S):
+                outs[s]["step_loss"] = step_loss[s]
+            outs[-1]["loss"] = loss
+        return outs
+
     def fit(self, x: Dict[str, np.ndarray], y: Dict[str, np.ndarray], batch_size: int = 32, epochs: int = 10,
             validation_split: float = 0.0, shuffle: bool = True, verbose: int = 1, seed: int = 0,
             graph: bool = False, sample_weight=None, class_weight=None):

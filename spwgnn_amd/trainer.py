@@ -96,6 +96,11 @@ class HipEngine:
         g, _ = E.backward(params, batch, run, self.ws, dlogits, grads=self.grads)
         return g
 
+    def eval_metrics(self, logits, target, tables, batch, weights=None, threshold=0.5):
+        """The evaluation counts of `logits` (the rows `forward` returned) added to `tables` on the device
+        (engine.eval_metrics)."""
+        return E.eval_metrics(logits, target, tables, batch=batch, node_weights=weights, threshold=threshold)
+
     def early_event(self):
         """The event the library records once the early gradient range is final
         (spwgnn_run.grads_early_event); created (recorded once) on first use."""
@@ -378,6 +383,66 @@ class Trainer:
                          device=self.params.device if dist.get_backend(self.group) != "gloo" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
         return int(t.item())
+
+    def _sum_ranks(self, t: torch.Tensor) -> torch.Tensor:
+        """t ← Σ over ranks of t, in place (one all-reduce; the identity without a process group)."""
+        if not self.distributed:
+            return t
+        if t.is_cuda and dist.get_backend(self.group) == "gloo":
+            h = t.cpu()
+            dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.group)
+            return t.copy_(h)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return t
+
+    def evaluate(self, batches, targets, weights=None, threshold: float = 0.5) -> dict:
+        """The model's metrics over the GLOBAL evaluation set, of which `batches` / `targets` (one or a list:
+        micro-batches) are this rank's shard: an inference run (no dropout, nothing stored, no step taken)
+        whose integer tables (engine.EvalTables) are filled on the device and summed over the ranks with one
+        all-reduce; the fp64 pair [Σ loss·n, n] takes a second. Returns metrics.summarize of the summed tables
+        plus ``loss`` (the node-weighted mean of the micro-batch losses) — the same dict on every rank.
+
+        `weights` (one per micro-batch, a weight per node): the weighted loss of `step`, each micro-batch's
+        divided by its own non-zero count, which is also its n in the pair; a zero weight masks its node out
+        of every count. `threshold`: a node is predicted stable when its probability exceeds it. With
+        step_loss_weights the engine's (mp_steps, n) rows are all scored: the dict describes the last step,
+        ``loss`` is Σ_s λ_s·loss_s and ``steps`` lists every step's summary. The engine needs
+        `eval_metrics(logits, target, tables, batch, weights, threshold)`."""
+        from . import metrics as M
+        batches = batches if isinstance(batches, (list, tuple)) else [batches]
+        targets = targets if isinstance(targets, (list, tuple)) else [targets]
+        if len(batches) != len(targets) or not batches:
+            raise ValueError("one target per micro-batch")
+        if weights is not None:
+            weights = weights if isinstance(weights, (list, tuple)) else [weights]
+            if len(weights) != len(batches):
+                raise ValueError("one weight tensor per micro-batch")
+        if not hasattr(self.engine, "eval_metrics"):
+            raise ValueError("evaluate needs an engine with eval_metrics(logits, target, tables, batch, weights, threshold)")
+        tau = E.check_threshold(threshold)
+        rows = self.mp_steps if self.step_loss_weights is not None else 1
+        run = E.RunConfig(self.mp_steps, training=False, dropout=0.0, math=self.math)
+        tables = E.EvalTables(self.params.device, rows=rows)
+        sums = torch.zeros(2, dtype=torch.float64, device=self.params.device)   # Σ loss·n, n
+        for i, (b, tg) in enumerate(zip(batches, targets)):
+            z = self.engine.forward(self.params, b, run)
+            if weights is None:
+                wt = None
+                out3, _ = self.engine.loss(z, tg)
+            else:
+                wt = weights[i]
+                out3, _ = self.engine.loss_weighted(z, tg, wt, max(int(torch.count_nonzero(torch.as_tensor(wt)).item()), 1))
+            n_i = out3[2].to(sums)           # the nodes that count: all of them, or those with w ≠ 0
+            sums += torch.stack([out3[0].to(sums) * n_i, n_i])   # before the engine reuses its out3 buffer
+            self.engine.eval_metrics(z, tg, tables, b, wt, tau)
+        self._sum_ranks(tables.flat)
+        self._sum_ranks(sums)
+        counts = tables.cpu()
+        loss_n, n = sums.tolist()
+        out = dict(M.summarize(counts), loss=loss_n / n if n else float("nan"))
+        if rows > 1:
+            out["steps"] = [M.summarize(counts, row=s) for s in range(rows)]
+        return out
 
     def step(self, batch, target, n_global: Optional[int] = None, weights=None, norm_global: Optional[int] = None):
         """One optimizer step. `batch`/`target` may be lists (micro-batches of this rank's shard);
