@@ -155,6 +155,13 @@ class Workspace:
         return (self.buf is not None and self.fwd_batch is not None and self.fwd_batch() is batch
                 and self.fwd_key == Workspace.key(batch, run))
 
+    def stored(self, batch: TowerBatch, run: "RunConfig", ok: bool, has_state: bool):
+        """What a forward that returned `ok` left here (a failed one: nothing a backward may read)."""
+        self.fwd_key = Workspace.key(batch, run) if ok else None
+        self.fwd_batch = weakref.ref(batch) if ok else None
+        self.bwd_key = None
+        self.has_state = bool(has_state) and ok
+
     def get(self, nbytes: int) -> torch.Tensor:
         if self.buf is None or self.buf.numel() < nbytes:
             self.buf = None
@@ -251,8 +258,7 @@ def _check_dstate(ws: Workspace, batch: TowerBatch, dstate: torch.Tensor) -> tor
 
 
 def _out_buffer(t: torch.Tensor, shape: tuple, what: str) -> torch.Tensor:
-    """A caller's output buffer, validated as `forward` validates ``state``: on the GPU, fp32, contiguous,
-    of exactly `shape`."""
+    """A caller's output buffer, validated: on the GPU, fp32, contiguous, of exactly `shape`."""
     _require_gpu(t, what)
     if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous():
         raise ValueError(f"{what} must be a contiguous fp32 {tuple(shape)} tensor")
@@ -268,6 +274,61 @@ def _dprop_buffer(batch: TowerBatch, dprop: Optional[torch.Tensor], want_dprop: 
     return None
 
 
+def _check_params(flat_params: torch.Tensor):
+    _require_gpu(flat_params, "params")
+    if flat_params.dtype != torch.float32 or not flat_params.is_contiguous() or flat_params.numel() != P.flat_size():
+        raise ValueError("params must be a contiguous fp32 flat buffer of spwgnn_param_count() floats")
+
+
+def _training_forward(ws: Workspace, batch: TowerBatch, run: RunConfig, dstate: Optional[torch.Tensor] = None):
+    """The guard of every backward: `ws` holds the training forward of `batch` and `run` (and, for a state
+    cotangent, its final state). Returns the checked ``dstate``."""
+    if not run.training:
+        raise _lib.SpwgnnError("backward needs a training forward on the same workspace")
+    if dstate is not None:
+        dstate = _check_dstate(ws, batch, dstate)
+    if not ws.holds(batch, run):
+        # the backward reads what the forward stored (masks, activations, packed weights); the split-
+        # bf16 maths do not store z1/zo1 at all, so a mismatched math or step count reads garbage
+        raise _lib.SpwgnnError("backward needs the training forward of the same batch and RunConfig "
+                               f"on this workspace (stored {ws.fwd_key}, asked {Workspace.key(batch, run)})")
+    return dstate
+
+
+def _check_sums(total3: Optional[torch.Tensor], weights3: Optional[torch.Tensor]):
+    """The epoch sums of the accumulating losses: both or neither, float64."""
+    if (total3 is None) != (weights3 is None):
+        raise ValueError("total3 and weights3 go together")
+    if total3 is not None:
+        assert total3.dtype == torch.float64 and weights3.dtype == torch.float64
+
+
+def _forward(symbol: str, takes_state: bool, flat_params, batch, run, ws, out, shape, what, return_state, state):
+    """`forward` / `forward_steps`: ``out`` (or a fresh buffer) of `shape` written by the library's `symbol`,
+    whose argument list has a state pointer when `takes_state`."""
+    _check_params(flat_params)
+    buf = ws.get(workspace_bytes(batch, run))
+    if out is None:
+        out = _poison(torch.empty(shape, dtype=torch.float32, device=batch.device))
+    else:
+        _out_buffer(out, shape, what)
+    if not return_state:
+        if state is not None:
+            raise ValueError("a state buffer goes with return_state=True")
+    elif state is None:
+        state = _poison(torch.empty(batch.n_nodes, STATE_WIDTH, dtype=torch.float32, device=batch.device))
+    else:
+        _out_buffer(state, (batch.n_nodes, STATE_WIDTH), "state")
+    b = batch.cstruct()
+    r = run.cstruct(with_prologue=True)
+    tail = (state.data_ptr() if return_state else None,) if takes_state else ()
+    st = getattr(_lib.lib(), symbol)(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
+                                     out.data_ptr(), *tail, _stream(batch.device))
+    ws.stored(batch, run, st == 0, return_state)
+    _lib.check(st, symbol)
+    return (out, state) if return_state else out
+
+
 def forward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
             logits: Optional[torch.Tensor] = None, return_state: bool = False,
             state: Optional[torch.Tensor] = None):
@@ -275,36 +336,44 @@ def forward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Wo
     in the plan's node order (spwgnn_forward_state) — what the next call takes as its ``prop`` — as
     ``(logits, state)``; the logits are the same bits either way. ``state``: the buffer to write it to
     (a captured forward's static output, like ``logits``)."""
-    _require_gpu(flat_params, "params")
-    if flat_params.dtype != torch.float32 or not flat_params.is_contiguous() or flat_params.numel() != P.flat_size():
-        raise ValueError("params must be a contiguous fp32 flat buffer of spwgnn_param_count() floats")
-    nbytes = workspace_bytes(batch, run)
-    buf = ws.get(nbytes)
-    if logits is None:
-        logits = _poison(torch.empty(batch.n_nodes, dtype=torch.float32, device=batch.device))
+    return _forward("spwgnn_forward_state" if return_state else "spwgnn_forward", return_state, flat_params, batch,
+                    run, ws, logits, (batch.n_nodes,), "logits", return_state, state)
+
+
+def forward_steps(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
+                  step_logits: Optional[torch.Tensor] = None, return_state: bool = False,
+                  state: Optional[torch.Tensor] = None):
+    """`forward` with every propagation step's logits (spwgnn_forward_steps): (mp_steps, n_nodes) fp32, row
+    s = the readout after step s + 1 steps, nodes in the plan's order; the last row holds `forward`'s
+    bits. ``step_logits`` / ``state``: the buffers to write to (a captured forward's static outputs).
+    With ``return_state`` returns ``(step_logits, state)``."""
+    return _forward("spwgnn_forward_steps", True, flat_params, batch, run, ws, step_logits,
+                    (int(run.mp_steps), batch.n_nodes), "step_logits", return_state, state)
+
+
+def _backward(symbol: str, takes_dstate: bool, flat_params, batch, run, ws, dlogits, rows, grads, want_dprop, dstate,
+              dprop):
+    """`backward` / `backward_steps` through the library's `symbol`, whose argument list has a state
+    cotangent when `takes_dstate`. `rows`: the (mp_steps, n_nodes) shape ``dlogits`` must have, or None."""
+    dstate = _training_forward(ws, batch, run, dstate)
+    if rows is not None and (not isinstance(dlogits, torch.Tensor) or tuple(dlogits.shape) != rows):
+        raise ValueError(f"dstep_logits must be a {rows} tensor: one row of logit cotangents per propagation step "
+                         f"(got {tuple(getattr(dlogits, 'shape', ()))})")
+    _require_gpu(dlogits, "dstep_logits" if rows is not None else "dlogits")
+    dlogits = dlogits.to(torch.float32).contiguous()
+    if grads is None:
+        grads = _poison(torch.empty_like(flat_params))
+    dprop = _dprop_buffer(batch, dprop, want_dprop)
     b = batch.cstruct()
-    r = run.cstruct(with_prologue=True)
-    if not return_state:
-        if state is not None:
-            raise ValueError("a state buffer goes with return_state=True")
-    elif state is None:
-        state = _poison(torch.empty(batch.n_nodes, STATE_WIDTH, dtype=torch.float32, device=batch.device))
-    else:
-        _require_gpu(state, "state")
-        if tuple(state.shape) != (batch.n_nodes, STATE_WIDTH) or state.dtype != torch.float32 or not state.is_contiguous():
-            raise ValueError(f"state must be a contiguous fp32 ({batch.n_nodes}, {STATE_WIDTH}) tensor")
-    if return_state:
-        st = _lib.lib().spwgnn_forward_state(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(),
-                                             buf.numel(), logits.data_ptr(), state.data_ptr(), _stream(batch.device))
-    else:
-        st = _lib.lib().spwgnn_forward(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
-                                       logits.data_ptr(), _stream(batch.device))
-    ws.fwd_key = Workspace.key(batch, run) if st == 0 else None
-    ws.fwd_batch = weakref.ref(batch) if st == 0 else None
-    ws.bwd_key = None
-    ws.has_state = bool(return_state) and st == 0
-    _lib.check(st, "spwgnn_forward_state" if return_state else "spwgnn_forward")
-    return (logits, state) if return_state else logits
+    r = run.cstruct()
+    buf = ws.buf
+    mid = (dstate.data_ptr() if dstate is not None else None,) if takes_dstate else ()
+    st = getattr(_lib.lib(), symbol)(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
+                                     dlogits.data_ptr(), *mid, grads.data_ptr(),
+                                     dprop.data_ptr() if dprop is not None else None, _stream(batch.device))
+    ws.bwd_key = ws.fwd_key if st == 0 else None
+    _lib.check(st, symbol)
+    return grads, dprop
 
 
 def backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace, dlogits: torch.Tensor,
@@ -315,74 +384,8 @@ def backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: W
     this workspace must then have been ``forward(..., return_state=True)``. A caller with a loss on the
     state alone passes zero ``dlogits``. ``dprop``: the (n_nodes, 100) buffer to write d/d'propagation' to
     (it implies ``want_dprop``). Returns (grads, dprop)."""
-    if not run.training:
-        raise _lib.SpwgnnError("backward needs a training forward on the same workspace")
-    if dstate is not None:
-        dstate = _check_dstate(ws, batch, dstate)
-    if not ws.holds(batch, run):
-        # the backward reads what the forward stored (masks, activations, packed weights); the split-
-        # bf16 maths do not store z1/zo1 at all, so a mismatched math or step count reads garbage
-        raise _lib.SpwgnnError("backward needs the training forward of the same batch and RunConfig "
-                               f"on this workspace (stored {ws.fwd_key}, asked {Workspace.key(batch, run)})")
-    dlogits = dlogits.contiguous().to(torch.float32)
-    _require_gpu(dlogits, "dlogits")
-    if grads is None:
-        grads = _poison(torch.empty_like(flat_params))
-    dprop = _dprop_buffer(batch, dprop, want_dprop)
-    b = batch.cstruct()
-    r = run.cstruct()
-    buf = ws.buf
-    dprop_ptr = dprop.data_ptr() if dprop is not None else None
-    if dstate is not None:
-        st = _lib.lib().spwgnn_backward_state(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(),
-                                              buf.numel(), dlogits.data_ptr(), dstate.data_ptr(), grads.data_ptr(),
-                                              dprop_ptr, _stream(batch.device))
-    else:
-        st = _lib.lib().spwgnn_backward(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
-                                        dlogits.data_ptr(), grads.data_ptr(), dprop_ptr, _stream(batch.device))
-    ws.bwd_key = ws.fwd_key if st == 0 else None
-    _lib.check(st, "spwgnn_backward_state" if dstate is not None else "spwgnn_backward")
-    return grads, dprop
-
-
-def forward_steps(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
-                  step_logits: Optional[torch.Tensor] = None, return_state: bool = False,
-                  state: Optional[torch.Tensor] = None):
-    """`forward` with every propagation step's logits (spwgnn_forward_steps): (mp_steps, n_nodes) fp32, row
-    s = the readout after step s + 1 steps, nodes in the plan's order; the last row holds `forward`'s
-    bits. ``step_logits`` / ``state``: the buffers to write to (a captured forward's static outputs).
-    With ``return_state`` returns ``(step_logits, state)``."""
-    _require_gpu(flat_params, "params")
-    if flat_params.dtype != torch.float32 or not flat_params.is_contiguous() or flat_params.numel() != P.flat_size():
-        raise ValueError("params must be a contiguous fp32 flat buffer of spwgnn_param_count() floats")
-    buf = ws.get(workspace_bytes(batch, run))
-    shape = (int(run.mp_steps), batch.n_nodes)
-    if step_logits is None:
-        step_logits = _poison(torch.empty(shape, dtype=torch.float32, device=batch.device))
-    else:
-        _require_gpu(step_logits, "step_logits")
-        if tuple(step_logits.shape) != shape or step_logits.dtype != torch.float32 or not step_logits.is_contiguous():
-            raise ValueError(f"step_logits must be a contiguous fp32 {shape} tensor")
-    if not return_state:
-        if state is not None:
-            raise ValueError("a state buffer goes with return_state=True")
-    elif state is None:
-        state = _poison(torch.empty(batch.n_nodes, STATE_WIDTH, dtype=torch.float32, device=batch.device))
-    else:
-        _require_gpu(state, "state")
-        if tuple(state.shape) != (batch.n_nodes, STATE_WIDTH) or state.dtype != torch.float32 or not state.is_contiguous():
-            raise ValueError(f"state must be a contiguous fp32 ({batch.n_nodes}, {STATE_WIDTH}) tensor")
-    b = batch.cstruct()
-    r = run.cstruct(with_prologue=True)
-    st = _lib.lib().spwgnn_forward_steps(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
-                                         step_logits.data_ptr(), state.data_ptr() if return_state else None,
-                                         _stream(batch.device))
-    ws.fwd_key = Workspace.key(batch, run) if st == 0 else None
-    ws.fwd_batch = weakref.ref(batch) if st == 0 else None
-    ws.bwd_key = None
-    ws.has_state = bool(return_state) and st == 0
-    _lib.check(st, "spwgnn_forward_steps")
-    return (step_logits, state) if return_state else step_logits
+    return _backward("spwgnn_backward_state" if dstate is not None else "spwgnn_backward", dstate is not None,
+                     flat_params, batch, run, ws, dlogits, None, grads, want_dprop, dstate, dprop)
 
 
 def backward_steps(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
@@ -393,32 +396,8 @@ def backward_steps(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig,
     the cotangent of step s's logits (`forward_steps`' rows). The forward on this workspace may be any of
     `forward` / `forward_steps`; ``dstate`` needs ``return_state=True`` there. ``dprop`` as in `backward`.
     Returns (grads, dprop)."""
-    if not run.training:
-        raise _lib.SpwgnnError("backward needs a training forward on the same workspace")
-    if dstate is not None:
-        dstate = _check_dstate(ws, batch, dstate)
-    if not ws.holds(batch, run):
-        raise _lib.SpwgnnError("backward needs the training forward of the same batch and RunConfig "
-                               f"on this workspace (stored {ws.fwd_key}, asked {Workspace.key(batch, run)})")
-    shape = (int(run.mp_steps), batch.n_nodes)
-    if not isinstance(dstep_logits, torch.Tensor) or tuple(dstep_logits.shape) != shape:
-        raise ValueError(f"dstep_logits must be a {shape} tensor: one row of logit cotangents per propagation step "
-                         f"(got {tuple(getattr(dstep_logits, 'shape', ()))})")
-    _require_gpu(dstep_logits, "dstep_logits")
-    dstep_logits = dstep_logits.to(torch.float32).contiguous()
-    if grads is None:
-        grads = _poison(torch.empty_like(flat_params))
-    dprop = _dprop_buffer(batch, dprop, want_dprop)
-    b = batch.cstruct()
-    r = run.cstruct()
-    buf = ws.buf
-    st = _lib.lib().spwgnn_backward_steps(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
-                                          dstep_logits.data_ptr(), dstate.data_ptr() if dstate is not None else None,
-                                          grads.data_ptr(), dprop.data_ptr() if dprop is not None else None,
-                                          _stream(batch.device))
-    ws.bwd_key = ws.fwd_key if st == 0 else None
-    _lib.check(st, "spwgnn_backward_steps")
-    return grads, dprop
+    return _backward("spwgnn_backward_steps", True, flat_params, batch, run, ws, dstep_logits,
+                     (int(run.mp_steps), batch.n_nodes), grads, want_dprop, dstate, dprop)
 
 
 def backward_inputs(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
@@ -458,23 +437,16 @@ def bce_backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, w
     With `node_weights` / `norm` (see `bce`) the weighted loss (spwgnn_bce_backward_weighted), whose
     loss launch always runs first. ``logits`` holds one value per node of the batch (the folded loss indexes
     it by plan node). ``dprop`` as in `backward`. Returns (out3, dlogits, grads, dprop)."""
-    if not run.training:
-        raise _lib.SpwgnnError("backward needs a training forward on the same workspace")
     if logits.numel() != batch.n_nodes:
         raise ValueError(f"logits must hold one value per node of the batch ({batch.n_nodes}), got {logits.numel()}")
-    if not ws.holds(batch, run):
-        raise _lib.SpwgnnError("backward needs the training forward of the same batch and RunConfig "
-                               f"on this workspace (stored {ws.fwd_key}, asked {Workspace.key(batch, run)})")
+    _training_forward(ws, batch, run)
     targets = targets.reshape(-1).to(torch.float32).contiguous()
     _require_gpu(logits, "logits")
     if dlogits is None:
         dlogits = _poison(torch.empty_like(logits))
     if grads is None:
         grads = _poison(torch.empty_like(flat_params))
-    if (total3 is None) != (weights3 is None):
-        raise ValueError("total3 and weights3 go together")
-    if total3 is not None:
-        assert total3.dtype == torch.float64 and weights3.dtype == torch.float64
+    _check_sums(total3, weights3)
     dprop = _dprop_buffer(batch, dprop, want_dprop)
     b = batch.cstruct()
     r = run.cstruct()
@@ -550,11 +522,8 @@ def bce(logits: torch.Tensor, targets: torch.Tensor, scratch: BceScratch, dlogit
     targets = targets.reshape(-1).to(torch.float32).contiguous()
     if dlogits is None:
         dlogits = _poison(torch.empty_like(logits))
+    _check_sums(total3, weights3)
     if node_weights is not None:
-        if (total3 is None) != (weights3 is None):
-            raise ValueError("total3 and weights3 go together")
-        if total3 is not None:
-            assert total3.dtype == torch.float64 and weights3.dtype == torch.float64
         lw, _keep = _loss_weights(node_weights, norm, logits)
         st = _lib.lib().spwgnn_bce_weighted(
             logits.data_ptr(), targets.data_ptr(), logits.numel(), C.byref(lw), scratch.out3.data_ptr(),
@@ -570,7 +539,6 @@ def bce(logits: torch.Tensor, targets: torch.Tensor, scratch: BceScratch, dlogit
         st = _lib.lib().spwgnn_bce(*args, _stream(logits.device))
         _lib.check(st, "spwgnn_bce")
     else:
-        assert total3.dtype == torch.float64 and weights3 is not None and weights3.dtype == torch.float64
         st = _lib.lib().spwgnn_bce_accumulate(*args, weights3.data_ptr(), total3.data_ptr(), _stream(logits.device))
         _lib.check(st, "spwgnn_bce_accumulate")
     return scratch.out3, dlogits
@@ -633,8 +601,7 @@ def bce_steps(step_logits: torch.Tensor, targets: torch.Tensor, step_weights, sc
         dlogits = _poison(torch.empty_like(step_logits))
     elif tuple(dlogits.shape) != (S, n) or dlogits.dtype != torch.float32 or not dlogits.is_contiguous():
         raise ValueError(f"dlogits must be a contiguous fp32 ({S}, {n}) tensor")
-    if (total3 is None) != (weights3 is None):
-        raise ValueError("total3 and weights3 go together")
+    _check_sums(total3, weights3)
     if total3s is not None and total3 is None:
         raise ValueError("total3s goes with total3 and weights3")
     for t, shp in ((total3, (3,)), (weights3, (3,)), (total3s, (S, 3))):

@@ -21,7 +21,8 @@ from . import engine as E
 from . import params as P
 from .batch import HostPlan, TowerBatch
 from .network import GraphNetwork
-from .replay import DeviceCounters, ReplayCache
+from .replay import DeviceCounters, ReplayCache, step_body
+from .step import AdamUpdate, DeepLossPath, LossPath, delegated
 
 
 def node_weights(target, sample_weight=None, class_weight=None) -> np.ndarray:
@@ -117,27 +118,22 @@ class KerasModel:
             raise ValueError("only object_dim=3 ([x, y, width]) is supported, as in the working reference path")
         self.net = net
         self.n_objects = n_objects
-        self.lr, self.l2 = lr, l2
-        self.beta1, self.beta2, self.eps = 0.9, 0.999, 1e-7
+        dev = net.device
         # Keras 2.x Adam(lr, decay, clipnorm, clipvalue) and the non-finite guard (0 / False = off): with
         # any of them set every step's update is engine.adam_clipped(_dev), one launch more
-        E.check_clip_options(clipnorm, clipvalue, decay)
-        self.clipnorm, self.clipvalue, self.decay = float(clipnorm), float(clipvalue), float(decay)
-        self.skip_nonfinite = bool(skip_nonfinite)
-        self._clip: Optional[E.ClipScratch] = None
-        dev = net.device
+        self.opt = AdamUpdate(dev, lr, l2=l2, clipnorm=clipnorm, clipvalue=clipvalue, decay=decay,
+                              skip_nonfinite=skip_nonfinite, totals=True)
         # deep supervision: None (the reference's loss on the last step, exactly the launches of before) or
         # mp_steps weights λ_s >= 0, not all zero — every step then trains on Σ_s λ_s·BCE(z_s, y)
-        # (engine.forward_steps / bce_steps / backward_steps)
-        self.step_loss_weights = None if step_loss_weights is None else \
-            E.check_step_weights(step_loss_weights, net.mp_steps)
-        self._bce_steps = None if step_loss_weights is None else E.BceStepsScratch(dev, net.mp_steps)
+        self._plain = LossPath(dev, net.mp_steps)
+        self._path = self._plain if step_loss_weights is None else DeepLossPath(dev, net.mp_steps, step_loss_weights)
+        self._rows: Optional[DeepLossPath] = None
+        self.step_loss_weights = self._path.lam
         self._tot_s = None if step_loss_weights is None else torch.zeros(net.mp_steps, 3, dtype=torch.float64, device=dev)
         self.m = torch.zeros_like(net.flat.data)
         self.v = torch.zeros_like(net.flat.data)
         self.iterations = 0
         self._ws = E.Workspace(dev)
-        self._bce = E.BceScratch(dev)
         self._grads = torch.empty_like(net.flat.data)
         self.history: Dict[str, List[float]] = {}
         # replayed fit steps (spwgnn_amd/replay.py): device step words, per-geometry graphs, epoch sums
@@ -147,29 +143,47 @@ class KerasModel:
         self._tot = torch.zeros(3, dtype=torch.float64, device=dev)
         self._w3: Dict[int, torch.Tensor] = {}
 
+    lr, l2, beta1, beta2, eps = (delegated("opt", k) for k in ("lr", "l2", "beta1", "beta2", "eps"))
+    clipnorm, clipvalue, decay, skip_nonfinite = (delegated("opt", k) for k in
+                                                  ("clipnorm", "clipvalue", "decay", "skip_nonfinite"))
+    step_out3 = property(lambda self: self._path.out3s)   # the last loss's (S, 3) per-step rows (step_loss_weights)
+
+    def _every_step(self) -> DeepLossPath:
+        """A path over every step's rows whatever the model trains on: λ = e_{S−1} gives the plain loss's bits."""
+        if self._path.lam is not None:
+            return self._path
+        if self._rows is None:
+            self._rows = DeepLossPath(self.net.device, self.net.mp_steps, (0.0,) * (self.net.mp_steps - 1) + (1.0,))
+        return self._rows
+
+    def _weights3(self, towers: int) -> torch.Tensor:
+        """The epoch sums' fp64 weights [towers of the batch, 1, 1] (fit's convention), cached."""
+        if towers not in self._w3:
+            self._w3[towers] = torch.tensor([float(towers), 1.0, 1.0], dtype=torch.float64, device=self.net.device)
+        return self._w3[towers]
+
+    def _dense_slices(self, x: Dict[str, np.ndarray], batch_size: int):
+        """(slice, TowerBatch) over the towers of a dense input dict, `batch_size` at a time: predict's
+        batches (the plan fit's validation batch has)."""
+        objects = np.asarray(x["objects"], np.float32)
+        Rs, Rr, prop = np.asarray(x["sender_relations"]), np.asarray(x["receiver_relations"]), x.get("propagation")
+        for b0 in range(0, objects.shape[0], batch_size):
+            sl = slice(b0, min(objects.shape[0], b0 + batch_size))
+            yield sl, TowerBatch.from_dense(objects[sl], Rs[sl], Rr[sl], None if prop is None else np.asarray(prop)[sl],
+                                            device=self.net.device)
+
     # ---------------------------------------------------------------- inference
     def predict(self, x: Dict[str, np.ndarray], batch_size: int = 32768, return_steps: bool = False) -> np.ndarray:
         """(B, N, 1) probabilities; ``return_steps``: (B, N, S), the probabilities read out after each of
         the S propagation steps (the last column is the plain prediction)."""
-        objects = np.asarray(x["objects"], np.float32)
-        B, N = objects.shape[:2]
-        S = self.net.mp_steps
-        out = np.zeros((B, N, S if return_steps else 1), np.float32)
+        B, N = np.shape(x["objects"])[:2]
+        path, R = (self._every_step(), self.net.mp_steps) if return_steps else (self._plain, 1)
+        out = np.zeros((B, N, R), np.float32)
         run = self.net.run_config()
-        for b0 in range(0, B, batch_size):
-            sl = slice(b0, min(B, b0 + batch_size))
-            prop = x.get("propagation")
-            batch = TowerBatch.from_dense(objects[sl], np.asarray(x["sender_relations"])[sl],
-                                          np.asarray(x["receiver_relations"])[sl],
-                                          None if prop is None else np.asarray(prop)[sl], device=self.net.device)
+        for sl, batch in self._dense_slices(x, batch_size):
             with torch.no_grad():
-                if return_steps:
-                    z = E.forward_steps(self.net.flat.detach(), batch, run, self._ws)
-                    out[sl] = E.sigmoid(z.reshape(-1)).reshape(S, -1, N).permute(1, 2, 0).cpu().numpy()
-                    continue
-                z = E.forward(self.net.flat.detach(), batch, run, self._ws)
-                p = E.sigmoid(z)
-            out[sl, :, 0] = p.reshape(-1, N).cpu().numpy()
+                z = path.forward(self.net.flat.detach(), batch, run, self._ws)
+                out[sl] = E.sigmoid(z.reshape(-1)).reshape(R, -1, N).permute(1, 2, 0).cpu().numpy()
         return out
 
     # ---------------------------------------------------------------- training
@@ -178,41 +192,26 @@ class KerasModel:
         (device). `node_weights` (one per node, in the targets' order): the weighted loss of engine.bce
         with the divisor max(#non-zero weights, 1) (one host sync to count them). With step_loss_weights
         out3 = [Σ_s λ_s·loss_s, the last step's correct, n] and `step_out3` holds the (S, 3) per-step rows."""
-        net = self.net
+        net, path = self.net, self._path
         net._step_seed += 1
         run = net.run_config(True, dropout=net.dropout, seed=net._step_seed)
-        if self.step_loss_weights is not None:
-            z = E.forward_steps(net.flat.data, batch, run, self._ws)
-            out3, self.step_out3, dz = E.bce_steps(z, target, self.step_loss_weights, self._bce_steps,
-                                                   node_weights=self._dev_weights(node_weights))
-            E.backward_steps(net.flat.data, batch, run, self._ws, dz, grads=self._grads)
-        else:
-            z = E.forward(net.flat.data, batch, run, self._ws)
-            out3, dz = E.bce(z, target, self._bce, node_weights=self._dev_weights(node_weights))
-            E.backward(net.flat.data, batch, run, self._ws, dz, grads=self._grads)
+        z = path.forward(net.flat.data, batch, run, self._ws)
+        out3, dz = path.loss(z, target, node_weights=self._dev_weights(node_weights))
+        path.backward(net.flat.data, batch, run, self._ws, dz, self._grads)
         self.iterations += 1
-        if not self._clip_on():
-            E.adam(net.flat.data, self._grads, self.m, self.v, self.iterations, self.lr, self.beta1, self.beta2,
-                   self.eps, self.l2)
-            return out3
-        lr = E.adam_lr_decayed(self.lr, self.decay, self.iterations - 1) if self.decay else self.lr
-        E.adam_clipped(net.flat.data, self._grads, self.m, self.v, self.iterations, self._clip_scratch(), lr,
-                       self.beta1, self.beta2, self.eps, self.l2, 1.0, self.clipnorm, self.clipvalue,
-                       self.skip_nonfinite)
+        self.opt.update(net.flat.data, self._grads, self.m, self.v, self.iterations)
         return out3
 
     def _clip_on(self) -> bool:
-        return bool(self.clipnorm or self.clipvalue or self.decay or self.skip_nonfinite)
+        return self.opt.clip_on()
 
-    def _clip_scratch(self) -> E.ClipScratch:
-        if self._clip is None:
-            self._clip = E.ClipScratch(self.net.device, totals=True)
-        return self._clip
+    def _clip_scratch(self) -> E.ClipScratch:   # with totals: the epoch's clip sums
+        return self.opt.clip_scratch()
 
     @property
     def clip_stats(self) -> Optional[torch.Tensor]:
         """The last clipped step's [norm, scale, skipped, clipped] (device tensor), None before one."""
-        return None if self._clip is None else self._clip.out4
+        return None if self.opt.scratch is None else self.opt.scratch.out4
 
     def _dev_weights(self, node_weights) -> Optional[torch.Tensor]:
         if node_weights is None:
@@ -223,60 +222,17 @@ class KerasModel:
         """One fit step's launches for a replayed geometry: the same sequence as train_on_batch
         (key + 1, forward, BCE, backward, Adam at the incremented step) with the per-step scalars
         read from the device, and the epoch sums accumulated on the device."""
-        net, ctr = self.net, self._ctr
-        clip = self._clip_scratch() if self._clip_on() else None
-        lam = self.step_loss_weights
-        sbuf = {}   # deep supervision: this geometry's (S, n) rows and loss scratch, made by its first (eager) run
-
-        def body(batch, target, ws, bce, z, dz, pre=None, weights=None, norm=None):
-            w3 = self._w3[batch.n_towers]        # created before the first (eager) run of a geometry
-            # the key/step advance (and the replayed batch upload, `pre`) ride in the forward's first launch
-            pro = None
-            if E.FOLD_PROLOGUE:
-                pro = pre if pre is not None else E.Prologue()
-                pro.key, pro.step, pro.mode = ctr.key, ctr.step, _lib.STEP_KEY_COUNTER
-            else:
-                E.step_advance(ctr.key, ctr.step, _lib.STEP_KEY_COUNTER)
-            run = net.run_config(True, dropout=net.dropout, seed_dev=ctr.key, prologue=pro)
-            if lam is not None:
-                # every step's logits, the step-weighted loss with the epoch sums (combined and per step) in
-                # its own launch, and one backward over the step loop with each step's cotangent row
-                if not sbuf:
-                    sbuf["z"] = torch.empty(net.mp_steps, batch.n_nodes, dtype=torch.float32, device=z.device)
-                    sbuf["dz"] = torch.empty_like(sbuf["z"])
-                    sbuf["bce"] = E.BceStepsScratch(z.device, net.mp_steps)
-                E.forward_steps(net.flat.data, batch, run, ws, step_logits=sbuf["z"])
-                E.bce_steps(sbuf["z"], target, lam, sbuf["bce"], dlogits=sbuf["dz"], total3=self._tot, weights3=w3,
-                            total3s=self._tot_s, node_weights=weights, norm=norm)
-                E.backward_steps(net.flat.data, batch, run, ws, sbuf["dz"], grads=self._grads)
-            else:
-                E.forward(net.flat.data, batch, run, ws, logits=z)
-                # loss + epoch sums and the backward in one call: on the fused small-batch loop the loss
-                # needs no launch of its own (spwgnn_bce_backward); weights / norm: a weighted fit's per-node
-                # loss weights and their divisor, views of the step's static buffer
-                E.bce_backward(net.flat.data, batch, run, ws, z, target, bce, dlogits=dz, total3=self._tot,
-                               weights3=w3, grads=self._grads, node_weights=weights, norm=norm)
-            if clip is None:
-                E.adam_dev(net.flat.data, self._grads, self.m, self.v, ctr.step, ctr.lr_table, self.beta1, self.beta2,
-                           self.eps, self.l2)
-            else:   # the decay is in the lr table; the epoch's clip sums ride in the update launch
-                E.adam_clipped_dev(net.flat.data, self._grads, self.m, self.v, ctr.step, ctr.lr_table, clip,
-                                   self.beta1, self.beta2, self.eps, self.l2, 1.0, self.clipnorm, self.clipvalue,
-                                   self.skip_nonfinite, accumulate=True)
-        return body
+        net = self.net
+        return step_body(net.flat.data, self._grads, self.m, self.v, self._path, self.opt, self._ctr,
+                         lambda **kw: net.run_config(True, dropout=net.dropout, **kw), _lib.STEP_KEY_COUNTER,
+                         sums=(self._tot, self._tot_s, self._w3))
 
     def evaluate_batch(self, batch: TowerBatch, target: torch.Tensor, node_weights=None, norm=None):
-        """out3 = [loss, correct, n] of an inference forward; `node_weights` / `norm` as engine.bce takes
-        them (norm None: the non-zero weights are counted, one host sync)."""
-        run = self.net.run_config()
-        if self.step_loss_weights is not None:   # [Σ_s λ_s·loss_s, the last step's correct, n]
-            z = E.forward_steps(self.net.flat.data, batch, run, self._ws)
-            out3, self.step_out3, _ = E.bce_steps(z, target, self.step_loss_weights, self._bce_steps,
-                                                  node_weights=self._dev_weights(node_weights), norm=norm)
-            return out3
-        z = E.forward(self.net.flat.data, batch, run, self._ws)
-        out3, _ = E.bce(z, target, self._bce, node_weights=self._dev_weights(node_weights), norm=norm)
-        return out3
+        """out3 = [loss, correct, n] of an inference forward ([Σ_s λ_s·loss_s, the last step's correct, n] with
+        step_loss_weights); `node_weights` / `norm` as engine.bce takes them (norm None: the non-zero weights
+        are counted, one host sync)."""
+        z = self._path.forward(self.net.flat.data, batch, self.net.run_config(), self._ws)
+        return self._path.loss(z, target, node_weights=self._dev_weights(node_weights), norm=norm)[0]
 
     def evaluate(self, x: Dict[str, np.ndarray], y, batch_size: int = 32768, sample_weight=None,
                  threshold: float = 0.5, return_dict: bool = False, return_steps: bool = False):
@@ -301,37 +257,23 @@ class KerasModel:
         target = np.asarray(y["target"] if isinstance(y, dict) else y, np.float32).reshape(B, -1)
         tau = E.check_threshold(threshold)
         W = node_weights(target, sample_weight) if sample_weight is not None else None
-        Rs, Rr, prop = np.asarray(x["sender_relations"]), np.asarray(x["receiver_relations"]), x.get("propagation")
         dev, net, S = self.net.device, self.net, self.net.mp_steps
         lam = self.step_loss_weights
-        by_steps = return_steps or lam is not None
-        if by_steps:   # every step's loss rides in the one loss launch; λ = e_{S−1} gives the plain loss's bits
-            lam_eval = lam if lam is not None else (0.0,) * (S - 1) + (1.0,)
-            steps_scratch = self._bce_steps if self._bce_steps is not None else E.BceStepsScratch(dev, S)
-            tot_s = torch.zeros(S, 3, dtype=torch.float64, device=dev)
+        # return_steps: every step's loss rides in the one loss launch, whatever the model trains on
+        path = self._every_step() if return_steps else self._path
+        by_steps = path.lam is not None
+        tot_s = torch.zeros(S, 3, dtype=torch.float64, device=dev) if by_steps else None
         tables = E.EvalTables(dev, rows=S if return_steps else 1)
         tot = torch.zeros(3, dtype=torch.float64, device=dev)
         run = net.run_config()
-        for b0 in range(0, B, batch_size):
-            idx = slice(b0, min(B, b0 + batch_size))
-            batch = TowerBatch.from_dense(objects[idx], Rs[idx], Rr[idx], None if prop is None else np.asarray(prop)[idx],
-                                          device=dev)   # predict's batches: the plan fit's validation batch has
+        for idx, batch in self._dense_slices(x, batch_size):
             tgt = torch.as_tensor(target[idx], device=dev).reshape(-1).contiguous()
             w = self._dev_weights(W[idx]) if W is not None else None
             norm = max(int(np.count_nonzero(W[idx])), 1) if W is not None else None   # counted on the host
-            if batch.n_towers not in self._w3:
-                self._w3[batch.n_towers] = torch.tensor([float(batch.n_towers), 1.0, 1.0], dtype=torch.float64, device=dev)
-            w3 = self._w3[batch.n_towers]
-            if by_steps:
-                z = E.forward_steps(net.flat.data, batch, run, self._ws)
-                E.bce_steps(z, tgt, lam_eval, steps_scratch, total3=tot, weights3=w3, total3s=tot_s, node_weights=w,
-                            norm=norm)
-                if not return_steps:
-                    z = z[S - 1]
-            else:
-                z = E.forward(net.flat.data, batch, run, self._ws)
-                E.bce(z, tgt, self._bce, total3=tot, weights3=w3, node_weights=w, norm=norm)
-            E.eval_metrics(z, tgt, tables, batch=batch, node_weights=w, threshold=tau)
+            z = path.forward(net.flat.data, batch, run, self._ws)
+            path.loss(z, tgt, total3=tot, weights3=self._weights3(batch.n_towers), total3s=tot_s, node_weights=w,
+                      norm=norm)
+            E.eval_metrics(z if return_steps else path.last(z), tgt, tables, batch=batch, node_weights=w, threshold=tau)
         # the one device read: the integer tables and the bits of the fp64 loss sums in one copy
         sums = [tot.view(torch.int64)] + ([tot_s.reshape(-1).view(torch.int64)] if by_steps else [])
         host = torch.cat([tables.flat] + sums).cpu()
@@ -451,8 +393,7 @@ class KerasModel:
                 clip.total4.zero_()
             for b0 in range(0, n_tr, batch_size):
                 idx = order[b0:b0 + batch_size]
-                if len(idx) not in self._w3:
-                    self._w3[len(idx)] = torch.tensor([float(len(idx)), 1.0, 1.0], dtype=torch.float64, device=dev)
+                self._weights3(len(idx))
                 self._replays(ds.subset_plan(idx, edge_cap=True), target[idx], W[idx] if weighted else None)
                 self.net._step_seed += 1
                 self.iterations += 1

@@ -35,31 +35,18 @@ class _PropagationFn(torch.autograd.Function):
         ctx.want_state = want_state
         ctx.want_steps = want_steps
         ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None, not as zeros
-        if want_steps:
-            return E.forward_steps(flat, batch, run, ws, return_state=want_state)
-        if want_state:
-            return E.forward(flat, batch, run, ws, return_state=True)
-        return E.forward(flat, batch, run, ws)
+        return (E.forward_steps if want_steps else E.forward)(flat, batch, run, ws, return_state=want_state)
 
     @staticmethod
     def backward(ctx, dlogits, dstate=None):
         (flat,) = ctx.saved_tensors
         if dstate is not None:
             dstate = dstate.to(torch.float32).contiguous()
-        if ctx.want_steps:
-            if dlogits is None:
-                dlogits = torch.zeros(ctx.run.mp_steps, ctx.batch.n_nodes, dtype=torch.float32, device=flat.device)
-            grads, dprop = E.backward_steps(flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop,
-                                            dstate=dstate)
-            dobj = E.backward_inputs(flat, ctx.batch, ctx.run, ctx.ws) if ctx.want_obj else None
-            return grads, dprop, dobj, None, None, None, None, None
         if dlogits is None:   # a loss on the state alone: the library still takes a dlogits array
-            dlogits = torch.zeros(ctx.batch.n_nodes, dtype=torch.float32, device=flat.device)
-        if dstate is None:    # no loss on the state: the plain backward
-            grads, dprop = E.backward(flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop)
-        else:
-            grads, dprop = E.backward(flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop,
-                                      dstate=dstate)
+            shape = (ctx.run.mp_steps, ctx.batch.n_nodes) if ctx.want_steps else (ctx.batch.n_nodes,)
+            dlogits = torch.zeros(shape, dtype=torch.float32, device=flat.device)
+        grads, dprop = (E.backward_steps if ctx.want_steps else E.backward)(
+            flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop, dstate=dstate)
         dobj = E.backward_inputs(flat, ctx.batch, ctx.run, ctx.ws) if ctx.want_obj else None
         return grads, dprop, dobj, None, None, None, None, None
 
@@ -149,22 +136,16 @@ class GraphNetwork(nn.Module):
             odummy = batch.to_plan_order(objects.reshape(batch.n_nodes, 3).to(self.device, torch.float32))
         else:
             odummy = dummy.new_zeros(0)
-        if return_steps:
-            if not run.training:
-                with torch.no_grad():
-                    out = E.forward_steps(self.flat.detach(), batch, run, ws, return_state=return_state)
-            else:
-                out = _PropagationFn.apply(self.flat, dummy, odummy, batch, run, ws, return_state, True)
-            steps = out[0] if return_state else out
-            if batch.node_perm is not None:   # rows of a packed plan back in the input's node order
-                steps = batch.to_input_order(steps.t()).t()
-            return (steps, out[1]) if return_state else steps
         if not run.training:
             with torch.no_grad():
-                return E.forward(self.flat.detach(), batch, run, ws, return_state=return_state)
-        if return_state:
-            return _PropagationFn.apply(self.flat, dummy, odummy, batch, run, ws, True)
-        return _PropagationFn.apply(self.flat, dummy, odummy, batch, run, ws)
+                out = (E.forward_steps if return_steps else E.forward)(self.flat.detach(), batch, run, ws,
+                                                                       return_state=return_state)
+        else:
+            out = _PropagationFn.apply(self.flat, dummy, odummy, batch, run, ws, return_state, return_steps)
+        if return_steps and batch.node_perm is not None:   # rows of a packed plan back in the input's node order
+            steps = batch.to_input_order((out[0] if return_state else out).t()).t()
+            return (steps, out[1]) if return_state else steps
+        return out
 
     def rollout(self, batches: Sequence[TowerBatch], prop: Optional[torch.Tensor] = None,
                 objects: Optional[Sequence[Optional[torch.Tensor]]] = None) -> Tuple[List[torch.Tensor], torch.Tensor]:

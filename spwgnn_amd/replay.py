@@ -295,5 +295,35 @@ class ReplayCache:
         return st
 
 
+def step_body(params, grads, m, v, path, adam, counters: DeviceCounters, make_run: Callable, key_mode: int,
+              seed: int = 0, rank: int = 0, grad_scale: float = 1.0, sums: Optional[tuple] = None) -> Callable:
+    """The launches of one optimizer step for `ReplayStep`, the one body of every front end: the key/step
+    advance in `key_mode` (with `seed`, `rank`), the forward, the loss with the backward, the gradient
+    scale and Adam at the device step word. `path`: the front end's step.LossPath, `adam`: its
+    step.AdamUpdate; `make_run(seed_dev=, prologue=)` builds the training RunConfig. `sums`: the epoch
+    sums (total3, total3s or None, {towers of the batch: weights3}) the loss launch adds to. The buffers
+    are bound here, as a captured graph binds their addresses."""
+    path = path.for_replay()
+    tot, tot_s, w3s = sums if sums is not None else (None, None, None)
+
+    def body(batch, target, ws, bce, z, dz, pre=None, weights=None, norm=None):
+        # the key/step advance (and the replayed batch upload, `pre`) ride in the forward's first launch
+        pro = None
+        if E.FOLD_PROLOGUE:
+            pro = pre if pre is not None else E.Prologue()
+            pro.key, pro.step, pro.mode, pro.seed, pro.rank = counters.key, counters.step, key_mode, seed, rank
+        else:
+            E.step_advance(counters.key, counters.step, key_mode, seed, rank)
+        run = make_run(seed_dev=counters.key, prologue=pro)
+        logits = path.forward(params, batch, run, ws, z)
+        # weights / norm: a weighted step's per-node loss weights and their divisor, views of its static buffer
+        path.loss_backward(params, batch, run, ws, logits, target, bce, dz, grads, tot,
+                           w3s[batch.n_towers] if w3s is not None else None, tot_s, weights, norm)
+        if grad_scale != 1.0:
+            grads.mul_(grad_scale)
+        adam.update_dev(params, grads, m, v, counters, adam.totals)   # the epoch's clip sums ride in the update
+    return body
+
+
 def step_key_mode(kind: str) -> int:
     return {"counter": _lib.STEP_KEY_COUNTER, "splitmix": _lib.STEP_KEY_SPLITMIX}[kind]

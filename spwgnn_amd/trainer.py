@@ -32,6 +32,8 @@ import torch.distributed as dist
 
 from . import _lib, engine as E, params as P
 from .batch import TowerBatch
+from .replay import DeviceCounters, step_body
+from .step import AdamUpdate, delegated, loss_path
 
 
 _M64 = (1 << 64) - 1
@@ -56,45 +58,38 @@ def dropout_key(seed: int, iteration: int, rank: int, micro: int) -> int:
 
 
 class HipEngine:
+    """The product engine of the protocol (spwgnn_amd/step.py): libspwgnn_hip on one device. With
+    step_loss_weights set (deep supervision) "logits" and "dlogits" are the (mp_steps, n) rows of every step
+    and the loss is Σ_s λ_s·BCE(z_s); the Trainer's control flow — scaling, all-reduce, the early-gradient
+    event — only hands them through, so which loss runs is `path`'s business alone."""
+
     def __init__(self, device):
         self.device = torch.device(device)
         self.ws = E.Workspace(self.device)
-        self.bce_scratch = E.BceScratch(self.device)
         self.grads: Optional[torch.Tensor] = None
-        # deep supervision (Trainer(step_loss_weights=)): with weights set, "logits" and "dlogits" below are
-        # the (mp_steps, n) rows of every step and the loss is Σ_s λ_s·BCE(z_s) (engine.bce_steps); the
-        # Trainer's control flow — scaling, all-reduce, the early-gradient event — only hands them through
-        self.step_loss_weights = None
-        self.steps_scratch: Optional[E.BceStepsScratch] = None
-        self.out3s = None     # the last loss's per-step [loss, correct, n] (device, (mp_steps, 3))
+        self._early_ev = self._clip = None
+        self.set_step_loss_weights(None, E.REF_MP_STEPS)
 
     def set_step_loss_weights(self, lam, mp_steps: int):
-        self.step_loss_weights = None if lam is None else E.check_step_weights(lam, mp_steps)
-        self.steps_scratch = None if lam is None else E.BceStepsScratch(self.device, mp_steps)
+        self.path = loss_path(self.device, mp_steps, lam)
+
+    step_loss_weights = property(lambda self: self.path.lam)
+    bce_scratch = property(lambda self: self.path.scratch)
+    out3s = property(lambda self: self.path.out3s)   # the last loss's per-step [loss, correct, n] (device, (mp_steps, 3))
 
     def forward(self, params, batch: TowerBatch, run: E.RunConfig):
-        if self.step_loss_weights is not None:
-            return E.forward_steps(params, batch, run, self.ws)
-        return E.forward(params, batch, run, self.ws)
+        return self.path.forward(params, batch, run, self.ws)
 
     def loss(self, logits, target):
-        return self.loss_weighted(logits, target, None, None)
+        return self.path.loss(logits, target)
 
     def loss_weighted(self, logits, target, weights, norm):
-        if self.step_loss_weights is not None:
-            out3, self.out3s, dz = E.bce_steps(logits, target, self.step_loss_weights, self.steps_scratch,
-                                               node_weights=weights, norm=norm)
-            return out3, dz
-        return E.bce(logits, target, self.bce_scratch, node_weights=weights, norm=norm)
+        return self.path.loss(logits, target, node_weights=weights, norm=norm)
 
     def backward(self, params, batch, run, dlogits):
         if self.grads is None or self.grads.numel() != params.numel():
             self.grads = torch.empty_like(params)
-        if self.step_loss_weights is not None:
-            g, _ = E.backward_steps(params, batch, run, self.ws, dlogits, grads=self.grads)
-            return g
-        g, _ = E.backward(params, batch, run, self.ws, dlogits, grads=self.grads)
-        return g
+        return self.path.backward(params, batch, run, self.ws, dlogits, self.grads)
 
     def eval_metrics(self, logits, target, tables, batch, weights=None, threshold=0.5):
         """The evaluation counts of `logits` (the rows `forward` returned) added to `tables` on the device
@@ -104,17 +99,16 @@ class HipEngine:
     def early_event(self):
         """The event the library records once the early gradient range is final
         (spwgnn_run.grads_early_event); created (recorded once) on first use."""
-        ev = getattr(self, "_early_ev", None)
-        if ev is None:
-            ev = self._early_ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))   # creates the underlying hipEvent_t
-        return ev
+        if self._early_ev is None:
+            self._early_ev = torch.cuda.Event()
+            self._early_ev.record(torch.cuda.current_stream(self.device))   # creates the underlying hipEvent_t
+        return self._early_ev
 
     def adam(self, params, grads, m, v, step, lr, b1, b2, eps, l2, gscale):
         E.adam(params, grads, m, v, step, lr, b1, b2, eps, l2, gscale)
 
     def clip_scratch(self) -> "E.ClipScratch":
-        if getattr(self, "_clip", None) is None:
+        if self._clip is None:
             self._clip = E.ClipScratch(self.device)
         return self._clip
 
@@ -124,6 +118,23 @@ class HipEngine:
         clipped], a device tensor the next step overwrites."""
         return E.adam_clipped(params, grads, m, v, step, self.clip_scratch(), lr, b1, b2, eps, l2, gscale,
                               clipnorm, clipvalue, skip_nonfinite)
+
+
+def _micro_batches(batches, targets, weights):
+    """`step`'s and `evaluate`'s arguments as lists of equal length, one entry per micro-batch."""
+    batches = batches if isinstance(batches, (list, tuple)) else [batches]
+    targets = targets if isinstance(targets, (list, tuple)) else [targets]
+    if len(batches) != len(targets) or not batches:
+        raise ValueError("one target per micro-batch")
+    if weights is not None:
+        weights = weights if isinstance(weights, (list, tuple)) else [weights]
+        if len(weights) != len(batches):
+            raise ValueError("one weight tensor per micro-batch")
+    return batches, targets, weights
+
+
+def _nonzero(weights) -> int:
+    return int(torch.count_nonzero(torch.as_tensor(weights)).item())   # one host sync
 
 
 class Trainer:
@@ -140,25 +151,24 @@ class Trainer:
         # Keras 2.x optimizer arguments (0 = off) and the non-finite guard: with any of them set the
         # update is engine.adam_clipped — the global norm of the all-reduced gradient, one launch more —
         # instead of engine.adam; with none, exactly the launches of before
-        E.check_clip_options(clipnorm, clipvalue, decay)
-        self.clipnorm, self.clipvalue, self.decay = float(clipnorm), float(clipvalue), float(decay)
-        self.skip_nonfinite = bool(skip_nonfinite)
+        # (the eager `step` goes through the engine protocol; `opt` itself runs the replayed steps' update)
+        self.opt = AdamUpdate(params.device, lr, beta1, beta2, eps, l2, clipnorm, clipvalue, decay, skip_nonfinite)
         self.params = params
         self.engine = engine if engine is not None else HipEngine(params.device)
-        if self._clip_on() and not hasattr(self.engine, "adam_clipped"):
+        if self.opt.clip_on() and not hasattr(self.engine, "adam_clipped"):
             raise ValueError("clipnorm / clipvalue / decay / skip_nonfinite need an engine with adam_clipped("
                              "params, grads, m, v, step, lr, b1, b2, eps, l2, gscale, clipnorm, clipvalue, "
-                             "skip_nonfinite)")
+                             "skip_nonfinite) (the engine protocol: spwgnn_amd/step.py)")
         self.step_loss_weights = None if step_loss_weights is None else E.check_step_weights(step_loss_weights, mp_steps)
         if self.step_loss_weights is not None:
             if not hasattr(self.engine, "set_step_loss_weights"):
-                raise ValueError("step_loss_weights needs an engine with set_step_loss_weights(weights, mp_steps)")
+                raise ValueError("step_loss_weights needs an engine with set_step_loss_weights(weights, mp_steps) "
+                                 "(the engine protocol: spwgnn_amd/step.py)")
             self.engine.set_step_loss_weights(self.step_loss_weights, mp_steps)
         self.clip_stats = None    # the last clipped step's [norm, scale, skipped, clipped] (device tensor)
         self.m = torch.zeros_like(params)
         self.v = torch.zeros_like(params)
         self.mp_steps, self.dropout, self.seed, self.math = mp_steps, dropout, seed, math
-        self.lr, self.b1, self.b2, self.eps, self.l2 = lr, beta1, beta2, eps, l2
         self.iterations = 0
         self.group = group
         self.distributed = dist.is_available() and dist.is_initialized()
@@ -182,22 +192,23 @@ class Trainer:
         self._early_lo = next(off for name, off, _ in P.layout() if name == "rmp.1.kernel")
         self._ctr = None          # replayed steps' device counters (replay_body)
         self._ctr_at = 0          # the host iteration count the device step word holds
-        self._w3 = {}             # (n_nodes, 1, 1) fp64 weights of a micro-batch's [loss, correct, n]
+        self._w3 = {}             # (count, 1, 1) fp64 weights of a micro-batch's [loss, correct, n]
+        self._acc = None          # the micro-batches' gradient sum (the engine reuses its own buffer)
 
-    def _clip_on(self) -> bool:
-        return bool(self.clipnorm or self.clipvalue or self.decay or self.skip_nonfinite)
+    lr, b1, b2, eps, l2 = (delegated("opt", k) for k in ("lr", "beta1", "beta2", "eps", "l2"))
+    clipnorm, clipvalue, decay, skip_nonfinite = (delegated("opt", k) for k in
+                                                  ("clipnorm", "clipvalue", "decay", "skip_nonfinite"))
 
     def _adam(self, acc):
         """The update of step `iterations` (already advanced) from the reduced gradient `acc`: after the
         all-reduce, so every rank clips by the same norm and takes the same skip decision."""
-        if not self._clip_on():
-            self.engine.adam(self.params, acc, self.m, self.v, self.iterations, self.lr, self.b1, self.b2, self.eps,
-                             self.l2, 1.0)
+        o = self.opt
+        if not o.clip_on():
+            self.engine.adam(self.params, acc, self.m, self.v, self.iterations, o.lr, o.beta1, o.beta2, o.eps, o.l2, 1.0)
             return
-        lr = E.adam_lr_decayed(self.lr, self.decay, self.iterations - 1) if self.decay else self.lr
-        self.clip_stats = self.engine.adam_clipped(self.params, acc, self.m, self.v, self.iterations, lr, self.b1,
-                                                   self.b2, self.eps, self.l2, 1.0, self.clipnorm, self.clipvalue,
-                                                   self.skip_nonfinite)
+        lr = E.adam_lr_decayed(o.lr, o.decay, self.iterations - 1) if o.decay else o.lr
+        self.clip_stats = self.engine.adam_clipped(self.params, acc, self.m, self.v, self.iterations, lr, o.beta1,
+                                                   o.beta2, o.eps, o.l2, 1.0, o.clipnorm, o.clipvalue, o.skip_nonfinite)
 
     def _early(self, run):
         """Overlapped steps: the engine's early-gradient event, handed to the backward through `run`."""
@@ -216,7 +227,6 @@ class Trainer:
     def _sync_counters(self):
         """Device step word and lr table ← the host's iteration count and (lr, β1, β2, decay), when they
         differ (a step() or an lr / decay change since the last replay)."""
-        from .replay import DeviceCounters
         if self._ctr is None:
             self._ctr = DeviceCounters(self.params.device, 0, self.iterations, self.lr, self.b1, self.b2,
                                        decay=self.decay)
@@ -243,51 +253,17 @@ class Trainer:
         if not isinstance(self.engine, HipEngine):
             raise ValueError("replayed steps need the HIP engine")
         self._sync_counters()
-        ctr = self._ctr
         if weighted and n_global not in (None, n_nodes):
             raise ValueError("weighted replayed steps cover the whole batch (no n_global)")
-        w = n_nodes / (n_global or n_nodes)
-        grads = torch.empty_like(self.params)
         E.check_clip_options(self.clipnorm, self.clipvalue, self.decay)
-        clip = self.engine.clip_scratch() if self._clip_on() else None
-        if clip is not None:
-            self.clip_stats = clip.out4
-        lam = self.step_loss_weights
-        sbuf = {}   # deep supervision: this geometry's (mp_steps, n) rows and loss scratch, made by its first (eager) run
+        if self.opt.clip_on():
+            self.clip_stats = self.opt.clip_scratch().out4
 
-        def body(batch, target, ws, bce, z, dz, pre=None, weights=None, norm=None):
-            # the key/step advance (and the replayed batch upload, `pre`) ride in the forward's first launch
-            pro = None
-            if E.FOLD_PROLOGUE:
-                pro = pre if pre is not None else E.Prologue()
-                pro.key, pro.step, pro.mode, pro.seed, pro.rank = ctr.key, ctr.step, _lib.STEP_KEY_SPLITMIX, self.seed, self.rank
-            else:
-                E.step_advance(ctr.key, ctr.step, _lib.STEP_KEY_SPLITMIX, self.seed, self.rank)
-            run = E.RunConfig(self.mp_steps, training=True, dropout=self.dropout, math=self.math, seed_dev=ctr.key,
-                              prologue=pro)
-            if lam is not None:   # every step's logits, the step-weighted loss (its own launch), one backward
-                if not sbuf:
-                    sbuf["z"] = torch.empty(self.mp_steps, batch.n_nodes, dtype=torch.float32, device=z.device)
-                    sbuf["dz"] = torch.empty_like(sbuf["z"])
-                    sbuf["bce"] = E.BceStepsScratch(z.device, self.mp_steps)
-                E.forward_steps(self.params, batch, run, ws, step_logits=sbuf["z"])
-                E.bce_steps(sbuf["z"], target, lam, sbuf["bce"], dlogits=sbuf["dz"], node_weights=weights, norm=norm)
-                E.backward_steps(self.params, batch, run, ws, sbuf["dz"], grads=grads)
-            else:
-                E.forward(self.params, batch, run, ws, logits=z)
-                # the loss and the backward in one call (spwgnn_bce_backward: no loss launch of its own on
-                # the fused small-batch loop; bit-identical to bce then backward)
-                E.bce_backward(self.params, batch, run, ws, z, target, bce, dlogits=dz, grads=grads,
-                               node_weights=weights, norm=norm)
-            if w != 1.0:
-                grads.mul_(w)
-            if clip is None:
-                E.adam_dev(self.params, grads, self.m, self.v, ctr.step, ctr.lr_table, self.b1, self.b2, self.eps,
-                           self.l2)
-            else:   # the decay is in the lr table (_sync_counters)
-                E.adam_clipped_dev(self.params, grads, self.m, self.v, ctr.step, ctr.lr_table, clip, self.b1, self.b2,
-                                   self.eps, self.l2, 1.0, self.clipnorm, self.clipvalue, self.skip_nonfinite)
-        return body
+        def make_run(**kw):
+            return E.RunConfig(self.mp_steps, training=True, dropout=self.dropout, math=self.math, **kw)
+        return step_body(self.params, torch.empty_like(self.params), self.m, self.v, self.engine.path, self.opt,
+                         self._ctr, make_run, _lib.STEP_KEY_SPLITMIX, self.seed, self.rank,
+                         grad_scale=n_nodes / (n_global or n_nodes))
 
     def bucket_bounds(self, n: int):
         """[(start, end)) of the gradient buckets over a flat buffer of n floats (64-float aligned)."""
@@ -317,15 +293,14 @@ class Trainer:
         return self.distributed and self.overlap and hasattr(self.engine, "early_event")
 
     def _combine(self, acc, g, w, sl, first):
-        """acc[sl] ← w·g[sl] (first micro-batch) or acc[sl] + w·g[sl]; acc may be g itself."""
-        if first:
-            if acc is g:
-                if w != 1.0:
-                    acc[sl].mul_(w)
-            else:
-                torch.mul(g[sl], w, out=acc[sl])
-        else:
-            acc[sl].add_(g[sl], alpha=w)
+        """acc[sl] ← w·g[sl] (first micro-batch) or acc[sl] + w·g[sl]; acc may be g itself; sl None: all of it."""
+        a, b = (acc, g) if sl is None else (acc[sl], g[sl])
+        if not first:
+            a.add_(b, alpha=w)
+        elif acc is not g:
+            torch.mul(b, w, out=a)
+        elif w != 1.0:
+            a.mul_(w)
 
     def reduce_split(self, acc, g, w, first, ev):
         """The last backward's gradient `g` folded into `acc` (weight w) and the sum over ranks, in two
@@ -409,16 +384,10 @@ class Trainer:
         ``loss`` is Σ_s λ_s·loss_s and ``steps`` lists every step's summary. The engine needs
         `eval_metrics(logits, target, tables, batch, weights, threshold)`."""
         from . import metrics as M
-        batches = batches if isinstance(batches, (list, tuple)) else [batches]
-        targets = targets if isinstance(targets, (list, tuple)) else [targets]
-        if len(batches) != len(targets) or not batches:
-            raise ValueError("one target per micro-batch")
-        if weights is not None:
-            weights = weights if isinstance(weights, (list, tuple)) else [weights]
-            if len(weights) != len(batches):
-                raise ValueError("one weight tensor per micro-batch")
+        batches, targets, weights = _micro_batches(batches, targets, weights)
         if not hasattr(self.engine, "eval_metrics"):
-            raise ValueError("evaluate needs an engine with eval_metrics(logits, target, tables, batch, weights, threshold)")
+            raise ValueError("evaluate needs an engine with eval_metrics(logits, target, tables, batch, weights, threshold) "
+                             "(the engine protocol: spwgnn_amd/step.py)")
         tau = E.check_threshold(threshold)
         rows = self.mp_steps if self.step_loss_weights is not None else 1
         run = E.RunConfig(self.mp_steps, training=False, dropout=0.0, math=self.math)
@@ -431,7 +400,7 @@ class Trainer:
                 out3, _ = self.engine.loss(z, tg)
             else:
                 wt = weights[i]
-                out3, _ = self.engine.loss_weighted(z, tg, wt, max(int(torch.count_nonzero(torch.as_tensor(wt)).item()), 1))
+                out3, _ = self.engine.loss_weighted(z, tg, wt, max(_nonzero(wt), 1))
             n_i = out3[2].to(sums)           # the nodes that count: all of them, or those with w ≠ 0
             sums += torch.stack([out3[0].to(sums) * n_i, n_i])   # before the engine reuses its out3 buffer
             self.engine.eval_metrics(z, tg, tables, b, wt, tau)
@@ -456,120 +425,65 @@ class Trainer:
         weights mask their nodes. Counting each micro-batch's non-zero weights is one host sync. The
         result is then [loss over this rank's counted nodes, correct among them, their number]. The
         engine needs `loss_weighted(logits, target, weights, norm)`."""
-        batches = batch if isinstance(batch, (list, tuple)) else [batch]
-        targets = target if isinstance(target, (list, tuple)) else [target]
-        if len(batches) != len(targets) or not batches:
-            raise ValueError("one target per micro-batch")
-        if weights is not None:
-            return self._step_weighted(batches, targets, weights if isinstance(weights, (list, tuple)) else [weights],
-                                       norm_global)
-        if norm_global is not None:
-            raise ValueError("norm_global goes with weights")
-        n_local = sum(b.n_nodes for b in batches)
-        if n_global is None:
-            n_global = self._count_global(n_local)
-        run = self.run_config()
-        acc = None
-        tot3 = None
-        if len(batches) == 1:   # one batch: its [loss, correct, n] as the engine computed them (one copy)
-            b, tg = batches[0], targets[0]
-            z = self.engine.forward(self.params, b, run)
-            out3, dz = self.engine.loss(z, tg)
-            res = out3.clone()          # the engine reuses its out3 buffer
-            ev = self._early(run)
-            acc = self.engine.backward(self.params, b, run, dz)
-            w = b.n_nodes / n_global
-            if ev is not None:
-                self.reduce_split(acc, acc, w, True, ev)
-            else:
-                if w != 1.0:
-                    acc.mul_(w)
-                if self.distributed:   # any process group (one rank: the identity, through the collective)
-                    self.allreduce(acc)
-            self.iterations += 1
-            self._adam(acc)
-            return res.float() if res.dtype != torch.float32 else res
-        for i, (b, tg) in enumerate(zip(batches, targets)):
-            if i:
-                run = self.run_config(micro=i)
-            z = self.engine.forward(self.params, b, run)
-            out3, dz = self.engine.loss(z, tg)
-            # [loss, correct, n] of this micro-batch, folded in before the engine reuses its buffer:
-            # Σ loss_i·n_i, Σ correct_i, Σ n_i (the engine's out3 is one persistent tensor)
-            key = (b.n_nodes, out3.device)
-            wt = self._w3.pop(key, None)
-            if wt is None:
-                wt = out3.new_tensor([float(b.n_nodes), 1.0, 1.0], dtype=torch.float64)
-            self._w3[key] = wt            # most recent last; ragged micro-batches keep at most 16
-            while len(self._w3) > 16:
-                self._w3.pop(next(iter(self._w3)))
-            w3 = out3.double() * wt
-            tot3 = w3 if tot3 is None else tot3 + w3
-            last = i == len(batches) - 1
-            ev = self._early(run) if last else None
-            g = self.engine.backward(self.params, b, run, dz)
-            w = b.n_nodes / n_global
-            if ev is not None:   # the last micro-batch: accumulate and reduce in two pieces
-                if acc is None:
-                    if getattr(self, "_acc", None) is None or self._acc.shape != g.shape or self._acc.device != g.device:
-                        self._acc = torch.empty_like(g)
-                    acc = self._acc
-                    self.reduce_split(acc, g, w, True, ev)
-                else:
-                    self.reduce_split(acc, g, w, False, ev)
-                continue
-            if acc is None:
-                # the engine writes every backward into one buffer (HipEngine.grads), so the sum lives in
-                # a buffer of its own: the Trainer's persistent accumulator, overwritten here
-                if getattr(self, "_acc", None) is None or self._acc.shape != g.shape or self._acc.device != g.device:
-                    self._acc = torch.empty_like(g)
-                acc = torch.mul(g, w, out=self._acc)
-            else:
-                acc.add_(g, alpha=w)
-        if self.distributed and not self._split():
-            self.allreduce(acc)
-        self.iterations += 1
-        self._adam(acc)
-        # node-weighted mean loss of this rank's shard, total correct, total nodes (device, fp32)
-        return torch.stack([tot3[0] / tot3[2], tot3[1], tot3[2]]).float()
-
-    def _step_weighted(self, batches, targets, weights, norm_global):
-        """`step` with per-node loss weights: micro-batch i's loss divides by its own non-zero count
-        nnz_i (at least 1) and its gradient is scaled by nnz_i / norm_global."""
-        if len(weights) != len(batches):
-            raise ValueError("one weight tensor per micro-batch")
-        nnz = [int(torch.count_nonzero(torch.as_tensor(w)).item()) for w in weights]
-        if norm_global is None:
-            norm_global = self._count_global(sum(nnz))
-        norm_global = max(int(norm_global), 1)
-        acc = None
-        tot3 = None
-        for i, (b, tg, wt, k) in enumerate(zip(batches, targets, weights, nnz)):
+        batches, targets, weights = _micro_batches(batch, target, weights)
+        # micro-batch i counts k_i nodes — all of them, or those with w ≠ 0 — of `total` in the global batch:
+        # its loss is the mean over its k_i, its gradient enters the sum scaled by k_i / total
+        if weights is None:
+            if norm_global is not None:
+                raise ValueError("norm_global goes with weights")
+            counts = [b.n_nodes for b in batches]
+            total = n_global if n_global is not None else self._count_global(sum(counts))
+        else:
+            counts = [_nonzero(w) for w in weights]
+            total = max(int(norm_global if norm_global is not None else self._count_global(sum(counts))), 1)
+        single = len(batches) == 1
+        acc = tot3 = None
+        for i, (b, tg, k) in enumerate(zip(batches, targets, counts)):
             run = self.run_config(micro=i)
             z = self.engine.forward(self.params, b, run)
-            out3, dz = self.engine.loss_weighted(z, tg, wt, max(k, 1))
-            w3 = out3.double() * out3.new_tensor([float(k), 1.0, 1.0], dtype=torch.float64)
-            tot3 = w3 if tot3 is None else tot3 + w3   # before the engine reuses its out3 buffer
-            last = i == len(batches) - 1
-            ev = self._early(run) if last else None
+            if weights is None:
+                out3, dz = self.engine.loss(z, tg)
+            else:
+                out3, dz = self.engine.loss_weighted(z, tg, weights[i], max(k, 1))
+            # the engine's out3 is one persistent tensor: kept before the next call reuses it — one batch's as
+            # the engine computed it (one copy), micro-batches' as Σ loss_i·k_i, Σ correct_i, Σ n_i in fp64
+            if single and weights is None:
+                res = out3.clone()
+            else:
+                w3 = out3.double() * self._weights3(k, out3)
+                tot3 = w3 if tot3 is None else tot3 + w3
+            ev = self._early(run) if i == len(batches) - 1 else None
             g = self.engine.backward(self.params, b, run, dz)
-            w = k / norm_global
             if acc is None:
-                if len(batches) == 1:
-                    acc = g
-                else:   # the engine writes every backward into one buffer: the sum lives in the Trainer's
-                    if getattr(self, "_acc", None) is None or self._acc.shape != g.shape or self._acc.device != g.device:
-                        self._acc = torch.empty_like(g)
-                    acc = self._acc
-                first = True
+                # one batch: the engine's own buffer (HipEngine.grads), scaled in place; micro-batches: the
+                # engine writes every backward into that buffer, so the sum lives in the Trainer's accumulator
+                acc = g if single else self._accumulator(g)
+            if ev is not None:   # the last micro-batch: accumulate and reduce in two pieces
+                self.reduce_split(acc, g, k / total, i == 0, ev)
             else:
-                first = False
-            if ev is not None:
-                self.reduce_split(acc, g, w, first, ev)
-            else:
-                self._combine(acc, g, w, slice(0, g.numel()), first)
-        if self.distributed and not self._split():
+                self._combine(acc, g, k / total, None, i == 0)
+        if self.distributed and not self._split():   # any process group (one rank: the identity, through the collective)
             self.allreduce(acc)
         self.iterations += 1
         self._adam(acc)
-        return torch.stack([tot3[0] / tot3[2].clamp(min=1.0), tot3[1], tot3[2]]).float()
+        if tot3 is None:
+            return res.float() if res.dtype != torch.float32 else res
+        # mean loss over this rank's counted nodes, total correct, total counted (device, fp32)
+        n = tot3[2] if weights is None else tot3[2].clamp(min=1.0)
+        return torch.stack([tot3[0] / n, tot3[1], tot3[2]]).float()
+
+    def _weights3(self, k: int, out3: torch.Tensor) -> torch.Tensor:
+        """The cached fp64 [k, 1, 1] on out3's device (most recent last; ragged micro-batches keep 16)."""
+        key = (k, out3.device)
+        wt = self._w3.pop(key, None)
+        if wt is None:
+            wt = out3.new_tensor([float(k), 1.0, 1.0], dtype=torch.float64)
+        self._w3[key] = wt
+        while len(self._w3) > 16:
+            self._w3.pop(next(iter(self._w3)))
+        return wt
+
+    def _accumulator(self, g: torch.Tensor) -> torch.Tensor:
+        if self._acc is None or self._acc.shape != g.shape or self._acc.device != g.device:
+            self._acc = torch.empty_like(g)
+        return self._acc

@@ -130,7 +130,7 @@ def test_front_ends_validate_step_loss_weights(bad):
 def test_none_is_the_model_of_before():
     """step_loss_weights=None adds nothing: the update choice, the replay options and the buffers."""
     plain = PropagationNetwork(device="cpu").getModel(4)
-    assert plain.step_loss_weights is None and plain._bce_steps is None and plain._tot_s is None
+    assert plain.step_loss_weights is None and plain._path.lam is None and plain._tot_s is None
     assert plain._clip_on() is False and plain._replay_graph is None and plain.history == {}
     deep = PropagationNetwork(device="cpu", step_loss_weights=[0.1, 0.1, 0.1, 0.2, 0.5]).getModel(4)
     assert deep.step_loss_weights == (0.1, 0.1, 0.1, 0.2, 0.5) and deep._clip_on() is False
