@@ -659,6 +659,57 @@ typedef struct spwgnn_eval {
 int32_t spwgnn_eval_metrics(const float* logits /* [R][n] */, const float* targets /* [n] */, int64_t n,
                             const spwgnn_eval* ev, spwgnn_stream_t stream);
 
+/* Tower-level loss (added within ABI 8: new symbols only). A binary cross-entropy on
+ * "the whole tower stands", with the noisy-AND likelihood spwgnn_eval_metrics' tower tables imply: the
+ * probability that every counted block of tower u stands is P_u = Π σ(z_i). A data set that records only
+ * whether a tower stood or fell (the label of JengaBuilder.py:333-346 taken per tower) trains on it.
+ *
+ * Tower u = nodes [tower_offsets[u], tower_offsets[u+1]) as in spwgnn_eval_metrics (every range clamped
+ * to [0, n) before it is walked; the offsets are the caller's contract: nondecreasing, from 0 to n —
+ * dlogits of a node that lies in no tower is not written). Node i is counted when lw == NULL or
+ * lw->w[i] != 0 (a select: NaN under a zero weight stays out); a tower with no counted node is skipped.
+ *   q_i = max(−z_i, 0) + log1pf(expf(−|z_i|))         (−log σ(z_i))
+ *   s_u = −Σ q_i over the counted nodes, in fp32, in node order           (log P_u)
+ *   T_u = tower_targets[u] == 1.f, or without tower_targets: every counted targets[i] == 1.f
+ *   lo = logf(1e-7f), hi = log1pf(−1e-7f), s~ = clamp(s_u, lo, hi), inside = lo < s_u < hi
+ *   l_u = T_u ? −s~ : −log1mexp(s~),  log1mexp(x) = x > −ln 2 ? logf(−expm1f(x)) : log1pf(−expf(x))
+ *   g_u = inside ? (T_u ? −1 : 1 / expm1f(−s_u)) : 0
+ *   L_tower = Σ_u l_u / norm_t;  d_tower_i = ((mu·g_u)·(1 / (1 + expf(z_i)))) / norm_t  (counted nodes)
+ * (Keras's clip of the probability to [1e-7, 1 − 1e-7], Networks.py:102, applied to P_u.) A tower is
+ * correct when (every counted σ(z_i) > 0.5) == T_u: with derived targets, tower6's tTP + tTN at 0.5.
+ * The objective is L = alpha·L_node + mu·L_tower with L_node spwgnn_bce's loss (lw NULL) or
+ * spwgnn_bce_weighted's (lw set: its weights and divisor), and
+ *   dlogits_i = alpha·d_node_i + d_tower_i   (each product and the sum rounded on its own; d_node_i the
+ *   dlogits of those calls; alpha == 0 and a tower outside the clip are selects, not products).
+ * out6 = {L_node, node correct, node count, L_tower, towers correct, towers counted}; its first three
+ * hold the bits spwgnn_bce / spwgnn_bce_weighted write to out3 for the same inputs. out3 = {L, node
+ * correct, node count}. alpha == 0 with tower_targets allows targets == NULL (tower-only labels): the node
+ * row is then {0, 0, counted nodes}. dlogits may be NULL (loss only).
+ * The sums are per-workgroup fp32 partials added in workgroup order in double: no atomics, the same bits
+ * on every run. One launch when n <= 256 and n_towers <= 256, otherwise two. No allocation, no
+ * synchronisation; capturable. scratch: >= spwgnn_bce_tower_scratch_bytes(n, n_towers) device bytes.
+ * SPWGNN_E_ARG before any device work: a null logits, tl, out3, scratch, tl->tower_offsets or tl->out6;
+ * targets NULL unless alpha == 0 and tower_targets is set; n < 1; n_towers < 1; reserved != 0; mu <= 0
+ * or not finite; alpha < 0 or not finite; norm_t <= 0 without norm_t_dev; weights6 / total6 not both set
+ * or both NULL; lw set but not a valid spwgnn_loss_weights. */
+typedef struct spwgnn_tower_loss {
+    int32_t n_towers;
+    int32_t reserved;              /* 0 */
+    const int32_t* tower_offsets;  /* [n_towers+1] device int32 */
+    const float* tower_targets;    /* [n_towers] device fp32 0/1, or NULL = derived from targets */
+    float alpha, mu;               /* alpha >= 0, mu > 0 */
+    const float* norm_t_dev;       /* device float holding the tower divisor; NULL = use norm_t */
+    double norm_t;                 /* the divisor (the counted towers) when norm_t_dev == NULL; > 0 */
+    float* out6;                   /* [6] device */
+    float* per_tower;              /* [n_towers] device: l_u (0 for a skipped tower), or NULL = none */
+    const double* weights6;        /* with total6: total6[k] += (double)out6[k] * weights6[k], same launch */
+    double* total6;
+} spwgnn_tower_loss;
+int64_t spwgnn_bce_tower_scratch_bytes(int64_t n, int32_t n_towers);
+int32_t spwgnn_bce_tower(const float* logits, const float* targets, int64_t n,
+                         const spwgnn_loss_weights* lw /* or NULL */, const spwgnn_tower_loss* tl, float* out3,
+                         float* dlogits, void* scratch, spwgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,8 +6,8 @@ reference's interface (PropagationNetwork.getModel → fit / predict).
 """
 from .batch import TowerBatch
 from .engine import RunConfig
-from .network import GraphNetwork
+from .network import GraphNetwork, tower_bce
 from .keras_api import PropagationNetwork, KerasModel
 from . import metrics
 
-__all__ = ["TowerBatch", "RunConfig", "GraphNetwork", "PropagationNetwork", "KerasModel", "metrics"]
+__all__ = ["TowerBatch", "RunConfig", "GraphNetwork", "tower_bce", "PropagationNetwork", "KerasModel", "metrics"]

@@ -91,6 +91,14 @@ class EvalC(C.Structure):
                 ("by_size", C.c_void_p), ("hist", C.c_void_p)]
 
 
+class TowerLossC(C.Structure):
+    """spwgnn_tower_loss: the towers, weights, divisor and outputs of spwgnn_bce_tower (added within ABI 8)."""
+    _fields_ = [("n_towers", C.c_int32), ("reserved", C.c_int32), ("tower_offsets", C.c_void_p),
+                ("tower_targets", C.c_void_p), ("alpha", C.c_float), ("mu", C.c_float), ("norm_t_dev", C.c_void_p),
+                ("norm_t", C.c_double), ("out6", C.c_void_p), ("per_tower", C.c_void_p), ("weights6", C.c_void_p),
+                ("total6", C.c_void_p)]
+
+
 K_EDGE_FWD, K_NODE_FWD, K_EDGE_BWD, K_NODE_BWD, K_ENC_EDGE, K_ENC_EDGE_BWD, K_WGRAD_W2, K_DA = 1, 2, 3, 4, 5, 6, 7, 8
 K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD, K_INPUT_BWD, K_PLAN_DEVICE, K_STATE = 9, 10, 11, 12, 13, 14
 MATH_F32, MATH_X6, MATH_BF16, MATH_X3, MATH_H3 = 0, 1, 2, 3, 4
@@ -161,6 +169,8 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_accumulate_out3": (i32, [vp, vp, vp, vp]),
         "spwgnn_tower_readout": (i32, [vp, vp, i32, i32, vp, vp]),
         "spwgnn_eval_metrics": (i32, [vp, vp, i64, C.POINTER(EvalC), vp]),
+        "spwgnn_bce_tower_scratch_bytes": (i64, [i64, i32]),
+        "spwgnn_bce_tower": (i32, [vp, vp, i64, C.POINTER(LossWeightsC), C.POINTER(TowerLossC), vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -182,7 +192,7 @@ def lib() -> C.CDLL:
             raise SpwgnnError(f"{path} implements ABI {lib_.spwgnn_version()}, this binding expects {ABI_VERSION}: "
                               "rebuild with `python -m spwgnn_amd.build`")
         for which, st in ((0, BatchC), (1, RunC), (2, PlanSizes), (3, ParamInfo), (4, LossWeightsC), (6, PlanDeviceC),
-                          (7, ClipC), (9, StepWeightsC), (10, EvalC)):
+                          (7, ClipC), (9, StepWeightsC), (10, EvalC), (12, TowerLossC)):
             if lib_.spwgnn_struct_size(which) != C.sizeof(st):
                 raise SpwgnnError(f"{path} was built with a different {st.__name__} layout "
                                   f"({lib_.spwgnn_struct_size(which)} vs {C.sizeof(st)} bytes): rebuild it")

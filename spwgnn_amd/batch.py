@@ -264,6 +264,21 @@ class TowerBatch:
         out[self.node_perm] = x
         return out
 
+    def towers_to_plan_order(self, x):
+        """Per-tower rows (tower targets) in the input's tower order → the plan's (identity unless the plan
+        was packed). Plan tower t starts at input node node_perm[offset_t]; the input's towers start at
+        increasing nodes, so the rank of that node among the towers' first nodes is the input tower."""
+        if self.node_perm is None:
+            return x
+        tn = np.asarray(self.tower_nodes, np.int64)
+        if np.any(tn < 1):
+            raise ValueError("a packed plan with an empty tower has no tower order")
+        first = np.asarray(self.node_perm)[np.concatenate([[0], np.cumsum(tn)[:-1]])]
+        order = np.argsort(np.argsort(first, kind="stable"), kind="stable")
+        if isinstance(x, torch.Tensor):
+            return x[torch.as_tensor(order, device=x.device)]
+        return np.asarray(x)[order]
+
     @property
     def n_edges(self) -> int:
         return int(len(self.src))

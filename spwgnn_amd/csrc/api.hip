@@ -320,6 +320,41 @@ int32_t spwgnn_bce_weighted(const float* logits, const float* targets, int64_t n
     return bce_launch(logits, targets, n, out3, dlogits, scratch, weights3, total3, lw, stream);
 }
 
+// The tower-level loss: the node row's partials [256][3], then the towers' [kTowerBlocksMax][3]
+int64_t spwgnn_bce_tower_scratch_bytes(int64_t n, int32_t n_towers) {
+    if (n < 1 || n_towers < 1) return -1;
+    return (int64_t)(256 + kTowerBlocksMax) * 3 * sizeof(float);
+}
+
+int32_t spwgnn_bce_tower(const float* logits, const float* targets, int64_t n, const spwgnn_loss_weights* lw,
+                         const spwgnn_tower_loss* tl, float* out3, float* dlogits, void* scratch,
+                         spwgnn_stream_t stream) {
+    if (!logits || !tl || !out3 || !scratch || n < 1) return SPWGNN_E_ARG;
+    if (!tl->tower_offsets || !tl->out6 || tl->n_towers < 1 || tl->reserved != 0) return SPWGNN_E_ARG;
+    if (!std::isfinite(tl->mu) || !(tl->mu > 0.f) || !std::isfinite(tl->alpha) || tl->alpha < 0.f) return SPWGNN_E_ARG;
+    if (!targets && !(tl->alpha == 0.f && tl->tower_targets)) return SPWGNN_E_ARG;
+    if (!tl->norm_t_dev && !(tl->norm_t > 0.0)) return SPWGNN_E_ARG;
+    if ((!tl->weights6) != (!tl->total6) || (lw && !loss_weights_ok(lw))) return SPWGNN_E_ARG;
+    TowerLossArgs a{};
+    a.b = bce_args(logits, targets, n, tl->out6, nullptr, scratch, nullptr, nullptr, lw);
+    a.off = tl->tower_offsets;
+    a.ttargets = tl->tower_targets;
+    a.n_towers = tl->n_towers;
+    a.tblocks = (int)std::min<int64_t>(kTowerBlocksMax, ((int64_t)tl->n_towers + 255) / 256);
+    a.alpha = tl->alpha;
+    a.mu = tl->mu;
+    a.norm_t_dev = tl->norm_t_dev;
+    a.norm_t = tl->norm_t_dev ? 0.f : (float)tl->norm_t;
+    a.dlogits = dlogits;
+    a.tpartial = static_cast<float*>(scratch) + 256 * 3;
+    a.out3 = out3;
+    a.out6 = tl->out6;
+    a.per_tower = tl->per_tower;
+    a.w6 = tl->weights6;
+    a.tot6 = tl->total6;
+    return status(launch_bce_tower(a, static_cast<hipStream_t>(stream)));
+}
+
 int64_t spwgnn_bce_steps_scratch_bytes(int64_t n, int32_t mp_steps) {
     (void)n;
     if (mp_steps < 1 || mp_steps > kMaxSteps) return -1;

@@ -80,6 +80,7 @@ int32_t spwgnn_struct_size(int32_t which) {
         case 7: return (int32_t)sizeof(spwgnn_clip);
         case 9: return (int32_t)sizeof(spwgnn_step_weights);   // 8 stays -1
         case 10: return (int32_t)sizeof(spwgnn_eval);
+        case 12: return (int32_t)sizeof(spwgnn_tower_loss);   // 11 stays -1
         default: return -1;
     }
 }

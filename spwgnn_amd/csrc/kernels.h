@@ -496,6 +496,23 @@ struct EvalArgs {
     unsigned long long *node4, *tower6, *by_size, *hist;   // [R][4], [R][6], [R][33][6], [R][2][256]; all but node4 may be null
 };
 hipError_t launch_eval_metrics(const EvalArgs& a, hipStream_t st);
+// spwgnn_bce_tower (kernels_loss.hip): the node row of `b` (sums only: b.dlogits null, b.out3
+// = out6, b.targets null for tower-only labels) and the tower-level loss over the towers `off`, whose
+// walk also writes dlogits = alpha·d_node + d_tower
+constexpr int kTowerBlocksMax = 256;
+struct TowerLossArgs {
+    BceArgs b;
+    const int32_t* off;        // [n_towers + 1]
+    const float* ttargets;     // [n_towers] or null (derived from b.targets)
+    int n_towers, tblocks;     // workgroups [b.blocks, b.blocks + tblocks) walk the towers
+    float alpha, mu;
+    const float* norm_t_dev;
+    float norm_t;
+    float *dlogits, *tpartial, *out3, *out6, *per_tower;   // tpartial [tblocks][3]; dlogits, per_tower may be null
+    const double* w6;
+    double* tot6;
+};
+hipError_t launch_bce_tower(const TowerLossArgs& a, hipStream_t st);
 // The propagation state at the library's edge (spwgnn_forward_state / spwgnn_backward_state): P_S in
 // chunk-major node blocks → row-major [n_nodes][100], and a row-major cotangent → the chunk-major dP_S slot
 hipError_t launch_state_export(const float* P_cm, float* state, int n_nodes, hipStream_t st);

@@ -1,5 +1,5 @@
-// Keras BCE loss (one row and per step), Keras Adam and its clipped form, the step counter, the
-// read-outs, the replayed step's copy-in and the state layout kernels.
+// Keras BCE loss (one row and per step), the tower-level loss, Keras Adam and its clipped form, the step
+// counter, the read-outs, the replayed step's copy-in and the state layout kernels.
 #include "kernels.h"
 #include "loss_blocks.h"
 #include <cstdlib>
@@ -92,6 +92,187 @@ __global__ void k_bce_steps_final(BceStepsArgs a) {
         }
         bce_steps_store<W>(a, s, norm, ls, cs, ns, comb);
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The tower-level loss (spwgnn_bce_tower; the definition is in spwgnn.h). Node workgroups
+// [0, b.blocks) run the node row's sums exactly as the one-row loss does (bce_row_block without dlogits:
+// the same blocks, the same order, so out6[0:3] carries spwgnn_bce's bits); tower workgroups walk one tower
+// per thread, twice: once for s_u, T_u and the prediction, once to write dlogits = alpha·d_node + d_tower
+// with d_node recomputed by bce_dlogit / bce_dlogit_w. Every dlogit is written by its tower's thread only.
+__device__ __forceinline__ float log1mexp(float x) {
+    return x > -0.69314718f ? logf(-expm1f(x)) : log1pf(-expf(x));
+}
+// a workgroup's tree sum of three values per thread (bce_row_block's tree); thread 0 holds the result
+__device__ __forceinline__ void block_sum3(float (&v)[3]) {
+    __shared__ float t0[256], t1[256], t2[256];
+    t0[threadIdx.x] = v[0];
+    t1[threadIdx.x] = v[1];
+    t2[threadIdx.x] = v[2];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            t0[threadIdx.x] += t0[threadIdx.x + o];
+            t1[threadIdx.x] += t1[threadIdx.x + o];
+            t2[threadIdx.x] += t2[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    v[0] = t0[0];
+    v[1] = t1[0];
+    v[2] = t2[0];
+    __syncthreads();
+}
+// node workgroup `blk`: red = the node row's {Σ loss, correct, counted}; without targets {0, 0, counted}
+template <bool W>
+__device__ __forceinline__ void tower_node_block(const TowerLossArgs& a, int blk, float (&red)[3]) {
+    const BceArgs& b = a.b;
+    if (b.targets) {
+        bce_row_block<W>(b.logits, nullptr, b.targets, b.w, b.n, b.blocks, blk, 1.0f, W ? bce_norm(b) : (float)b.n, red);
+        return;
+    }
+    red[0] = red[1] = red[2] = 0.f;
+    if constexpr (W) {
+        for (int64_t i = (int64_t)blk * 256 + threadIdx.x; i < b.n; i += (int64_t)b.blocks * 256)
+            red[2] += b.w[i] != 0.f ? 1.f : 0.f;
+        block_sum3(red);
+    }
+}
+// tower workgroup `blk` of a.tblocks: red = {Σ l_u, towers correct, towers counted} over its towers
+template <bool W>
+__device__ __forceinline__ void tower_block(const TowerLossArgs& a, int blk, float (&red)[3]) {
+#pragma clang fp contract(off)   // every product and sum below is rounded on its own (spwgnn.h)
+    const BceArgs& b = a.b;
+    const float lo = logf(1e-7f), hi = log1pf(-1e-7f);
+    const float norm_t = a.norm_t_dev ? *a.norm_t_dev : a.norm_t;
+    const float inv_n = 1.0f / (W ? bce_norm(b) : (float)b.n);
+    red[0] = red[1] = red[2] = 0.f;
+    for (int64_t u = (int64_t)blk * 256 + threadIdx.x; u < a.n_towers; u += (int64_t)a.tblocks * 256) {
+        const int64_t o0 = a.off[u], o1 = a.off[u + 1];
+        const int64_t bg = std::min<int64_t>(std::max<int64_t>(o0, 0), b.n), en = std::min<int64_t>(std::max<int64_t>(o1, 0), b.n);
+        float qs = 0.f;
+        int counted = 0;
+        bool pstable = true, astable = true;
+        for (int64_t i = bg; i < en; ++i) {
+            if constexpr (W)
+                if (!(b.w[i] != 0.f)) continue;
+            const float z = b.logits[i];
+            qs = __fadd_rn(qs, __fadd_rn(fmaxf(-z, 0.f), log1pf(expf(-fabsf(z)))));
+            pstable = pstable && 1.f / (1.f + expf(-z)) > 0.5f;
+            if (!a.ttargets) astable = astable && b.targets[i] == 1.f;
+            ++counted;
+        }
+        float l = 0.f, g = 0.f;
+        bool inside = false;
+        if (counted) {
+            const bool T = a.ttargets ? a.ttargets[u] == 1.f : astable;
+            const float s = -qs;
+            const float sc = s < lo ? lo : (s > hi ? hi : s);   // selects: a NaN sum stays a NaN loss
+            inside = lo < s && s < hi;
+            l = T ? -sc : -log1mexp(sc);
+            g = inside ? (T ? -1.f : 1.f / expm1f(-s)) : 0.f;
+            red[0] += l;
+            red[1] += pstable == T ? 1.f : 0.f;
+            red[2] += 1.f;
+        }
+        if (a.per_tower) a.per_tower[u] = l;
+        if (!a.dlogits) continue;
+        const float c = __fmul_rn(a.mu, g);
+        for (int64_t i = bg; i < en; ++i) {
+            const float z = b.logits[i];
+            bool on = true;
+            float dn = 0.f;
+            if constexpr (W) {
+                const float w = b.w[i];
+                on = w != 0.f;
+                if (b.targets) dn = bce_dlogit_w(z, b.targets[i], w, inv_n);
+            } else {
+                if (b.targets) dn = bce_dlogit(z, b.targets[i], inv_n);
+            }
+            float d = a.alpha != 0.f ? __fmul_rn(a.alpha, dn) : 0.f;
+            if (on && inside) d = __fadd_rn(d, __fdiv_rn(__fmul_rn(c, 1.f / (1.f + expf(z))), norm_t));
+            a.dlogits[i] = d;
+        }
+    }
+    block_sum3(red);
+}
+// One thread: out6, out3 and the totals from the node row's sums and the towers' sums (both in double)
+template <bool W>
+__device__ __forceinline__ void tower_store(const TowerLossArgs& a, const double (&ns)[3], const double (&ts)[3]) {
+#pragma clang fp contract(off)
+    const BceArgs& b = a.b;
+    float o[6];
+    if (b.targets) {
+        float o3[3];
+        bce_row_store<W>(a.out6, nullptr, nullptr, ns[0], ns[1], ns[2], W ? bce_norm(b) : 0.f, b.n, o3);
+        o[0] = o3[0], o[1] = o3[1], o[2] = o3[2];
+    } else {
+        o[0] = o[1] = 0.f;
+        o[2] = W ? (float)ns[2] : (float)b.n;
+    }
+    const float norm_t = a.norm_t_dev ? *a.norm_t_dev : a.norm_t;
+    o[3] = (float)(ts[0] / (double)norm_t);
+    o[4] = (float)ts[1];
+    o[5] = (float)ts[2];
+    for (int k = 0; k < 6; ++k) {
+        a.out6[k] = o[k];
+        if (a.tot6) a.tot6[k] += (double)o[k] * a.w6[k];
+    }
+    a.out3[0] = (float)((double)a.alpha * (double)o[0] + (double)a.mu * (double)o[3]);
+    a.out3[1] = o[1];
+    a.out3[2] = o[2];
+}
+// n <= 256 and n_towers <= 256 (the reference's batch): one workgroup, one launch
+template <bool W>
+__global__ __launch_bounds__(256) void k_bce_tower_one(TowerLossArgs a) {
+    float nr[3], tr[3];
+    tower_node_block<W>(a, 0, nr);
+    tower_block<W>(a, 0, tr);
+    if (threadIdx.x != 0) return;
+    const double ns[3] = {(double)nr[0], (double)nr[1], W ? (double)nr[2] : 0.0};
+    const double ts[3] = {(double)tr[0], (double)tr[1], (double)tr[2]};
+    tower_store<W>(a, ns, ts);
+}
+template <bool W>
+__global__ __launch_bounds__(256) void k_bce_tower_partial(TowerLossArgs a) {
+    const int nb = a.b.blocks;
+    float red[3];
+    const bool node = (int)blockIdx.x < nb;   // uniform per workgroup
+    if (node) tower_node_block<W>(a, blockIdx.x, red);
+    else tower_block<W>(a, (int)blockIdx.x - nb, red);
+    if (threadIdx.x != 0) return;
+    float* q = node ? a.b.partial + 3 * blockIdx.x : a.tpartial + 3 * ((int)blockIdx.x - nb);
+    q[0] = red[0];
+    q[1] = red[1];
+    q[2] = node && !W ? 0.f : red[2];
+}
+template <bool W>
+__global__ void k_bce_tower_final(TowerLossArgs a) {
+    if (threadIdx.x != 0) return;
+    double ns[3] = {0.0, 0.0, 0.0}, ts[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < a.b.blocks; ++k)
+        for (int j = 0; j < 3; ++j) ns[j] += a.b.partial[3 * k + j];
+    for (int k = 0; k < a.tblocks; ++k)
+        for (int j = 0; j < 3; ++j) ts[j] += a.tpartial[3 * k + j];
+    tower_store<W>(a, ns, ts);
+}
+hipError_t launch_bce_tower(const TowerLossArgs& a, hipStream_t st) {
+    if (a.b.blocks < 1 || a.tblocks < 1 || a.tblocks > kTowerBlocksMax) return hipErrorInvalidValue;
+    const dim3 b(256);
+    if (a.b.blocks == 1 && a.tblocks == 1) {
+        if (a.b.w) hipLaunchKernelGGL(k_bce_tower_one<true>, dim3(1), b, 0, st, a);
+        else hipLaunchKernelGGL(k_bce_tower_one<false>, dim3(1), b, 0, st, a);
+        return hipGetLastError();
+    }
+    const dim3 g(a.b.blocks + a.tblocks);
+    if (a.b.w) {
+        hipLaunchKernelGGL(k_bce_tower_partial<true>, g, b, 0, st, a);
+        hipLaunchKernelGGL(k_bce_tower_final<true>, dim3(1), dim3(64), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(k_bce_tower_partial<false>, g, b, 0, st, a);
+        hipLaunchKernelGGL(k_bce_tower_final<false>, dim3(1), dim3(64), 0, st, a);
+    }
+    return hipGetLastError();
 }
 
 __global__ void k_adam(AdamArgs a) {

@@ -544,6 +544,122 @@ def bce(logits: torch.Tensor, targets: torch.Tensor, scratch: BceScratch, dlogit
     return scratch.out3, dlogits
 
 
+def check_tower_loss(tower_loss, node_loss=1.0) -> tuple:
+    """(mu, alpha) of the tower-level loss L = alpha·L_node + mu·L_tower: mu finite and >= 0 (0 = the
+    tower term is off and every front end runs the launches it ran without it), alpha finite and >= 0."""
+    mu, alpha = float(tower_loss), float(node_loss)
+    if not (0.0 <= mu < float("inf")) or not (0.0 <= alpha < float("inf")):   # False for a NaN
+        raise ValueError(f"tower_loss and node_loss must be finite and >= 0 (got {tower_loss}, {node_loss})")
+    return mu, alpha
+
+
+def counted_towers(batch: TowerBatch, node_weights: Optional[torch.Tensor] = None) -> int:
+    """The towers of `batch` with at least one counted node — the tower loss's divisor norm_t. Without
+    weights a host count; with weights one host sync."""
+    if node_weights is None:
+        return int((batch.tower_nodes > 0).sum())
+    return counted_nodes_towers(batch, node_weights)[1]
+
+
+def counted_nodes_towers(batch: TowerBatch, node_weights: torch.Tensor) -> tuple:
+    """(nodes with a non-zero weight, towers holding one) of `batch`, read with one host sync."""
+    nz = (node_weights.reshape(-1) != 0).to(torch.int64)
+    on = torch.cat([nz.new_zeros(1), nz.cumsum(0)])
+    off = batch.tower_offsets.to(on.device, torch.int64)
+    k, t = torch.stack([on[-1], ((on[off[1:]] - on[off[:-1]]) > 0).sum()]).tolist()
+    return int(k), int(t)
+
+
+class TowerLossScratch:
+    """The buffers of `bce_tower`: its scratch, out3 = [L, node correct, node count] and out6 = [L_node, node
+    correct, node count, L_tower, towers correct, towers counted]; with ``totals`` the fp64 epoch sums
+    total6 += out6 · weights6 of the same launch (weights6 preset to ones)."""
+
+    def __init__(self, device, totals: bool = False):
+        n = int(_lib.lib().spwgnn_bce_tower_scratch_bytes(1, 1))
+        self.scratch = torch.empty(n, dtype=torch.uint8, device=device)
+        self.out3 = torch.empty(3, dtype=torch.float32, device=device)
+        self.out6 = torch.empty(6, dtype=torch.float32, device=device)
+        self.total6 = torch.zeros(6, dtype=torch.float64, device=device) if totals else None
+        self.weights6 = torch.ones(6, dtype=torch.float64, device=device) if totals else None
+
+
+def bce_tower(logits: torch.Tensor, targets: Optional[torch.Tensor], batch: TowerBatch, scratch: TowerLossScratch,
+              tower_loss: float = 1.0, node_loss: float = 1.0, tower_targets: Optional[torch.Tensor] = None,
+              norm_t=None, dlogits: Optional[torch.Tensor] = None, node_weights: Optional[torch.Tensor] = None,
+              norm=None, total6: Optional[torch.Tensor] = None, weights6: Optional[torch.Tensor] = None,
+              per_tower: Optional[torch.Tensor] = None, want_dlogits: bool = True):
+    """The combined objective L = node_loss·L_node + tower_loss·L_tower and d L / d logit on the device
+    (spwgnn_bce_tower; the exact definition is in include/spwgnn.h). L_node is `bce`'s loss (with
+    `node_weights` / `norm`, its weighted one); L_tower is the binary cross-entropy of "every counted block of
+    the tower stands", P_u = Π σ(z_i), against the tower's label: ``tower_targets`` ((n_towers,) 0/1, in the
+    PLAN's tower order: `TowerBatch.towers_to_plan_order`) or, when None, 1 iff every counted node target is 1.
+    A zero node weight masks its node out of its tower as well; a tower without a counted node is skipped.
+    ``norm_t``: the tower divisor — a number, a one-element device fp32 tensor, or None = the towers with a
+    counted node (`counted_towers`; with weights one host sync). ``targets`` may be None for tower-only labels
+    (node_loss 0 and tower_targets given). ``logits`` and ``targets`` are in the plan's node order.
+    Returns (out3, dlogits); scratch.out6 holds the six parts. ``per_tower``: an (n_towers,) fp32 buffer for
+    the per-tower losses. ``want_dlogits`` False: the loss only (evaluation)."""
+    _require_gpu(logits, "logits")
+    mu, alpha = check_tower_loss(tower_loss, node_loss)
+    if not mu > 0:
+        raise ValueError("bce_tower needs tower_loss > 0; without the tower term use bce")
+    if logits.dim() != 1 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("logits must be a contiguous fp32 (n,) tensor")
+    n, T = int(logits.numel()), int(batch.n_towers)
+    if n != batch.n_nodes:
+        raise ValueError(f"logits must hold one value per node of the batch ({batch.n_nodes}), got {n}")
+    if targets is None:
+        if alpha != 0 or tower_targets is None:
+            raise ValueError("targets may be None only with node_loss == 0 and tower_targets given")
+    else:
+        targets = targets.reshape(-1).to(torch.float32).contiguous()
+        if targets.numel() != n or targets.device != logits.device:
+            raise ValueError(f"targets must hold one value per node ({n}) on {logits.device}")
+    off = batch.tower_offsets
+    if off.device != logits.device or off.dtype != torch.int32 or off.numel() != T + 1:
+        raise ValueError("the batch's tower offsets must be (n_towers + 1,) int32 on the logits' device")
+    tl = _lib.TowerLossC()
+    tl.n_towers, tl.tower_offsets, tl.alpha, tl.mu = T, off.data_ptr(), alpha, mu
+    if tower_targets is not None:
+        tower_targets = tower_targets.reshape(-1).to(torch.float32).contiguous()
+        if tower_targets.numel() != T or tower_targets.device != logits.device:
+            raise ValueError(f"tower_targets must hold one value per tower ({T}) on {logits.device}")
+        tl.tower_targets = tower_targets.data_ptr()
+    lw = keep = None
+    if node_weights is not None:
+        lw, keep = _loss_weights(node_weights, norm, logits)
+    elif norm is not None:
+        raise ValueError("norm goes with node_weights")
+    if norm_t is None:
+        norm_t = max(counted_towers(batch, keep[0] if keep else None), 1)
+    if isinstance(norm_t, torch.Tensor):
+        if norm_t.dtype != torch.float32 or norm_t.numel() != 1 or norm_t.device != logits.device:
+            raise ValueError("a device norm_t is one fp32 element on the logits' device")
+        tl.norm_t_dev = norm_t.data_ptr()
+    else:
+        if not float(norm_t) > 0:
+            raise ValueError(f"norm_t must be > 0 (got {norm_t}); pass max(counted towers, 1)")
+        tl.norm_t = float(norm_t)
+    if (total6 is None) != (weights6 is None):
+        raise ValueError("total6 and weights6 go together")
+    if total6 is not None:
+        assert total6.dtype == torch.float64 and weights6.dtype == torch.float64 and total6.numel() == 6 == weights6.numel()
+        tl.total6, tl.weights6 = total6.data_ptr(), weights6.data_ptr()
+    if per_tower is not None:
+        _out_buffer(per_tower, (T,), "per_tower")
+        tl.per_tower = per_tower.data_ptr()
+    tl.out6 = scratch.out6.data_ptr()
+    if want_dlogits and dlogits is None:
+        dlogits = _poison(torch.empty_like(logits))
+    st = _lib.lib().spwgnn_bce_tower(
+        logits.data_ptr(), targets.data_ptr() if targets is not None else None, n, C.byref(lw) if lw is not None else None,
+        C.byref(tl), scratch.out3.data_ptr(), dlogits.data_ptr() if want_dlogits else None, scratch.scratch.data_ptr(),
+        _stream(logits.device))
+    _lib.check(st, "spwgnn_bce_tower")
+    return scratch.out3, (dlogits if want_dlogits else None)
+
+
 def check_step_weights(step_loss_weights, mp_steps: int):
     """Validates per-step loss weights λ (deep supervision): ``mp_steps`` finite floats >= 0, not all zero
     — the rules spwgnn_bce_steps refuses by. Returns them as a tuple of floats."""

@@ -22,7 +22,7 @@ from . import params as P
 from .batch import HostPlan, TowerBatch
 from .network import GraphNetwork
 from .replay import DeviceCounters, ReplayCache, step_body
-from .step import AdamUpdate, DeepLossPath, LossPath, delegated
+from .step import AdamUpdate, DeepLossPath, LossPath, TowerLossPath, delegated
 
 
 def node_weights(target, sample_weight=None, class_weight=None) -> np.ndarray:
@@ -111,7 +111,7 @@ class KerasModel:
 
     def __init__(self, net: GraphNetwork, n_objects: int, object_dim: int = 3, lr: float = 5e-4,
                  l2: float = 0.0, clipnorm: float = 0.0, clipvalue: float = 0.0, decay: float = 0.0,
-                 skip_nonfinite: bool = False, step_loss_weights=None):
+                 skip_nonfinite: bool = False, step_loss_weights=None, tower_loss: float = 0.0, node_loss: float = 1.0):
         if object_dim != 3:
             # Networks.py:70-73 + main.py:28-31/59-63: the object_dim=2 path of the reference is
             # broken (om gets 1 feature, boxes[...,2] is out of range); only the Jenga layout runs.
@@ -128,6 +128,14 @@ class KerasModel:
         self._plain = LossPath(dev, net.mp_steps)
         self._path = self._plain if step_loss_weights is None else DeepLossPath(dev, net.mp_steps, step_loss_weights)
         self._rows: Optional[DeepLossPath] = None
+        # the tower-level loss: tower_loss > 0 trains on node_loss·L_node + tower_loss·L_tower; 0 =
+        # off, exactly the launches of before (node_loss is then not read)
+        self.tower_loss, self.node_loss = E.check_tower_loss(tower_loss, node_loss)
+        if self.tower_loss > 0:
+            if step_loss_weights is not None:
+                raise ValueError("tower_loss and step_loss_weights do not combine (the tower term on per-step rows "
+                                 "is not built)")
+            self._path = TowerLossPath(dev, net.mp_steps, self.tower_loss, self.node_loss, totals=True)
         self.step_loss_weights = self._path.lam
         self._tot_s = None if step_loss_weights is None else torch.zeros(net.mp_steps, 3, dtype=torch.float64, device=dev)
         self.m = torch.zeros_like(net.flat.data)
@@ -187,16 +195,26 @@ class KerasModel:
         return out
 
     # ---------------------------------------------------------------- training
-    def train_on_batch(self, batch: TowerBatch, target: torch.Tensor, node_weights=None):
+    def train_on_batch(self, batch: TowerBatch, target: torch.Tensor, node_weights=None, tower_targets=None):
         """One Keras step: forward (dropout on), BCE, backward, Adam. Returns out3 = [loss, correct, n]
         (device). `node_weights` (one per node, in the targets' order): the weighted loss of engine.bce
         with the divisor max(#non-zero weights, 1) (one host sync to count them). With step_loss_weights
-        out3 = [Σ_s λ_s·loss_s, the last step's correct, n] and `step_out3` holds the (S, 3) per-step rows."""
+        out3 = [Σ_s λ_s·loss_s, the last step's correct, n] and `step_out3` holds the (S, 3) per-step rows.
+        With tower_loss the loss is node_loss·L_node + tower_loss·L_tower (`loss_parts`: its six parts);
+        `tower_targets`: (n_towers,) 0/1 labels, None = derived from the node targets; a `target` of None
+        (tower-only labels) drops the node term."""
         net, path = self.net, self._path
         net._step_seed += 1
         run = net.run_config(True, dropout=net.dropout, seed=net._step_seed)
         z = path.forward(net.flat.data, batch, run, self._ws)
-        out3, dz = path.loss(z, target, node_weights=self._dev_weights(node_weights))
+        if self.tower_loss > 0:
+            out3, dz = path.loss(z, target, node_weights=self._dev_weights(node_weights), batch=batch,
+                                 tower_targets=self._dev_weights(tower_targets),
+                                 node_loss=0.0 if target is None else None)
+        else:
+            if tower_targets is not None:
+                raise ValueError("tower_targets need a model with tower_loss > 0")
+            out3, dz = path.loss(z, target, node_weights=self._dev_weights(node_weights))
         path.backward(net.flat.data, batch, run, self._ws, dz, self._grads)
         self.iterations += 1
         self.opt.update(net.flat.data, self._grads, self.m, self.v, self.iterations)
@@ -213,6 +231,12 @@ class KerasModel:
         """The last clipped step's [norm, scale, skipped, clipped] (device tensor), None before one."""
         return None if self.opt.scratch is None else self.opt.scratch.out4
 
+    @property
+    def loss_parts(self) -> Optional[torch.Tensor]:
+        """The last tower loss's [L_node, node correct, node count, L_tower, towers correct, towers counted]
+        (device tensor), None without tower_loss."""
+        return self._path.tower.out6 if self.tower_loss > 0 else None
+
     def _dev_weights(self, node_weights) -> Optional[torch.Tensor]:
         if node_weights is None:
             return None
@@ -227,12 +251,25 @@ class KerasModel:
                          lambda **kw: net.run_config(True, dropout=net.dropout, **kw), _lib.STEP_KEY_COUNTER,
                          sums=(self._tot, self._tot_s, self._w3))
 
-    def evaluate_batch(self, batch: TowerBatch, target: torch.Tensor, node_weights=None, norm=None):
+    def evaluate_batch(self, batch: TowerBatch, target: torch.Tensor, node_weights=None, norm=None, tower_targets=None):
         """out3 = [loss, correct, n] of an inference forward ([Σ_s λ_s·loss_s, the last step's correct, n] with
         step_loss_weights); `node_weights` / `norm` as engine.bce takes them (norm None: the non-zero weights
-        are counted, one host sync)."""
+        are counted, one host sync). With tower_loss: [node_loss·L_node + tower_loss·L_tower, node correct, n],
+        the six parts in `loss_parts`; `tower_targets` and a `target` of None as in `train_on_batch`."""
         z = self._path.forward(self.net.flat.data, batch, self.net.run_config(), self._ws)
+        if self.tower_loss > 0:
+            return self._tower_eval(z, batch, target, self._dev_weights(node_weights), norm,
+                                    self._dev_weights(tower_targets))
         return self._path.loss(z, target, node_weights=self._dev_weights(node_weights), norm=norm)[0]
+
+    def _tower_eval(self, z, batch, target, w, norm, tower_targets, sums: bool = False):
+        """The tower loss of inference logits, no gradient; `sums`: added to the path's epoch sums (else those
+        are left alone)."""
+        t = self._path.tower
+        return E.bce_tower(z, target, batch, t, self.tower_loss, 0.0 if target is None else self.node_loss,
+                           tower_targets=tower_targets, node_weights=w, norm=norm,
+                           total6=t.total6 if sums else None, weights6=t.weights6 if sums else None,
+                           want_dlogits=False)[0]
 
     def evaluate(self, x: Dict[str, np.ndarray], y, batch_size: int = 32768, sample_weight=None,
                  threshold: float = 0.5, return_dict: bool = False, return_steps: bool = False):
@@ -252,6 +289,10 @@ class KerasModel:
         With step_loss_weights the model's loss is Σ_s λ_s·loss_s, as in `fit`: it is the last entry's ``loss``,
         and every entry carries its own as ``step_loss``."""
         from . import metrics as M
+        if self.tower_loss > 0:
+            return self._evaluate_tower(x, y, batch_size, sample_weight, threshold, return_dict, return_steps)
+        if isinstance(y, dict) and "tower_target" in y:
+            raise ValueError("y['tower_target'] needs a model with tower_loss > 0")
         objects = np.asarray(x["objects"], np.float32)
         B = objects.shape[0]
         target = np.asarray(y["target"] if isinstance(y, dict) else y, np.float32).reshape(B, -1)
@@ -317,6 +358,11 @@ class KerasModel:
         With step_loss_weights set on the model `loss` / `val_loss` are Σ_s λ_s·loss_s, `binary_accuracy` stays
         the last step's, and the history gains `step_loss` and `step_binary_accuracy`: per epoch a list of S
         values, each step's own loss and accuracy, summed on the device in the loss launch."""
+        if self.tower_loss > 0:
+            return self._fit_tower(x, y, batch_size, epochs, validation_split, shuffle, verbose, seed, graph,
+                                   sample_weight, class_weight)
+        if "tower_target" in y:
+            raise ValueError("y['tower_target'] needs a model with tower_loss > 0")
         objects = np.asarray(x["objects"], np.float32)
         target = np.asarray(y["target"], np.float32).reshape(objects.shape[0], -1)
         B = objects.shape[0]
@@ -418,6 +464,191 @@ class KerasModel:
         return hist
 
 
+    # ---------------------------------------------------------------- the tower-level loss
+    def _tower_labels(self, x, y, sample_weight, class_weight=None):
+        """(B, N, node targets (B, N) or None, tower targets (B,) or None, node weights (B, N) or None) of a
+        fit / evaluate call on a tower-loss model. Without 'target' the node term is off (node_loss 0)."""
+        B, N = np.shape(x["objects"])[:2]
+        y = y if isinstance(y, dict) else {"target": y}
+        target = np.asarray(y["target"], np.float32).reshape(B, -1) if "target" in y else None
+        tt = np.asarray(y["tower_target"], np.float32).reshape(-1) if "tower_target" in y else None
+        if target is None and tt is None:
+            raise ValueError("y needs 'target', 'tower_target' or both")
+        if tt is not None and tt.shape != (B,):
+            raise ValueError(f"y['tower_target'] must hold one label per tower ({B},), got {tt.shape}")
+        W = None
+        if sample_weight is not None or class_weight is not None:
+            if target is None and class_weight is not None:
+                raise ValueError("class_weight goes by the node targets: it needs y['target']")
+            W = node_weights(target if target is not None else np.zeros((B, N), np.float32), sample_weight, class_weight)
+        return B, N, target, tt, W
+
+    def _tower_step(self, batch, target, w, tt):
+        """One eager fit step with the tower loss: the replayed step's launches (spwgnn_amd/replay.py step_body)
+        with this batch's own buffers — the key/step advance, the forward, the loss launch and the backward,
+        Adam at the device step word. Explicit tower targets and weighted batches take it: their labels and
+        the tower divisor, a per-batch count, are not part of a replayed geometry's static block."""
+        net, path, ctr = self.net, self._path, self._ctr
+        E.step_advance(ctr.key, ctr.step, _lib.STEP_KEY_COUNTER, 0, 0)
+        run = net.run_config(True, dropout=net.dropout, seed_dev=ctr.key)
+        z = path.forward(net.flat.data, batch, run, self._ws)
+        path.loss_backward(net.flat.data, batch, run, self._ws, z, target, None, None, self._grads, node_weights=w,
+                           tower_targets=tt, node_loss=0.0 if target is None else None)
+        self.opt.update_dev(net.flat.data, self._grads, self.m, self.v, ctr, self.opt.totals)
+
+    def _fit_tower(self, x, y, batch_size, epochs, validation_split, shuffle, verbose, seed, graph, sample_weight,
+                   class_weight):
+        """`fit` with tower_loss > 0. y: {'target': (B, N[, 1])} (tower labels derived: a tower stands iff every
+        counted node target is 1), {'tower_target': (B,)} alone (tower-only labels: node_loss is forced to 0) or
+        both. Derived labels without weights run the replayed step (`graph` as in `fit`); explicit tower
+        targets or weights run the same launches eagerly per batch (`_tower_step`). The history holds `loss`
+        (= node_loss·L_node + tower_loss·L_tower), `binary_accuracy`, `tower_loss` (L_tower) and
+        `tower_accuracy`, with `val_` forms under validation_split — batch means weighted by the batch's
+        towers, as `fit`'s — and the clip statistics of `fit`. Each batch's L_tower divides by its own
+        counted towers."""
+        B, N, target, tt, W = self._tower_labels(x, y, sample_weight, class_weight)
+        alpha = self.node_loss if target is not None else 0.0
+        weighted = W is not None
+        replayed = tt is None and not weighted
+        n_tr = keras_split_at(B, validation_split)
+        n_val = B - n_tr
+        ds = CompactDataset(np.asarray(x["objects"], np.float32), x["sender_relations"], x["receiver_relations"],
+                            x.get("propagation"))
+        rng = np.random.default_rng(seed)
+        dev, path = self.net.device, self._path
+        tot6, w6 = path.tower.total6, path.tower.weights6
+        hist = {"loss": [], "binary_accuracy": [], "tower_loss": [], "tower_accuracy": []}
+        clip_on = self._clip_on()
+        if clip_on:
+            hist.update({"grad_norm": [], "clipped_steps": [], "skipped_steps": []})
+            clip = self._clip_scratch()
+        if n_val:
+            hist.update({"val_" + k: [] for k in ("loss", "binary_accuracy", "tower_loss", "tower_accuracy")})
+            vbatch = ds.subset(np.arange(n_tr, B), dev)
+            vtgt = None if target is None else torch.as_tensor(target[n_tr:], device=dev).reshape(-1).contiguous()
+            vw = self._dev_weights(W[n_tr:]) if weighted else None
+            vnorm = max(int(np.count_nonzero(W[n_tr:])), 1) if weighted else None
+            vtt = self._dev_weights(tt[n_tr:]) if tt is not None else None
+        if self._ctr is None:
+            self._ctr = DeviceCounters(dev, self.net._step_seed, self.iterations, self.lr, self.beta1,
+                                       self.beta2, decay=self.decay)
+        else:
+            self._ctr.set(key=self.net._step_seed, step=self.iterations, lr=self.lr, beta1=self.beta1,
+                          beta2=self.beta2, decay=self.decay)
+        opts = (graph, "tower", self.tower_loss, alpha, self.clipnorm, self.clipvalue, self.skip_nonfinite, clip_on)
+        if replayed and (self._replays is None or self._replay_graph != opts):
+            net = self.net
+            self._replays = ReplayCache(dev, lambda: step_body(
+                net.flat.data, self._grads, self.m, self.v, path, self.opt, self._ctr,
+                lambda **kw: net.run_config(True, dropout=net.dropout, **kw), _lib.STEP_KEY_COUNTER), graph=graph)
+            self._replay_graph = opts
+        ep_tot = torch.zeros(epochs, 6, dtype=torch.float64, device=dev)
+        ep_val = torch.zeros(epochs, 6, dtype=torch.float32, device=dev)
+        ep_clip = torch.zeros(epochs, 4, dtype=torch.float64, device=dev) if clip_on else None
+        mu = self.tower_loss
+
+        def record(ep):
+            t = ep_tot[ep].tolist()
+            hist["loss"].append((alpha * t[0] + mu * t[3]) / max(n_tr, 1))
+            hist["binary_accuracy"].append(t[1] / max(t[2], 1))
+            hist["tower_loss"].append(t[3] / max(n_tr, 1))
+            hist["tower_accuracy"].append(t[4] / max(t[5], 1))
+            if clip_on:
+                c_norm, c_clipped, c_skipped, c_steps = ep_clip[ep].tolist()
+                hist["grad_norm"].append(c_norm / max(c_steps - c_skipped, 1.0))
+                hist["clipped_steps"].append(int(c_clipped))
+                hist["skipped_steps"].append(int(c_skipped))
+            if n_val:
+                v = ep_val[ep].tolist()
+                hist["val_loss"].append(alpha * v[0] + mu * v[3])
+                hist["val_binary_accuracy"].append(v[1] / max(v[2], 1))
+                hist["val_tower_loss"].append(v[3])
+                hist["val_tower_accuracy"].append(v[4] / max(v[5], 1))
+
+        for ep in range(epochs):
+            order = rng.permutation(n_tr) if shuffle else np.arange(n_tr)
+            tot6.zero_()
+            if clip_on:
+                clip.total4.zero_()
+            for b0 in range(0, n_tr, batch_size):
+                idx = order[b0:b0 + batch_size]
+                w6.copy_(self._weights6(len(idx)))          # stream-ordered: the step's loss launch reads it
+                plan = ds.subset_plan(idx, edge_cap=True)
+                if replayed:
+                    self._replays(plan, target[idx])
+                else:
+                    self._tower_step(TowerBatch.from_plan(plan, dev),
+                                     None if target is None else torch.as_tensor(target[idx], device=dev).reshape(-1).contiguous(),
+                                     self._dev_weights(W[idx]) if weighted else None,
+                                     self._dev_weights(tt[idx]) if tt is not None else None)
+                self.net._step_seed += 1
+                self.iterations += 1
+            ep_tot[ep].copy_(tot6)
+            if clip_on:
+                ep_clip[ep].copy_(clip.total4)
+            if n_val:
+                self.evaluate_batch(vbatch, vtgt, vw, vnorm, vtt)
+                ep_val[ep].copy_(path.tower.out6)
+            if verbose:
+                record(ep)
+                msg = (f"Epoch {ep + 1}/{epochs} - loss: {hist['loss'][-1]:.4f} - binary_accuracy: "
+                       f"{hist['binary_accuracy'][-1]:.4f} - tower_loss: {hist['tower_loss'][-1]:.4f} - tower_accuracy: "
+                       f"{hist['tower_accuracy'][-1]:.4f}")
+                if n_val:
+                    msg += (f" - val_loss: {hist['val_loss'][-1]:.4f} - val_tower_loss: {hist['val_tower_loss'][-1]:.4f}"
+                            f" - val_tower_accuracy: {hist['val_tower_accuracy'][-1]:.4f}")
+                print(msg)
+        w6.fill_(1.0)
+        if not verbose:
+            for ep in range(epochs):
+                record(ep)
+        for k, v in hist.items():
+            self.history.setdefault(k, []).extend(v)
+        return hist
+
+    def _weights6(self, towers: int) -> torch.Tensor:
+        """The epoch sums' fp64 weights of out6: the two losses times the batch's towers (fit's convention)."""
+        key = ("w6", towers)
+        if key not in self._w3:
+            self._w3[key] = torch.tensor([float(towers), 1.0, 1.0, float(towers), 1.0, 1.0], dtype=torch.float64,
+                                         device=self.net.device)
+        return self._w3[key]
+
+    def _evaluate_tower(self, x, y, batch_size, sample_weight, threshold, return_dict, return_steps):
+        """`evaluate` with tower_loss > 0: [loss, binary_accuracy, tower_loss, tower_accuracy], or with
+        ``return_dict`` the summary of `evaluate` plus ``tower_loss`` and ``tower_accuracy`` (at 0.5, against the
+        labels the loss uses: y['tower_target'] or the derived ones); ``loss`` is node_loss·L_node +
+        tower_loss·L_tower. y as in `fit`."""
+        from . import metrics as M
+        if return_steps:
+            raise ValueError("return_steps is not built for tower-loss models")
+        B, N, target, tt, W = self._tower_labels(x, y, sample_weight)
+        alpha = self.node_loss if target is not None else 0.0
+        tau = E.check_threshold(threshold)
+        dev, net, path = self.net.device, self.net, self._path
+        tables = E.EvalTables(dev) if target is not None else None
+        tot = torch.zeros(6, dtype=torch.float64, device=dev)
+        run = net.run_config()
+        for idx, batch in self._dense_slices(x, batch_size):
+            tgt = None if target is None else torch.as_tensor(target[idx], device=dev).reshape(-1).contiguous()
+            w = self._dev_weights(W[idx]) if W is not None else None
+            norm = max(int(np.count_nonzero(W[idx])), 1) if W is not None else None
+            z = path.forward(net.flat.data, batch, run, self._ws)
+            self._tower_eval(z, batch, tgt, w, norm, self._dev_weights(tt[idx]) if tt is not None else None)
+            tot += path.tower.out6.double() * self._weights6(batch.n_towers)
+            if tables is not None:
+                E.eval_metrics(z, tgt, tables, batch=batch, node_weights=w, threshold=tau)
+        t = tot.tolist()
+        parts = dict(loss=(alpha * t[0] + self.tower_loss * t[3]) / max(B, 1), tower_loss=t[3] / max(B, 1),
+                     tower_accuracy=t[4] / max(t[5], 1))
+        acc = t[1] / max(t[2], 1)
+        if not return_dict:
+            return [parts["loss"], acc, parts["tower_loss"], parts["tower_accuracy"]]
+        out = dict(M.summarize(tables.cpu())) if tables is not None else {"binary_accuracy": acc}
+        out.update(parts)
+        return out
+
+
 def keras_split_at(n_samples: int, validation_split: float) -> int:
     """Number of training samples Keras 2.x keeps for fit(validation_split=v) (main.py:96):
     split_at = int(n · (1 − v)); the validation set is the LAST n − split_at samples, taken before
@@ -435,13 +666,16 @@ class PropagationNetwork:
 
     def __init__(self, device="cuda", seed: int = 0, mp_steps: int = E.REF_MP_STEPS, dropout: float = E.REF_DROPOUT,
                  math: str = "x6", clipnorm: float = 0.0, clipvalue: float = 0.0, decay: float = 0.0,
-                 skip_nonfinite: bool = False, step_loss_weights=None):
+                 skip_nonfinite: bool = False, step_loss_weights=None, tower_loss: float = 0.0, node_loss: float = 1.0):
         # Networks.py:101 Adam(lr=0.0005, decay=0.0); clipnorm / clipvalue are Keras 2.x Optimizer kwargs
         E.check_clip_options(clipnorm, clipvalue, decay)
         if step_loss_weights is not None:   # deep supervision (KerasModel): one weight per propagation step
             step_loss_weights = E.check_step_weights(step_loss_weights, mp_steps)
+        tower_loss, node_loss = E.check_tower_loss(tower_loss, node_loss)   # the tower-level loss (KerasModel); 0 = off
+        if tower_loss > 0 and step_loss_weights is not None:
+            raise ValueError("tower_loss and step_loss_weights do not combine")
         self._opt = dict(clipnorm=clipnorm, clipvalue=clipvalue, decay=decay, skip_nonfinite=skip_nonfinite,
-                         step_loss_weights=step_loss_weights)
+                         step_loss_weights=step_loss_weights, tower_loss=tower_loss, node_loss=node_loss)
         if math not in E.MATH_MODES:
             raise ValueError(f"math must be one of {sorted(E.MATH_MODES)}")
         self._math = math   # every model's arithmetic (GraphNetwork.math); "x6": the fp32-class default

@@ -51,6 +51,40 @@ class _PropagationFn(torch.autograd.Function):
         return grads, dprop, dobj, None, None, None, None, None
 
 
+class _TowerLossFn(torch.autograd.Function):
+    """`tower_bce`: the loss launch of `engine.bce_tower` in the forward, which also writes d L / d logit;
+    the backward scales that stored dlogits by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, batch, scratch, tower_loss, node_loss, tower_targets, node_weights, norm, norm_t):
+        out3, dz = E.bce_tower(logits.detach().reshape(-1).to(torch.float32).contiguous(), targets, batch, scratch,
+                               tower_loss, node_loss, tower_targets=tower_targets, norm_t=norm_t,
+                               node_weights=node_weights, norm=norm)
+        ctx.save_for_backward(dz)
+        ctx.shape, ctx.dtype = logits.shape, logits.dtype
+        return out3[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        (dz,) = ctx.saved_tensors
+        return (grad * dz).reshape(ctx.shape).to(ctx.dtype), *([None] * 9)
+
+
+def tower_bce(logits: torch.Tensor, targets: Optional[torch.Tensor], batch: TowerBatch, tower_loss: float = 1.0,
+              node_loss: float = 1.0, tower_targets: Optional[torch.Tensor] = None,
+              node_weights: Optional[torch.Tensor] = None, norm=None, norm_t=None,
+              scratch: Optional["E.TowerLossScratch"] = None) -> torch.Tensor:
+    """The scalar L = node_loss·L_node + tower_loss·L_tower of `engine.bce_tower` as a
+    differentiable function of ``logits`` — what `GraphNetwork.forward_batch` returned for ``batch``, in the
+    plan's node order, as ``targets`` (`TowerBatch.to_plan_order`) and ``tower_targets``
+    (`TowerBatch.towers_to_plan_order`) are. ``scratch.out6`` (pass your own `engine.TowerLossScratch` to
+    read it) holds the six parts of the last call."""
+    if scratch is None:
+        scratch = E.TowerLossScratch(logits.device)
+    return _TowerLossFn.apply(logits, targets, batch, scratch, tower_loss, node_loss, tower_targets, node_weights,
+                              norm, norm_t)
+
+
 class GraphNetwork(nn.Module):
     """Propagation network (rm, om, rmp, omp) with shared weights across sizes and steps.
 

@@ -89,11 +89,16 @@ class StaticBatch:
 
     `weighted`: the block also carries per-node loss weights (n_nodes floats) and their divisor (one
     float) after the targets, each padded to 16 bytes and moved by the same copy: `weights` and
-    `norm` are the device views a weighted loss reads (engine.bce's node_weights / norm)."""
+    `norm` are the device views a weighted loss reads (engine.bce's node_weights / norm).
+
+    `towers`: the block also carries the plan's tower offsets (n_towers + 1 int32) and the number of its
+    towers that hold a node (one float): plans of one geometry may cut the same nodes into different towers,
+    so a step that walks towers (the tower-level loss) reads both from the block — `batch.tower_offsets` is
+    then the view `tower_offsets`, and `norm_t` the divisor (engine.bce_tower's norm_t)."""
 
     SLOTS = 2
 
-    def __init__(self, plan: HostPlan, device, weighted: bool = False):
+    def __init__(self, plan: HostPlan, device, weighted: bool = False, towers: bool = False):
         self.device = torch.device(device)
         self.geometry = plan.geometry
         self.offsets, total = [], 0
@@ -109,6 +114,12 @@ class StaticBatch:
             total += (plan.n_nodes * 4 + 15) // 16 * 16
             self.norm_off = total
             total += 16
+        self.towers = bool(towers)
+        if self.towers:
+            self.off_off = total
+            total += ((plan.n_towers + 1) * 4 + 15) // 16 * 16
+            self.norm_t_off = total
+            total += 16
         self.total = max(total, 16)
         self.buf = torch.zeros(self.total, dtype=torch.uint8, device=self.device)
         views = []
@@ -121,6 +132,11 @@ class StaticBatch:
             self.weights = self.buf[self.w_off:self.w_off + 4 * plan.n_nodes].view(torch.float32)
             self.norm = self.buf[self.norm_off:self.norm_off + 4].view(torch.float32)
         self.batch = TowerBatch.from_plan(plan, self.device, dev_arrays=views)
+        self.tower_offsets = self.norm_t = None
+        if self.towers:
+            self.tower_offsets = self.buf[self.off_off:self.off_off + 4 * (plan.n_towers + 1)].view(torch.int32)
+            self.norm_t = self.buf[self.norm_t_off:self.norm_t_off + 4].view(torch.float32)
+            object.__setattr__(self.batch, "_tower_offsets", self.tower_offsets)   # TowerBatch.tower_offsets' cache
         self.ring = [torch.zeros(self.total, dtype=torch.uint8, pin_memory=True) for _ in range(self.SLOTS)]
         self.ring_dev = [_mapped_device_ptr(r) for r in self.ring]
         self.loads = 0
@@ -148,6 +164,11 @@ class StaticBatch:
             hv[self.norm_off:self.norm_off + 4] = norm.view(np.uint8)
         elif weights is not None:
             raise ValueError("weights need a StaticBatch built with weighted=True")
+        if self.towers:
+            tn = np.asarray(plan.tower_nodes, np.int64)
+            off = np.concatenate([[0], np.cumsum(tn)]).astype(np.int32)
+            hv[self.off_off:self.off_off + off.nbytes] = off.view(np.uint8)
+            hv[self.norm_t_off:self.norm_t_off + 4] = np.array([max(int((tn > 0).sum()), 1)], np.float32).view(np.uint8)
         self.loads += 1
         # host-side copies the wrappers keep for reporting (edge ids, counts) follow the new batch
         b = self.batch
@@ -206,7 +227,9 @@ class ReplayStep:
     `body(batch, target, ws, bce, z, dz)` issues the step's launches on the current stream; it is
     run eagerly on the first call (a real step) and captured right after, then replayed. A `weighted`
     step uploads per-node loss weights and their divisor with the batch and passes them (views of the
-    static buffer) as `weights=` and `norm=` to a body whose signature names them.
+    static buffer) as `weights=` and `norm=` to a body whose signature names them. A body that walks the
+    towers (its attribute `needs_towers`, set by `step_body` for the tower-level loss) gets the plan's tower
+    offsets uploaded too — `batch.tower_offsets` — and their divisor as `norm_t=`.
 
     The batch upload is part of the step: its first kernel copies a pinned staging slot into the
     static device buffer (StaticBatch.copy_in). Two slots, one graph each: step i reads slot i mod 2,
@@ -216,7 +239,7 @@ class ReplayStep:
     profiles/r04_fit_step_gaps.txt)."""
 
     def __init__(self, plan: HostPlan, device, body: Callable, graph: bool = True, weighted: bool = False):
-        self.static = StaticBatch(plan, device, weighted=weighted)
+        self.static = StaticBatch(plan, device, weighted=weighted, towers=bool(getattr(body, "needs_towers", False)))
         self.device = self.static.device
         self.ws = E.Workspace(self.device)
         self.bce = E.BceScratch(self.device)
@@ -242,6 +265,8 @@ class ReplayStep:
     def _issue(self, k: int):
         st = self.static
         kw = {"weights": st.weights, "norm": st.norm} if st.weighted else {}
+        if st.towers:
+            kw["norm_t"] = st.norm_t
         if self.fold:   # the body's forward runs the upload in its first launch (spwgnn_run.prologue)
             pre = E.Prologue(dst=st.buf, src_dev_ptr=st.ring_dev[k], nbytes=st.total)
             self.body(st.batch, st.target, self.ws, self.bce, self.z, self.dz, pre=pre, **kw)
@@ -306,7 +331,9 @@ def step_body(params, grads, m, v, path, adam, counters: DeviceCounters, make_ru
     path = path.for_replay()
     tot, tot_s, w3s = sums if sums is not None else (None, None, None)
 
-    def body(batch, target, ws, bce, z, dz, pre=None, weights=None, norm=None):
+    tower_kw = bool(getattr(path, "needs_towers", False))
+
+    def body(batch, target, ws, bce, z, dz, pre=None, weights=None, norm=None, norm_t=None):
         # the key/step advance (and the replayed batch upload, `pre`) ride in the forward's first launch
         pro = None
         if E.FOLD_PROLOGUE:
@@ -318,10 +345,12 @@ def step_body(params, grads, m, v, path, adam, counters: DeviceCounters, make_ru
         logits = path.forward(params, batch, run, ws, z)
         # weights / norm: a weighted step's per-node loss weights and their divisor, views of its static buffer
         path.loss_backward(params, batch, run, ws, logits, target, bce, dz, grads, tot,
-                           w3s[batch.n_towers] if w3s is not None else None, tot_s, weights, norm)
+                           w3s[batch.n_towers] if w3s is not None else None, tot_s, weights, norm,
+                           **({"norm_t": norm_t} if tower_kw else {}))   # a tower-walking path: the uploaded divisor
         if grad_scale != 1.0:
             grads.mul_(grad_scale)
         adam.update_dev(params, grads, m, v, counters, adam.totals)   # the epoch's clip sums ride in the update
+    body.needs_towers = tower_kw   # ReplayStep then uploads the plan's tower offsets and their divisor
     return body
 
 

@@ -18,6 +18,13 @@ Optional (asked for only by the feature that needs it):
   early_event() -> event                                               the overlapped two-piece all-reduce
   set_step_loss_weights(weights, mp_steps)                             step_loss_weights
   eval_metrics(logits, target, tables, batch, weights, threshold)      evaluate
+  loss_tower(logits, target, batch, tower_targets, weights, norm, norm_t, tower_loss, node_loss, want_dlogits=True)
+      -> (out6, dlogits)                                               Trainer(tower_loss=): step, evaluate
+      out6 = [L_node, node correct, node count, L_tower, towers correct, towers counted]; target may be None
+      (node_loss 0), tower_targets None (derived), weights / norm None (unweighted). norm is the micro-batch's own
+      node divisor (node_loss arrives scaled by its share of the global batch), norm_t the GLOBAL tower divisor;
+      dlogits is the gradient of node_loss·L_node + tower_loss·L_tower with them, summed over ranks with weight 1
+      (None with want_dlogits False: evaluate, which passes the micro-batch's own tower count as norm_t)
 """
 from __future__ import annotations
 
@@ -108,8 +115,57 @@ class DeepLossPath(LossPath):
         return logits[self.mp_steps - 1]
 
 
-def loss_path(device, mp_steps: int, step_loss_weights=None) -> LossPath:
+class TowerLossPath(LossPath):
+    """The tower-level loss: L = node_loss·L_node + tower_loss·L_tower from one launch of its
+    own (`engine.bce_tower`, two past 256 nodes or towers) in place of `bce`, then the plain `backward` — the
+    backward is linear in dlogits, so nothing else changes. The loss needs the batch (its tower offsets):
+    `loss` and `loss_backward` take it, with the tower targets and the tower divisor, as keyword arguments.
+    `tower.out6` holds the last loss's six parts; with ``totals`` every loss launch also adds out6·weights6
+    to `tower.total6` (fit's epoch sums; the caller sets weights6)."""
+
+    needs_towers = True   # a replayed step uploads the plan's tower offsets and their divisor (replay.StaticBatch)
+
+    def __init__(self, device, mp_steps: int, tower_loss: float, node_loss: float = 1.0, totals: bool = False):
+        super().__init__(device, mp_steps)
+        self.mu, self.alpha = E.check_tower_loss(tower_loss, node_loss)
+        if not self.mu > 0:
+            raise ValueError("a TowerLossPath needs tower_loss > 0")
+        self.tower = E.TowerLossScratch(self.device, totals=totals)
+
+    def loss(self, logits, target, total3=None, weights3=None, total3s=None, node_weights=None, norm=None, *,
+             batch=None, tower_targets=None, norm_t=None, node_loss=None, dlogits=None, want_dlogits=True):
+        """(out3, dlogits) with out3 = [L, node correct, node count]. ``batch`` is required. ``node_loss``
+        overrides the path's (0 for tower-only labels: `target` may then be None)."""
+        if batch is None:
+            raise ValueError("the tower loss needs batch= (its tower offsets)")
+        if total3 is not None or total3s is not None:
+            raise ValueError("the tower loss keeps its epoch sums in tower.total6")
+        t = self.tower
+        return E.bce_tower(logits, target, batch, t, self.mu, self.alpha if node_loss is None else node_loss,
+                           tower_targets=tower_targets, norm_t=norm_t, dlogits=dlogits, node_weights=node_weights,
+                           norm=norm, total6=t.total6, weights6=t.weights6, want_dlogits=want_dlogits)
+
+    def loss_backward(self, params, batch, run, ws, logits, target, scratch, dlogits, grads, total3=None,
+                      weights3=None, total3s=None, node_weights=None, norm=None, *, tower_targets=None, norm_t=None,
+                      node_loss=None):
+        """The loss launch followed by `engine.backward`. A replayed step derives its tower targets from the node
+        targets; its tower offsets and its divisor (`norm_t`, a device float) come with the batch upload, since
+        plans of one geometry may cut their nodes into different towers. total3 / weights3 of the plain paths
+        are not taken (tower.total6 holds the sums)."""
+        _, dz = self.loss(logits, target, node_weights=node_weights, norm=norm, batch=batch,
+                          tower_targets=tower_targets, norm_t=norm_t, node_loss=node_loss, dlogits=dlogits)
+        E.backward(params, batch, run, ws, dz, grads=grads)
+
+
+def loss_path(device, mp_steps: int, step_loss_weights=None, *, tower_loss: float = 0.0, node_loss: float = 1.0,
+              totals: bool = False) -> LossPath:
     """The loss path of a front end: chosen here, once, not per step."""
+    mu, alpha = E.check_tower_loss(tower_loss, node_loss)
+    if mu > 0:
+        if step_loss_weights is not None:
+            raise ValueError("tower_loss and step_loss_weights do not combine (the tower term on per-step rows "
+                             "is not built)")
+        return TowerLossPath(device, mp_steps, mu, alpha, totals=totals)
     if step_loss_weights is None:
         return LossPath(device, mp_steps)
     return DeepLossPath(device, mp_steps, step_loss_weights)

@@ -73,6 +73,19 @@ class HipEngine:
     def set_step_loss_weights(self, lam, mp_steps: int):
         self.path = loss_path(self.device, mp_steps, lam)
 
+    def set_tower_loss(self, tower_loss: float, node_loss: float, mp_steps: int):
+        """The tower-level loss (step.TowerLossPath) as this engine's path: replayed steps run it too."""
+        self.path = loss_path(self.device, mp_steps, None, tower_loss=tower_loss, node_loss=node_loss)
+
+    def loss_tower(self, logits, target, batch, tower_targets, weights, norm, norm_t, tower_loss, node_loss,
+                   want_dlogits: bool = True):
+        """(out6, dlogits) of engine.bce_tower with the step's coefficients and divisors; out6 is one
+        persistent tensor the next call reuses. `want_dlogits` False (evaluate): the loss only, dlogits None."""
+        t = self.path.tower
+        _, dz = E.bce_tower(logits, target, batch, t, tower_loss, node_loss, tower_targets=tower_targets, norm_t=norm_t,
+                            node_weights=weights, norm=norm, want_dlogits=want_dlogits)
+        return t.out6, dz
+
     step_loss_weights = property(lambda self: self.path.lam)
     bce_scratch = property(lambda self: self.path.scratch)
     out3s = property(lambda self: self.path.out3s)   # the last loss's per-step [loss, correct, n] (device, (mp_steps, 3))
@@ -144,7 +157,11 @@ class Trainer:
                  dropout: float = E.REF_DROPOUT, seed: int = 0, lr: float = 5e-4, beta1: float = 0.9,
                  beta2: float = 0.999, eps: float = 1e-7, l2: float = 0.0, group=None, math: str = "x6",
                  buckets: int = 1, overlap: bool = True, clipnorm: float = 0.0, clipvalue: float = 0.0,
-                 decay: float = 0.0, skip_nonfinite: bool = False, step_loss_weights=None):
+                 decay: float = 0.0, skip_nonfinite: bool = False, step_loss_weights=None, tower_loss: float = 0.0,
+                 node_loss: float = 1.0):
+        # tower_loss (mu > 0): the objective is node_loss·L_node + tower_loss·L_tower, L_tower the tower-level
+        # BCE of engine.bce_tower; `step` then takes tower_targets= and sets `loss_parts`.
+        # 0: exactly the steps of before (node_loss is then not read).
         # step_loss_weights (None, or mp_steps floats >= 0, not all zero): deep supervision — the loss is
         # Σ_s λ_s·BCE(z_s, y) over every propagation step's logits instead of the last step's BCE; `step`
         # then returns [that sum, the last step's correct count, n]. None: exactly the steps of before.
@@ -165,6 +182,18 @@ class Trainer:
                 raise ValueError("step_loss_weights needs an engine with set_step_loss_weights(weights, mp_steps) "
                                  "(the engine protocol: spwgnn_amd/step.py)")
             self.engine.set_step_loss_weights(self.step_loss_weights, mp_steps)
+        self.tower_loss, self.node_loss = E.check_tower_loss(tower_loss, node_loss)
+        self.loss_parts = None    # the last tower-loss step's six numbers for this rank's shard (device, fp32)
+        if self.tower_loss > 0:
+            if self.step_loss_weights is not None:
+                raise ValueError("tower_loss and step_loss_weights do not combine (the tower term on per-step rows "
+                                 "is not built)")
+            if not hasattr(self.engine, "loss_tower"):
+                raise ValueError("tower_loss needs an engine with loss_tower(logits, target, batch, tower_targets, "
+                                 "weights, norm, norm_t, tower_loss, node_loss) (the engine protocol: "
+                                 "spwgnn_amd/step.py)")
+            if hasattr(self.engine, "set_tower_loss"):
+                self.engine.set_tower_loss(self.tower_loss, self.node_loss, mp_steps)
         self.clip_stats = None    # the last clipped step's [norm, scale, skipped, clipped] (device tensor)
         self.m = torch.zeros_like(params)
         self.v = torch.zeros_like(params)
@@ -255,6 +284,10 @@ class Trainer:
         self._sync_counters()
         if weighted and n_global not in (None, n_nodes):
             raise ValueError("weighted replayed steps cover the whole batch (no n_global)")
+        if self.tower_loss > 0 and (weighted or n_global not in (None, n_nodes)):
+            # the tower divisor of a weighted step is a per-step count, and a shard's needs the global one
+            raise ValueError("replayed tower-loss steps are unweighted whole-batch steps with derived tower targets; "
+                             "use step() otherwise")
         E.check_clip_options(self.clipnorm, self.clipvalue, self.decay)
         if self.opt.clip_on():
             self.clip_stats = self.opt.clip_scratch().out4
@@ -370,7 +403,7 @@ class Trainer:
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
         return t
 
-    def evaluate(self, batches, targets, weights=None, threshold: float = 0.5) -> dict:
+    def evaluate(self, batches, targets, weights=None, threshold: float = 0.5, *, tower_targets=None) -> dict:
         """The model's metrics over the GLOBAL evaluation set, of which `batches` / `targets` (one or a list:
         micro-batches) are this rank's shard: an inference run (no dropout, nothing stored, no step taken)
         whose integer tables (engine.EvalTables) are filled on the device and summed over the ranks with one
@@ -382,9 +415,20 @@ class Trainer:
         of every count. `threshold`: a node is predicted stable when its probability exceeds it. With
         step_loss_weights the engine's (mp_steps, n) rows are all scored: the dict describes the last step,
         ``loss`` is Σ_s λ_s·loss_s and ``steps`` lists every step's summary. The engine needs
-        `eval_metrics(logits, target, tables, batch, weights, threshold)`."""
+        `eval_metrics(logits, target, tables, batch, weights, threshold)`.
+
+        With tower_loss > 0 the loss launch is the tower loss's (no gradient written): ``loss`` is
+        node_loss·L_node + tower_loss·L_tower over the global set, and the dict gains ``tower_loss`` (L_tower, the
+        mean over the counted towers) and ``tower_accuracy`` (at 0.5, against `tower_targets` — one tensor per
+        micro-batch, plan order — or the derived labels; it replaces the table's, which is the derived one at
+        `threshold`). A `targets` entry of None (tower-only labels) drops that micro-batch's node term and, as
+        the tables need node targets, the summary: the dict then holds the three loss entries only."""
         from . import metrics as M
         batches, targets, weights = _micro_batches(batches, targets, weights)
+        if self.tower_loss > 0:
+            return self._evaluate_tower(batches, targets, weights, E.check_threshold(threshold), tower_targets)
+        if tower_targets is not None:
+            raise ValueError("tower_targets need Trainer(tower_loss > 0)")
         if not hasattr(self.engine, "eval_metrics"):
             raise ValueError("evaluate needs an engine with eval_metrics(logits, target, tables, batch, weights, threshold) "
                              "(the engine protocol: spwgnn_amd/step.py)")
@@ -413,7 +457,115 @@ class Trainer:
             out["steps"] = [M.summarize(counts, row=s) for s in range(rows)]
         return out
 
-    def step(self, batch, target, n_global: Optional[int] = None, weights=None, norm_global: Optional[int] = None):
+    def _evaluate_tower(self, batches, targets, weights, tau, tower_targets) -> dict:
+        """`evaluate` of a tower-loss trainer: per micro-batch the inference forward, the tower loss with the
+        micro-batch's own divisors (no dlogits) and the metrics launch; Σ L_node_i·k_i, Σ L_tower_i·t_i and the
+        counts are summed over the ranks with the tables."""
+        from . import metrics as M
+        tower_targets = self._tower_lists(batches, tower_targets)
+        if not hasattr(self.engine, "eval_metrics"):
+            raise ValueError("evaluate needs an engine with eval_metrics(logits, target, tables, batch, weights, threshold) "
+                             "(the engine protocol: spwgnn_amd/step.py)")
+        run = E.RunConfig(self.mp_steps, training=False, dropout=0.0, math=self.math)
+        tables = E.EvalTables(self.params.device)
+        sums = torch.zeros(7, dtype=torch.float64, device=self.params.device)   # the six parts' sums, micro-batches without node targets
+        for i, (b, tg) in enumerate(zip(batches, targets)):
+            wt = None if weights is None else weights[i]
+            k, t = (b.n_nodes, E.counted_towers(b)) if wt is None else E.counted_nodes_towers(b, torch.as_tensor(wt))
+            z = self.engine.forward(self.params, b, run)
+            out6, _ = self.engine.loss_tower(z, tg, b, None if tower_targets is None else tower_targets[i], wt,
+                                             None if wt is None else max(k, 1), max(t, 1), self.tower_loss,
+                                             self.node_loss if tg is not None else 0.0, want_dlogits=False)
+            sums[:6] += out6.to(sums) * self._weights6(k, max(t, 1), out6).to(sums)
+            if tg is None:
+                sums[6] += 1.0
+            else:
+                self.engine.eval_metrics(z, tg, tables, b, wt, tau)
+        self._sum_ranks(tables.flat)
+        self._sum_ranks(sums)
+        lp = self._tower_parts(sums[:6]).tolist()
+        out = dict(M.summarize(tables.cpu())) if sums[6].item() == 0 else {}
+        out.update(loss=self.node_loss * lp[0] + self.tower_loss * lp[3], tower_loss=lp[3],
+                   tower_accuracy=lp[4] / lp[5] if lp[5] else float("nan"))
+        return out
+
+    def _accumulate_and_update(self, batches, loss_of):
+        """The micro-batch loop of `step`: forward, `loss_of(i, logits, batch) -> (dlogits, gradient weight)`,
+        backward, the weighted gradient sum (the last one in two pieces when overlapped), the all-reduce and
+        the Adam update."""
+        single = len(batches) == 1
+        acc = None
+        for i, b in enumerate(batches):
+            run = self.run_config(micro=i)
+            z = self.engine.forward(self.params, b, run)
+            dz, w = loss_of(i, z, b)
+            ev = self._early(run) if i == len(batches) - 1 else None
+            g = self.engine.backward(self.params, b, run, dz)
+            if acc is None:
+                # one batch: the engine's own buffer (HipEngine.grads), scaled in place; micro-batches: the
+                # engine writes every backward into that buffer, so the sum lives in the Trainer's accumulator
+                acc = g if single else self._accumulator(g)
+            if ev is not None:   # the last micro-batch: accumulate and reduce in two pieces
+                self.reduce_split(acc, g, w, i == 0, ev)
+            else:
+                self._combine(acc, g, w, None, i == 0)
+        if self.distributed and not self._split():   # any process group (one rank: the identity, through the collective)
+            self.allreduce(acc)
+        self.iterations += 1
+        self._adam(acc)
+
+    def _tower_lists(self, batches, tower_targets):
+        if tower_targets is not None:
+            tower_targets = tower_targets if isinstance(tower_targets, (list, tuple)) else [tower_targets]
+            if len(tower_targets) != len(batches):
+                raise ValueError("one tower target tensor per micro-batch")
+        return tower_targets
+
+    def _tower_parts(self, parts):
+        """The shard's six numbers from Σ L_node_i·k_i, Σ L_tower_i·(its divisor) and the counts (fp64)."""
+        return torch.stack([parts[0] / parts[2].clamp(min=1.0), parts[1], parts[2],
+                            parts[3] / parts[5].clamp(min=1.0), parts[4], parts[5]])
+
+    def _tower_out3(self, lp):
+        """[node_loss·L_node + tower_loss·L_tower, node correct, node count] in fp64 with the coefficients as the
+        fp32 values the loss launch takes: for one whole batch the bits of its own out3."""
+        lp = lp.double()
+        a, m = (float(torch.tensor(c, dtype=torch.float32)) for c in (self.node_loss, self.tower_loss))
+        return torch.stack([a * lp[0] + m * lp[3], lp[1], lp[2]]).float()
+
+    def _step_tower(self, batches, targets, weights, counts, towers, total, tower_targets, towers_global):
+        """`step` with the tower term (tower_loss > 0). The node term of micro-batch i keeps its own divisor
+        k_i and enters with node_loss·k_i / total, as its gradient does without the tower term; tower counts
+        do not scale with node counts for ragged towers, so the tower term takes the GLOBAL divisor — the
+        counted towers of the whole batch, `towers_global` or all-reduced — inside the loss, and the
+        gradients are summed with weight 1."""
+        tower_targets = self._tower_lists(batches, tower_targets)
+        t_total = max(int(towers_global if towers_global is not None else self._count_global(sum(towers))), 1)
+        whole = len(batches) == 1 and self.world == 1 and towers_global is None
+        acc = [None]
+
+        def loss_of(i, z, b):
+            tg, k = targets[i], counts[i]
+            alpha = self.node_loss * (k / total) if tg is not None else 0.0
+            out6, dz = self.engine.loss_tower(z, tg, b, None if tower_targets is None else tower_targets[i],
+                                              None if weights is None else weights[i],
+                                              None if weights is None else max(k, 1), t_total, self.tower_loss, alpha)
+            # the engine's out6 is one persistent tensor: Σ L_node_i·k_i, Σ L_tower_i·t_total and the counts, in fp64
+            # (one batch that is the whole global batch: out6 itself — k / k and t_total / t_total change nothing)
+            if whole:
+                acc[0] = out6.clone()
+            else:
+                p = out6.double() * self._weights6(k, t_total, out6)
+                acc[0] = p if acc[0] is None else acc[0] + p
+            return dz, 1.0
+
+        self._accumulate_and_update(batches, loss_of)
+        lp = acc[0] if whole else self._tower_parts(acc[0])
+        self.loss_parts = lp.float()
+        return self._tower_out3(lp)
+
+    def step(self, batch, target, n_global: Optional[int] = None, weights=None, norm_global: Optional[int] = None, *,
+             tower_targets=None, towers_global: Optional[int] = None):
         """One optimizer step. `batch`/`target` may be lists (micro-batches of this rank's shard);
         `n_global` = nodes in the whole global batch (all ranks, all micro-batches). Returns one
         [loss, correct, n] device tensor for this rank's shard: the node-weighted mean BCE over its
@@ -424,8 +576,18 @@ class Trainer:
         w ≠ 0 in the whole global batch (all-reduced when None, as n_global is; at least 1). Zero
         weights mask their nodes. Counting each micro-batch's non-zero weights is one host sync. The
         result is then [loss over this rank's counted nodes, correct among them, their number]. The
-        engine needs `loss_weighted(logits, target, weights, norm)`."""
+        engine needs `loss_weighted(logits, target, weights, norm)`.
+
+        With tower_loss > 0 the objective is node_loss·L_node + tower_loss·L_tower.
+        `tower_targets`: one (n_towers,) 0/1 tensor per micro-batch in the plan's tower order, or None = a
+        tower's label is "every counted node target is 1". A `target` of None (tower-only labels) drops the
+        node term of that micro-batch. `towers_global`: the counted towers of the whole global batch
+        (all-reduced when None). The result is [node_loss·L_node + tower_loss·L_tower, node correct, node
+        count] of this rank's shard, and `loss_parts` holds its [L_node, node correct, node count, L_tower,
+        towers correct, towers counted]. The engine needs `loss_tower` (spwgnn_amd/step.py)."""
         batches, targets, weights = _micro_batches(batch, target, weights)
+        if self.tower_loss <= 0 and (tower_targets is not None or towers_global is not None):
+            raise ValueError("tower_targets / towers_global need Trainer(tower_loss > 0)")
         # micro-batch i counts k_i nodes — all of them, or those with w ≠ 0 — of `total` in the global batch:
         # its loss is the mean over its k_i, its gradient enters the sum scaled by k_i / total
         if weights is None:
@@ -434,13 +596,21 @@ class Trainer:
             counts = [b.n_nodes for b in batches]
             total = n_global if n_global is not None else self._count_global(sum(counts))
         else:
-            counts = [_nonzero(w) for w in weights]
+            if self.tower_loss > 0:   # both counts of every micro-batch in one host sync each
+                both = [E.counted_nodes_towers(bt, torch.as_tensor(w)) for bt, w in zip(batches, weights)]
+                counts, towers = [c[0] for c in both], [c[1] for c in both]
+            else:
+                counts = [_nonzero(w) for w in weights]
             total = max(int(norm_global if norm_global is not None else self._count_global(sum(counts))), 1)
+        if self.tower_loss > 0:
+            if weights is None:
+                towers = [E.counted_towers(bt) for bt in batches]
+            return self._step_tower(batches, targets, weights, counts, towers, total, tower_targets, towers_global)
         single = len(batches) == 1
-        acc = tot3 = None
-        for i, (b, tg, k) in enumerate(zip(batches, targets, counts)):
-            run = self.run_config(micro=i)
-            z = self.engine.forward(self.params, b, run)
+        keep = {}
+
+        def loss_of(i, z, b):
+            tg, k = targets[i], counts[i]
             if weights is None:
                 out3, dz = self.engine.loss(z, tg)
             else:
@@ -448,27 +618,18 @@ class Trainer:
             # the engine's out3 is one persistent tensor: kept before the next call reuses it — one batch's as
             # the engine computed it (one copy), micro-batches' as Σ loss_i·k_i, Σ correct_i, Σ n_i in fp64
             if single and weights is None:
-                res = out3.clone()
+                keep["res"] = out3.clone()
             else:
                 w3 = out3.double() * self._weights3(k, out3)
-                tot3 = w3 if tot3 is None else tot3 + w3
-            ev = self._early(run) if i == len(batches) - 1 else None
-            g = self.engine.backward(self.params, b, run, dz)
-            if acc is None:
-                # one batch: the engine's own buffer (HipEngine.grads), scaled in place; micro-batches: the
-                # engine writes every backward into that buffer, so the sum lives in the Trainer's accumulator
-                acc = g if single else self._accumulator(g)
-            if ev is not None:   # the last micro-batch: accumulate and reduce in two pieces
-                self.reduce_split(acc, g, k / total, i == 0, ev)
-            else:
-                self._combine(acc, g, k / total, None, i == 0)
-        if self.distributed and not self._split():   # any process group (one rank: the identity, through the collective)
-            self.allreduce(acc)
-        self.iterations += 1
-        self._adam(acc)
-        if tot3 is None:
+                keep["tot3"] = w3 if "tot3" not in keep else keep["tot3"] + w3
+            return dz, k / total
+
+        self._accumulate_and_update(batches, loss_of)
+        if "tot3" not in keep:
+            res = keep["res"]
             return res.float() if res.dtype != torch.float32 else res
         # mean loss over this rank's counted nodes, total correct, total counted (device, fp32)
+        tot3 = keep["tot3"]
         n = tot3[2] if weights is None else tot3[2].clamp(min=1.0)
         return torch.stack([tot3[0] / n, tot3[1], tot3[2]]).float()
 
@@ -478,6 +639,17 @@ class Trainer:
         wt = self._w3.pop(key, None)
         if wt is None:
             wt = out3.new_tensor([float(k), 1.0, 1.0], dtype=torch.float64)
+        self._w3[key] = wt
+        while len(self._w3) > 16:
+            self._w3.pop(next(iter(self._w3)))
+        return wt
+
+    def _weights6(self, k: int, towers: int, out6: torch.Tensor) -> torch.Tensor:
+        """The cached fp64 [k, 1, 1, towers, 1, 1] on out6's device (`_weights3`'s cache and its bound)."""
+        key = (k, towers, out6.device)
+        wt = self._w3.pop(key, None)
+        if wt is None:
+            wt = out6.new_tensor([float(k), 1.0, 1.0, float(towers), 1.0, 1.0], dtype=torch.float64)
         self._w3[key] = wt
         while len(self._w3) > 16:
             self._w3.pop(next(iter(self._w3)))
