@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense; spwgnn_clip, spwgnn_adam_clipped, spwgnn_adam_clipped_dev, spwgnn_adam_lr_decayed, spwgnn_adam_lr_table_decay; spwgnn_forward_steps, spwgnn_backward_steps, spwgnn_step_weights, spwgnn_bce_steps; spwgnn_eval, spwgnn_eval_metrics); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense; spwgnn_clip, spwgnn_adam_clipped, spwgnn_adam_clipped_dev, spwgnn_adam_lr_decayed, spwgnn_adam_lr_table_decay; spwgnn_forward_steps, spwgnn_backward_steps, spwgnn_step_weights, spwgnn_bce_steps; spwgnn_eval, spwgnn_eval_metrics; spwgnn_backward_relations); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
@@ -305,6 +305,7 @@ int32_t spwgnn_math_products_bwd(int32_t math);
 #define SPWGNN_K_INPUT_BWD 12  /* spwgnn_backward_inputs' one launch */
 #define SPWGNN_K_PLAN_DEVICE 13 /* spwgnn_plan_device_positions / _dense's one launch (spwgnn_plan_device.prof_events) */
 #define SPWGNN_K_STATE 14      /* the layout launch of spwgnn_forward_state (P_S out) / spwgnn_backward_state (dstate in) */
+#define SPWGNN_K_REL_BWD 15    /* spwgnn_backward_relations' one launch */
 
 /* Workspace bytes for (n_nodes, n_eblocks, mp_steps, training). */
 int64_t spwgnn_workspace_bytes(int32_t n_nodes, int32_t n_eblocks, int32_t mp_steps, int32_t training);
@@ -391,6 +392,33 @@ int32_t spwgnn_backward_state(const float* params, const spwgnn_batch* batch, co
  * (the same bits on every run). `params` is the flat buffer the forward ran with. */
 int32_t spwgnn_backward_inputs(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
                                void* workspace, int64_t workspace_bytes, float* dpos, spwgnn_stream_t stream);
+
+/* Relation gradients (added within ABI 8: a new symbol only, no existing struct or signature changed;
+ * DESIGN.md §3zy): which contact a prediction rests on. Put a scalar gate w_k on every active edge
+ * k = (src_k → dst_k) in the receiver sum of Networks.py:88 ALONE,
+ *   eff_{i,s} = tanh(Σ_{k: dst_k = i} w_k · e_{k,s}),   e_{k,s} = the edge propagator's output at step s,
+ * and take the gradient at w ≡ 1 (the forward is never gated):
+ *   r_{k,s} = ⟨g_s[dst_k], e_{k,s}⟩ = ⟨G3_s[dst_k], h2_{k,s}⟩ + ⟨g_s[dst_k], b3⟩,   r_k = Σ_s r_{k,s},
+ * g_s = d loss / d (pre-tanh receiver sum of step s), G3_s = g_s·W3ᵀ, h2 = relu(relu(A + U_s[src] +
+ * V_s[dst])·W2 + b2). In reference terms r_k is d loss / d receiver_relations[b, dst_k, k] through line 88
+ * alone: NOT through the gathers of Networks.py:33 and :85, which read the same tensors. (A forward that
+ * is gated — soft relations, DropEdge — is not built; this is its backward at the all-ones gate.)
+ * Of the last spwgnn_backward / _state / _steps / spwgnn_bce_backward* on this workspace (same batch, same
+ * run; before the next forward on it). One launch (kernel id SPWGNN_K_REL_BWD) that rebuilds h2 per
+ * (32-edge block, step) from the stored rows on the run's backward product class (X6 and H3: six bf16
+ * products, X3: three, BF16: one, F32: the f32 matrix instructions) and sums the steps per edge in step
+ * order: no atomics, the same bits on every run.
+ * drel [32·n_eblocks] device fp32 in the plan's edge-slot order (edge_src / edge_dst's): every slot is
+ * written, a padding slot (edge_src < 0 or edge_dst < 0) with 0; drel_steps (NULL = none) [mp_steps]
+ * [32·n_eblocks] holds r_{k,s} the same way. The workspace is only read: the gradients the backward
+ * returned, spwgnn_backward_inputs and a second call of this one work before or after it. `params` is the
+ * flat buffer the forward ran with. Ordinary, capacity-padded and receiver-block plans alike.
+ * SPWGNN_E_ARG (a null params or drel), SPWGNN_E_NOTRAIN, SPWGNN_E_WORKSPACE before any device work. */
+int32_t spwgnn_backward_relations(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                                  void* workspace, int64_t workspace_bytes,
+                                  float* drel       /* [32·n_eblocks] plan edge-slot order */,
+                                  float* drel_steps /* [mp_steps][32·n_eblocks], or NULL */,
+                                  spwgnn_stream_t stream);
 
 /* Keras binary_crossentropy on sigmoid(logits) (Networks.py:102), mean over n:
  * out3 = {loss, sum of correct (binary_accuracy numerator), n}; dlogits = dloss/dlogit.

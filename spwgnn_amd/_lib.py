@@ -101,6 +101,7 @@ class TowerLossC(C.Structure):
 
 K_EDGE_FWD, K_NODE_FWD, K_EDGE_BWD, K_NODE_BWD, K_ENC_EDGE, K_ENC_EDGE_BWD, K_WGRAD_W2, K_DA = 1, 2, 3, 4, 5, 6, 7, 8
 K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD, K_INPUT_BWD, K_PLAN_DEVICE, K_STATE = 9, 10, 11, 12, 13, 14
+K_REL_BWD = 15
 MATH_F32, MATH_X6, MATH_BF16, MATH_X3, MATH_H3 = 0, 1, 2, 3, 4
 E_ARG, E_WORKSPACE, E_NOTRAIN = -1, -4, -6   # SPWGNN_E_* statuses the bindings name
 E_SHAPE, E_RELATION, E_CAPACITY = -2, -3, -5
@@ -145,6 +146,7 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_bce_steps": (i32, [vp, vp, i64, i32, C.POINTER(StepWeightsC), C.POINTER(LossWeightsC), vp, vp, vp, vp,
                                    vp, vp, vp, vp]),
         "spwgnn_backward_inputs": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp]),
+        "spwgnn_backward_relations": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp]),
         "spwgnn_plan_device_positions": (i32, [C.POINTER(PlanDeviceC), vp, i32, f32, f32, vp]),
         "spwgnn_plan_device_dense": (i32, [C.POINTER(PlanDeviceC), vp, vp, i32, i32, vp]),
         "spwgnn_bce_scratch_bytes": (i64, [i64]),

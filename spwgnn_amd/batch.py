@@ -125,6 +125,10 @@ class HostPlan:
         return (self.n_towers, self.n_nodes, self.n_wtiles, self.n_eblocks, self.nw_max, self.has_prop, self.flags,
                 tuple(a.shape for a in self.arrays))
 
+    def edges_to_input(self, values, dense: bool = False):
+        """`TowerBatch.edges_to_input` of the batch this plan becomes (it reads the host fields they share)."""
+        return TowerBatch.edges_to_input(self, values, dense)
+
     @staticmethod
     def build(pos, tower_nodes, src, dst, tower_edges, prop=None, nw_max=None, node_shape=None, tower_ids=None,
               edge_cap=None, recv_blocks=None, pack: bool = False) -> "HostPlan":
@@ -278,6 +282,35 @@ class TowerBatch:
         if isinstance(x, torch.Tensor):
             return x[torch.as_tensor(order, device=x.device)]
         return np.asarray(x)[order]
+
+    def edges_to_input(self, values, dense: bool = False):
+        """Per-edge-slot results (`engine.backward_relations`: last axis = the plan's 32·n_eblocks edge
+        slots, numpy or torch, any leading axes such as the steps) → ``(src, dst, values)`` with the padding
+        slots dropped: edge j is the j-th active relation (the order of ``self.src`` / ``self.dst``:
+        tower-major, sender-major inside a tower), its node ids in the INPUT's node order (through
+        ``node_perm`` for packed plans), values[..., j] its value. With ``dense`` (towers of one size N
+        only) instead one (..., B, N, N) array indexed [tower, sender, receiver] in the input's tower
+        order, zero where there is no relation."""
+        eid = np.asarray(self.edge_id)
+        v = values.detach().cpu().numpy() if isinstance(values, torch.Tensor) else np.asarray(values)
+        if v.shape[-1] != len(eid):
+            raise ValueError(f"values must hold one entry per edge slot ({len(eid)}), got {v.shape}")
+        slots = np.nonzero(eid >= 0)[0]
+        slots = slots[np.argsort(eid[slots], kind="stable")]   # the slot of edge j
+        src, dst = np.asarray(self.src, np.int64), np.asarray(self.dst, np.int64)
+        if self.node_perm is not None:
+            perm = np.asarray(self.node_perm, np.int64)
+            src, dst = perm[src], perm[dst]
+        vals = v[..., slots]
+        if not dense:
+            return src, dst, vals
+        tn = np.asarray(self.tower_nodes)
+        if len(tn) == 0 or np.any(tn != tn[0]):
+            raise ValueError("the dense form needs towers of one size")
+        N = int(tn[0])
+        out = np.zeros(v.shape[:-1] + (len(tn), N, N), v.dtype)
+        out[..., src // N, src % N, dst % N] = vals
+        return out
 
     @property
     def n_edges(self) -> int:

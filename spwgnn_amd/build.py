@@ -19,7 +19,8 @@ if os.environ.get("SPWGNN_BUILD_OUT"):
     LIB = Path(os.environ["SPWGNN_BUILD_OUT"]).resolve()
     OBJDIR = HERE / "csrc" / ("build_" + LIB.stem)
 SOURCES = ["host.cpp", "api.hip", "path.hip", "forward.hip", "backward.hip", "kernels_fwd.hip", "kernels_bwd.hip",
-           "kernels_wgrad.hip", "kernels_loss.hip", "kernels_eval.hip", "kernels_team.hip", "kernels_input.hip", "kernels_plan.hip"]
+           "kernels_wgrad.hip", "kernels_loss.hip", "kernels_eval.hip", "kernels_team.hip", "kernels_input.hip", "kernels_plan.hip",
+           "kernels_rel.hip"]
 HEADERS = ["spwgnn_layout.h", "device_common.h", "gemm_blocks.h", "loss_blocks.h", "kernels.h", "weights.h", "workspace.h",
            "path.h", "run.h"]
 ARCH = os.environ.get("SPWGNN_ARCH", "gfx950")

@@ -159,6 +159,42 @@ int32_t spwgnn_backward_inputs(const float* params, const spwgnn_batch* batch, c
     return SPWGNN_OK;
 }
 
+// The rows k_rel_bwd reads are operands of the weight gradients, which every launch path (wide, receiver
+// blocks, team / fused, the loop-end shortcuts) runs over all S steps after the step loop: A, U_s, V_s,
+// G3_s of the W2 gradient (backward.hip wg_w2; U_0, V_0 unwritten under a null prop: uv_zero, as there) and
+// g_s of the rmp.2 gradient (wg_node, bf16 under Path::n16). No path leaves one out, so none is refused.
+int32_t spwgnn_backward_relations(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                                  int64_t workspace_bytes, float* drel, float* drel_steps, spwgnn_stream_t stream) {
+    Ws w;
+    if (int32_t stt = enter(batch, run, workspace, workspace_bytes, true, params && drel, w)) return stt;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const Ctx c{w, static_cast<char*>(workspace), false};
+    const ParamTable& pt = param_table();
+    const Path p = make_path(batch, run, w);
+    RelBwdArgs a{};
+    a.n_eblocks = batch->n_eblocks;
+    a.n_nodes = batch->n_nodes;
+    a.S = run->mp_steps;
+    a.uv_zero = !batch->prop;
+    a.step_e = w.RN * kRowE;
+    a.step_n = w.RN * kRowN;
+    a.esrc = batch->edge_src;
+    a.edst = batch->edge_dst;
+    a.A = c.f(w.A);
+    a.U = c.f(w.U);
+    a.V = c.f(w.V);
+    a.G3 = c.f(w.G3);
+    a.g = c.f(w.g);
+    a.w2 = params + pt.t[T_RMP1K].offset;
+    a.b2 = params + pt.t[T_RMP1B].offset;
+    a.b3 = params + pt.t[T_RMP2B].offset;
+    a.drel = drel;
+    a.drel_steps = drel_steps;
+    const Prof prof{run, st};
+    SPW_TIMED(prof, SPWGNN_K_REL_BWD, launch_rel_bwd(a, math_bwd(run->math), p.b16, p.n16, st));
+    return SPWGNN_OK;
+}
+
 // Argument checks of the device-plan calls (no device work): 0, or the status to return.
 static int32_t plan_device_check(const spwgnn_plan_device* p) {
     if (!p) return SPWGNN_E_ARG;

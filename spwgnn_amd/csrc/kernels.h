@@ -529,6 +529,20 @@ struct InputBwdArgs {
     int b16;
 };
 hipError_t launch_input_bwd(const InputBwdArgs& a, hipStream_t st);
+// k_rel_bwd (kernels_rel.hip): d/d(relation gate) per edge slot, from the rows the backward left
+struct RelBwdArgs {
+    int n_eblocks, n_nodes, S;
+    int uv_zero;                     // a null 'propagation': U_0 = V_0 = 0, step 0 does not read them (§3zh)
+    int64_t step_e, step_n;          // floats per step of a 152- / 104-feature node array (RN·kRowE, RN·kRowN)
+    const int32_t *esrc, *edst;      // [n_eblocks*32] global sender / receiver, -1 = padding
+    const float* A;                  // chunk-major edge rows (bf16 in that element order: Path::b16)
+    const float *U, *V, *G3, *g;     // step 0 of the chunk-major node rows (U, V, g bf16 under Path::n16; G3 fp32)
+    const float *w2, *b2, *b3;       // rmp.1.kernel [150][150], rmp.1.bias, rmp.2.bias in the flat parameters
+    float* drel;                     // [n_eblocks*32]
+    float* drel_steps;               // [S][n_eblocks*32], or null
+};
+// math: the backward's (math_bwd of the run's); b16 / n16: the run's storage (Path)
+hipError_t launch_rel_bwd(const RelBwdArgs& a, int math, bool b16, bool n16, hipStream_t st);
 // k_plan_device (kernels_plan.hip): the data-dependent arrays of a capacity plan, filled on the device
 struct PlanDevArgs {
     int n_wtiles, n_eblocks, n_nodes, n_towers;

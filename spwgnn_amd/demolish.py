@@ -89,6 +89,42 @@ def stability_gradients(net: Net, towers_raw: np.ndarray, mode: str = "sum_prob"
         return sums, (dobj / RELATION_THRESHOLD).reshape(C_, N, 3)
 
 
+def _readout_cotangent(z: torch.Tensor, mode: str, N: int) -> torch.Tensor:
+    """d readout / d logit of a `tower_readout` mode over towers of N boxes."""
+    if mode.endswith("prob"):
+        p = E.sigmoid(z)
+        dz = p * (1.0 - p)
+    else:
+        dz = torch.ones_like(z)
+    return dz / N if mode.startswith("mean") else dz
+
+
+def relation_gradients(net: Net, towers_raw: np.ndarray, mode: str = "sum_prob") -> Tuple[torch.Tensor, torch.Tensor]:
+    """`stability_sums` plus which contact each sum rests on: (sums (C,), rel (C, N, N)) with
+    rel[c, s, r] = the gradient of sums[c] with respect to a scalar gate on the relation s → r (sender,
+    receiver) of candidate c, in the receiver sum of Networks.py:88 alone and at the all-ones gate
+    (`engine.backward_relations`; the diagonal is zero). A large |rel[c, s, r]| says the
+    readout hangs on what box s tells box r; deleting that relation and re-running the forward is what it
+    replaces to first order. The forward is the one of `stability_gradients`: training mode with dropout
+    0 on fully connected towers, the same ``dz`` per readout mode."""
+    if mode not in E.READOUT_MODES:
+        raise ValueError(f"readout mode must be one of {sorted(E.READOUT_MODES)}")
+    g = _graph_net(net)
+    towers_raw = np.asarray(towers_raw, np.float64)
+    N = towers_raw.shape[1]
+    objects = (towers_raw / RELATION_THRESHOLD).astype(np.float32)
+    batch = TowerBatch.fully_connected(objects, device=g.device)
+    flat = g.flat.detach()
+    run = g.run_config(True, dropout=0.0)
+    ws = E.Workspace(g.device)
+    with torch.no_grad():
+        z = E.forward(flat, batch, run, ws)
+        sums = E.tower_readout(z, batch, mode)
+        E.backward(flat, batch, run, ws, _readout_cotangent(z, mode, N))
+        drel = E.backward_relations(flat, batch, run, ws)
+    return sums, torch.from_numpy(batch.edges_to_input(drel, dense=True)).to(g.device)
+
+
 def remove_to_demolish(net: Net, boxes_raw: np.ndarray) -> Tuple[np.ndarray, int]:
     """Batched `JengaBuilder.remove_to_demolish` decision: (box_stabilities (n,), remove_index)."""
     sums = stability_sums(net, removal_candidates(boxes_raw)).cpu().numpy().astype(np.float64)

@@ -427,6 +427,46 @@ def backward_inputs(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig
     return dpos[:, :3]
 
 
+def backward_relations(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
+                       drel: Optional[torch.Tensor] = None, per_step: bool = False,
+                       drel_steps: Optional[torch.Tensor] = None):
+    """d(loss)/d(relation gate) of the last `backward` / `bce_backward` on this workspace
+    (spwgnn_backward_relations): (32·n_eblocks,) fp32 in the plan's edge-slot order (``batch.edge_src`` /
+    ``edge_dst``'s; `TowerBatch.edges_to_input` maps it back), 0 in padding slots. Entry k is the gradient
+    of a scalar gate on edge k in the receiver sum of Networks.py:88 alone, taken at the all-ones gate — in
+    reference terms d loss / d receiver_relations[b, dst_k, k] through line 88, not through the gathers of
+    lines 33 and 85; the forward is never gated. One extra launch that only reads the workspace: the
+    gradients `backward` returned and `backward_inputs` are untouched, in either call order.
+    ``drel``: the buffer to write to. With ``per_step`` returns ``(drel, drel_steps)``, drel_steps
+    (mp_steps, 32·n_eblocks) holding each propagation step's share (their sum over steps is drel);
+    ``drel_steps``: the buffer for it (it implies ``per_step``)."""
+    per_step = per_step or drel_steps is not None
+    if not run.training:
+        _lib.check(_lib.E_NOTRAIN, "spwgnn_backward_relations")
+    if not ws.holds(batch, run) or ws.bwd_key != ws.fwd_key:
+        raise _lib.SpwgnnError("backward_relations needs the backward of the same batch and RunConfig on this "
+                               "workspace (it reads what that backward left there; a new forward discards it)")
+    _check_params(flat_params)
+    slots = 32 * batch.n_eblocks
+    if drel is None:
+        drel = _poison(torch.empty(slots, dtype=torch.float32, device=batch.device))
+    else:
+        _out_buffer(drel, (slots,), "drel")
+    steps = None
+    if drel_steps is not None:
+        steps = _out_buffer(drel_steps, (int(run.mp_steps), slots), "drel_steps")
+    elif per_step:
+        steps = _poison(torch.empty(int(run.mp_steps), slots, dtype=torch.float32, device=batch.device))
+    b = batch.cstruct()
+    r = run.cstruct()
+    buf = ws.buf
+    st = _lib.lib().spwgnn_backward_relations(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
+                                              drel.data_ptr(), steps.data_ptr() if per_step else None,
+                                              _stream(batch.device))
+    _lib.check(st, "spwgnn_backward_relations")
+    return (drel, steps) if per_step else drel
+
+
 def bce_backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace, logits: torch.Tensor,
                  targets: torch.Tensor, scratch: "BceScratch", dlogits: Optional[torch.Tensor] = None,
                  total3: Optional[torch.Tensor] = None, weights3: Optional[torch.Tensor] = None,

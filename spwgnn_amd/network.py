@@ -244,6 +244,51 @@ class GraphNetwork(nn.Module):
             return torch.sigmoid(z[0])[..., None], z[1]
         return torch.sigmoid(z)[..., None]
 
+    def relation_gradients(self, objects, sender_relations, receiver_relations, propagation=None, dlogits=None,
+                           loss=None) -> torch.Tensor:
+        """Which relation a prediction rests on: a tensor shaped like ``receiver_relations`` (B, N, E) that
+        holds r_k at [b, dst_k, k] for every active relation column k of tower b and zero elsewhere
+        (`engine.backward_relations`). r_k is the gradient of a scalar gate on relation k in
+        the receiver sum of Networks.py:88 ALONE, at the all-ones gate: d L / d receiver_relations[b, dst_k, k]
+        through line 88, not through the gathers of lines 33 and 85 that read the same tensors. The forward
+        is not gated (soft relations / DropEdge are not built).
+        L is Σ dlogits·z for a ``dlogits`` (B, N) tensor, or ``loss(z)`` for a callable taking the (B, N)
+        logits and returning a scalar (its d/dz by torch autograd), or — neither given — Σ sigmoid(z), the
+        stability readout. One training forward with dropout 0 (the inference values, activations kept),
+        one backward, one more launch. Inputs as `forward_logits` takes them (host plan)."""
+        if dlogits is not None and loss is not None:
+            raise ValueError("give dlogits or loss, not both")
+        to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        Rs, Rr = to_np(sender_relations), to_np(receiver_relations)
+        batch = self._dense_batch(objects, sender_relations, receiver_relations, None, "host")
+        if propagation is not None:
+            batch = batch.with_prop(torch.as_tensor(propagation, dtype=torch.float32, device=self.device)
+                                    .reshape(batch.n_nodes, 100))
+        B, N = batch.node_shape
+        flat = self.flat.detach()
+        run = self.run_config(True, dropout=0.0)
+        ws = E.Workspace(self.device)
+        with torch.no_grad():
+            z = E.forward(flat, batch, run, ws)
+        if dlogits is not None:
+            dz = torch.as_tensor(dlogits, dtype=torch.float32, device=self.device).reshape(-1)
+        else:
+            with torch.enable_grad():
+                zz = z.detach().reshape(B, N).requires_grad_(True)
+                L = torch.sigmoid(zz).sum() if loss is None else loss(zz)
+                (dz,) = torch.autograd.grad(L, zz)
+            dz = dz.reshape(-1)
+        with torch.no_grad():
+            E.backward(flat, batch, run, ws, dz.contiguous())
+            drel = E.backward_relations(flat, batch, run, ws)
+        dense = batch.edges_to_input(drel, dense=True)   # (B, N, N) [sender, receiver]
+        out = np.zeros(Rr.shape, np.float32)
+        for b in range(B):
+            cols = np.nonzero((Rr[b] != 0).any(0) & (Rs[b] != 0).any(0))[0]
+            s, r = Rs[b][:, cols].argmax(0), Rr[b][:, cols].argmax(0)
+            out[b, r, cols] = dense[b, s, r]
+        return torch.from_numpy(out).to(self.device)
+
     def forward_pooled(self, objects, sender_relations, receiver_relations, propagation=None,
                        mode: str = "mean_prob", plan: str = "host") -> torch.Tensor:
         """(B,) per-tower pooled output — the optional GlobalBlock-style readout (not in the
