@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense; spwgnn_clip, spwgnn_adam_clipped, spwgnn_adam_clipped_dev, spwgnn_adam_lr_decayed, spwgnn_adam_lr_table_decay; spwgnn_forward_steps, spwgnn_backward_steps, spwgnn_step_weights, spwgnn_bce_steps; spwgnn_eval, spwgnn_eval_metrics; spwgnn_backward_relations); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense; spwgnn_clip, spwgnn_adam_clipped, spwgnn_adam_clipped_dev, spwgnn_adam_lr_decayed, spwgnn_adam_lr_table_decay; spwgnn_forward_steps, spwgnn_backward_steps, spwgnn_step_weights, spwgnn_bce_steps; spwgnn_eval, spwgnn_eval_metrics; spwgnn_backward_relations; spwgnn_gates_supported, spwgnn_forward_gated, spwgnn_backward_gated); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
@@ -397,13 +397,13 @@ int32_t spwgnn_backward_inputs(const float* params, const spwgnn_batch* batch, c
  * DESIGN.md §3zy): which contact a prediction rests on. Put a scalar gate w_k on every active edge
  * k = (src_k → dst_k) in the receiver sum of Networks.py:88 ALONE,
  *   eff_{i,s} = tanh(Σ_{k: dst_k = i} w_k · e_{k,s}),   e_{k,s} = the edge propagator's output at step s,
- * and take the gradient at w ≡ 1 (the forward is never gated):
+ * and take the gradient at the run's gates (w ≡ 1 after an ungated forward; the gates of
+ * spwgnn_forward_gated / spwgnn_backward_gated after a gated one, below):
  *   r_{k,s} = ⟨g_s[dst_k], e_{k,s}⟩ = ⟨G3_s[dst_k], h2_{k,s}⟩ + ⟨g_s[dst_k], b3⟩,   r_k = Σ_s r_{k,s},
  * g_s = d loss / d (pre-tanh receiver sum of step s), G3_s = g_s·W3ᵀ, h2 = relu(relu(A + U_s[src] +
  * V_s[dst])·W2 + b2). In reference terms r_k is d loss / d receiver_relations[b, dst_k, k] through line 88
- * alone: NOT through the gathers of Networks.py:33 and :85, which read the same tensors. (A forward that
- * is gated — soft relations, DropEdge — is not built; this is its backward at the all-ones gate.)
- * Of the last spwgnn_backward / _state / _steps / spwgnn_bce_backward* on this workspace (same batch, same
+ * alone: NOT through the gathers of Networks.py:33 and :85, which read the same tensors.
+ * Of the last spwgnn_backward / _state / _gated / _steps / spwgnn_bce_backward* on this workspace (same batch, same
  * run; before the next forward on it). One launch (kernel id SPWGNN_K_REL_BWD) that rebuilds h2 per
  * (32-edge block, step) from the stored rows on the run's backward product class (X6 and H3: six bf16
  * products, X3: three, BF16: one, F32: the f32 matrix instructions) and sums the steps per edge in step
@@ -419,6 +419,42 @@ int32_t spwgnn_backward_relations(const float* params, const spwgnn_batch* batch
                                   float* drel       /* [32·n_eblocks] plan edge-slot order */,
                                   float* drel_steps /* [mp_steps][32·n_eblocks], or NULL */,
                                   spwgnn_stream_t stream);
+
+/* Relation gates (added within ABI 8: new symbols only, no existing struct or signature changed;
+ * DESIGN.md §3zz): soft relations in the forward and the backward. One gate w_k per active edge, shared by
+ * all mp_steps steps, any finite fp32 (0 and negative values included), in the receiver sum of
+ * Networks.py:88 ALONE:
+ *   eff_{i,s} = tanh(Σ_{k: dst_k = i} w_k · (h2_{k,s}·W3 + b3)) = tanh([Σ w_k·h2_{k,s} | Σ w_k]·[W3; b3]).
+ * Nothing else in the graph sees the gate: the gathers of Networks.py:33 and :85 stay ungated. w_k = 0
+ * MULTIPLIES, it does not delete: an edge whose message is infinite or NaN gives NaN under a zero gate
+ * (0·inf), where a plan built without that edge would not.
+ * gates: device fp32 [32·n_eblocks] (16-byte aligned) in the plan's edge-slot order (edge_src / edge_dst's,
+ * the order of spwgnn_backward_relations' drel). A padding slot's value is never used: any bits there, NaN
+ * included, leave every output unchanged.
+ * gates == NULL: spwgnn_forward_state / spwgnn_backward_state bit for bit, with the same launches (the
+ * team / fused small-batch path where it applies). With gates the call takes the wide kernels at every
+ * batch size and the one-hot edge forward on a receiver-block plan; the team / fused forms and the
+ * column-sum receiver-block kernel are not gated. Every plan kind (capacity, packed, device-filled with
+ * all-padding blocks, wave-tiles of up to 32 nodes), a null or non-null prop, with or without dprop /
+ * state_out / dstate, training and inference, every spwgnn_da_stored_steps setting.
+ * Maths: spwgnn_gates_supported(math) is 1 for X6, X3 and H3, 0 for F32 and BF16 — a gated call in those
+ * returns SPWGNN_E_SHAPE — and -1 for an id this library does not know. All argument errors (a
+ * misaligned gates pointer: SPWGNN_E_ARG) return before any device work.
+ * CONTRACT: the backward's gates hold the values the forward's held (the library cannot check it; the
+ * Python layer does, engine.Workspace). After spwgnn_backward_gated, spwgnn_backward_inputs works as
+ * before and spwgnn_backward_relations returns d loss / d w_k AT THESE GATES.
+ * Per-step logits with gates, spwgnn_bce_backward with gates and per-step gates are not part of this. */
+int32_t spwgnn_gates_supported(int32_t math);
+int32_t spwgnn_forward_gated(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                             void* workspace, int64_t workspace_bytes,
+                             const float* gates /* [32·n_eblocks] plan edge-slot order; NULL = ungated */,
+                             float* logits, float* state_out /* as spwgnn_forward_state */,
+                             spwgnn_stream_t stream);
+int32_t spwgnn_backward_gated(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                              void* workspace, int64_t workspace_bytes,
+                              const float* gates /* the forward's; NULL = ungated */,
+                              const float* dlogits, const float* dstate /* as spwgnn_backward_state */,
+                              float* grads, float* dprop, spwgnn_stream_t stream);
 
 /* Keras binary_crossentropy on sigmoid(logits) (Networks.py:102), mean over n:
  * out3 = {loss, sum of correct (binary_accuracy numerator), n}; dlogits = dloss/dlogit.

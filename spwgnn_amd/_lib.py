@@ -147,6 +147,9 @@ def _declare(lib: C.CDLL) -> None:
                                    vp, vp, vp, vp]),
         "spwgnn_backward_inputs": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp]),
         "spwgnn_backward_relations": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp]),
+        "spwgnn_gates_supported": (i32, [i32]),
+        "spwgnn_forward_gated": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp, vp]),
+        "spwgnn_backward_gated": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp, vp, vp, vp]),
         "spwgnn_plan_device_positions": (i32, [C.POINTER(PlanDeviceC), vp, i32, f32, f32, vp]),
         "spwgnn_plan_device_dense": (i32, [C.POINTER(PlanDeviceC), vp, vp, i32, i32, vp]),
         "spwgnn_bce_scratch_bytes": (i64, [i64]),

@@ -129,6 +129,10 @@ class HostPlan:
         """`TowerBatch.edges_to_input` of the batch this plan becomes (it reads the host fields they share)."""
         return TowerBatch.edges_to_input(self, values, dense)
 
+    def edge_gates(self, values, fill: float = 0.0, device=None) -> torch.Tensor:
+        """`TowerBatch.edge_gates` of the batch this plan becomes, on ``device`` (default: where ``values`` is)."""
+        return TowerBatch.edge_gates(self, values, fill, device)
+
     @staticmethod
     def build(pos, tower_nodes, src, dst, tower_edges, prop=None, nw_max=None, node_shape=None, tower_ids=None,
               edge_cap=None, recv_blocks=None, pack: bool = False) -> "HostPlan":
@@ -311,6 +315,45 @@ class TowerBatch:
         out = np.zeros(v.shape[:-1] + (len(tn), N, N), v.dtype)
         out[..., src // N, src % N, dst % N] = vals
         return out
+
+    def edge_gates(self, values, fill: float = 0.0, device=None) -> torch.Tensor:
+        """Per-relation values → the (32·n_eblocks,) fp32 tensor in the plan's edge-slot order that
+        ``engine.forward(..., gates=)`` takes: the inverse of `edges_to_input`. ``values`` is a 1-D tensor with
+        one entry per active relation in the input's edge order (the order of ``self.src`` / ``self.dst``), or,
+        for towers of one size N, a dense (B, N, N) tensor indexed [tower, sender, receiver] in the input's
+        tower and node order (through ``node_perm`` for packed plans); entries without a relation are not read.
+        Padding slots get ``fill`` (the engine never reads them). Built from torch indexing ops on the
+        batch's device, so autograd reaches ``values``."""
+        dev = getattr(self, "device", None) if device is None else torch.device(device)
+        v = values if isinstance(values, torch.Tensor) else torch.as_tensor(np.asarray(values))
+        if dev is None:
+            dev = v.device
+        v = v.to(device=dev, dtype=torch.float32)
+        eid = np.asarray(self.edge_id, np.int64)
+        src, dst = np.asarray(self.src, np.int64), np.asarray(self.dst, np.int64)
+        if v.dim() == 1:
+            if v.shape[0] != len(src):
+                raise ValueError(f"values must hold one entry per active relation ({len(src)}), got {tuple(v.shape)}")
+            pick = np.maximum(eid, 0)
+        elif v.dim() == 3:
+            tn = np.asarray(self.tower_nodes)
+            if len(tn) == 0 or np.any(tn != tn[0]) or tuple(v.shape) != (len(tn), int(tn[0]), int(tn[0])):
+                raise ValueError("the dense form needs towers of one size N and a (B, N, N) [tower, sender, receiver] "
+                                 f"tensor, got {tuple(v.shape)}")
+            N = int(tn[0])
+            if self.node_perm is not None:
+                perm = np.asarray(self.node_perm, np.int64)
+                src, dst = perm[src], perm[dst]
+            flat = src * N + dst % N   # ((b·N + s)·N + r) with src = b·N + s
+            pick = flat[np.maximum(eid, 0)] if len(flat) else np.zeros(len(eid), np.int64)
+            v = v.reshape(-1)
+        else:
+            raise ValueError(f"values must be 1-D (input edge order) or (B, N, N), got {tuple(v.shape)}")
+        if v.numel() == 0:
+            return torch.full((len(eid),), float(fill), dtype=torch.float32, device=dev)
+        active = torch.as_tensor(eid >= 0, device=dev)
+        got = v[torch.as_tensor(pick, device=dev)]
+        return torch.where(active, got, torch.full_like(got, float(fill))).contiguous()
 
     @property
     def n_edges(self) -> int:
@@ -719,6 +762,25 @@ class DeviceTowerBatch(TowerBatch):
     dst = property(lambda self: self._fetch()[2], doc="(Ne,) global receivers, fetched from the device (synchronises)")
     tower_edges = property(lambda self: self._fetch()[3], doc="(T,) active relations per tower, fetched from the device")
     edge_id = property(lambda self: self._fetch()[4], doc="(n_eblocks*32,) edge index per slot or -1, fetched from the device")
+
+    def edge_gates(self, values, fill: float = 0.0, device=None) -> torch.Tensor:
+        """`TowerBatch.edge_gates` from the device's own edge arrays. The dense (B, N, N) [tower, sender,
+        receiver] form (towers of one size) reads ``edge_src`` / ``edge_dst`` on the device: no host copy,
+        no synchronisation, valid for the relation set the batch holds when the ops run. The 1-D form
+        needs the host edge list (a synchronising fetch)."""
+        v = values if isinstance(values, torch.Tensor) else torch.as_tensor(np.asarray(values))
+        if v.dim() != 3:
+            return TowerBatch.edge_gates(self, values, fill, device)
+        tn = np.asarray(self.tower_nodes)
+        if len(tn) == 0 or np.any(tn != tn[0]) or tuple(v.shape) != (len(tn), int(tn[0]), int(tn[0])):
+            raise ValueError("the dense form needs towers of one size N and a (B, N, N) [tower, sender, receiver] "
+                             f"tensor, got {tuple(v.shape)}")
+        N = int(tn[0])
+        v = v.to(device=self.device, dtype=torch.float32).reshape(-1)
+        s, d = self.edge_src.long(), self.edge_dst.long()
+        active = s >= 0
+        got = v[torch.where(active, s * N + d % N, torch.zeros_like(s))]
+        return torch.where(active, got, torch.full_like(got, float(fill))).contiguous()
 
     def with_prop(self, prop: Optional[torch.Tensor]) -> "DeviceTowerBatch":
         """Same graph and device arrays, different propagation input (no host field is touched)."""

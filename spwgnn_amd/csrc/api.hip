@@ -53,16 +53,20 @@ int32_t spwgnn_team_max_blocks(int32_t set) { return team_max_blocks(set); }
 int32_t spwgnn_da_stored_steps(int32_t set) { return da_stored_steps(set); }
 int32_t spwgnn_math_products(int32_t math) { return math_products(math); }
 int32_t spwgnn_math_products_bwd(int32_t math) { return math_products_bwd(math); }
+// relation gates: the split maths with fp32 storage (one template family of the wide kernels)
+int32_t spwgnn_gates_supported(int32_t math) { return math_products(math) < 0 ? -1 : math_split32(math) ? 1 : 0; }
 
 static int32_t status(hipError_t e) { return e == hipSuccess ? SPWGNN_OK : (int32_t)e; }
 static bool mis16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; }
 
 // The prologue of every workspace call, in the order the status codes keep: validate, E_NOTRAIN, the
 // call's own argument checks (args_ok: the caller evaluates it first, so it follows neither batch nor
-// run), E_WORKSPACE. Fills w on SPWGNN_OK.
+// run), E_WORKSPACE. Fills w on SPWGNN_OK. gated: a call with relation gates — its math is a shape question
+// (SPWGNN_E_SHAPE where spwgnn_gates_supported answers 0), asked right after validate.
 static int32_t enter(const spwgnn_batch* batch, const spwgnn_run* run, const void* workspace, int64_t bytes,
-                     bool need_training, bool args_ok, Ws& w) {
+                     bool need_training, bool args_ok, Ws& w, bool gated = false) {
     if (int32_t stt = validate(batch, run)) return stt;
+    if (gated && !math_split32(run->math)) return SPWGNN_E_SHAPE;
     if (need_training && !run->training) return SPWGNN_E_NOTRAIN;
     if (!args_ok || !workspace) return SPWGNN_E_ARG;
     w = make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, run->training ? 1 : 0);
@@ -80,12 +84,13 @@ int32_t spwgnn_forward(const float* params, const spwgnn_batch* batch, const spw
 // DESIGN.md §3zr): the forward, then the state's export
 static int32_t forward_state(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
                              int64_t workspace_bytes, float* logits, float* state_out, bool steps,
-                             spwgnn_stream_t stream) {
+                             spwgnn_stream_t stream, const float* gates = nullptr) {
     Ws w;
-    if (int32_t stt = enter(batch, run, workspace, workspace_bytes, false, params && logits && !mis16(state_out), w))
+    if (int32_t stt = enter(batch, run, workspace, workspace_bytes, false,
+                            params && logits && !mis16(state_out) && !mis16(gates), w, gates != nullptr))
         return stt;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const FwdCall call{logits, state_out != nullptr, steps ? batch->n_nodes : 0};
+    const FwdCall call{logits, state_out != nullptr, steps ? batch->n_nodes : 0, gates};
     const int32_t stt = run_forward(params, batch, run, w, static_cast<char*>(workspace), call, st);
     if (stt || !state_out) return stt;
     const Ctx c{w, static_cast<char*>(workspace), false};
@@ -99,6 +104,14 @@ int32_t spwgnn_forward_state(const float* params, const spwgnn_batch* batch, con
     return forward_state(params, batch, run, workspace, workspace_bytes, logits, state_out, false, stream);
 }
 
+// gates null: spwgnn_forward_state itself. Otherwise the argument checks of that call, the gate pointer's own,
+// then the math (SPWGNN_E_SHAPE for one spwgnn_gates_supported answers 0 to) — all before any device work
+int32_t spwgnn_forward_gated(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                             int64_t workspace_bytes, const float* gates, float* logits, float* state_out,
+                             spwgnn_stream_t stream) {
+    return forward_state(params, batch, run, workspace, workspace_bytes, logits, state_out, false, stream, gates);
+}
+
 int32_t spwgnn_forward_steps(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
                              int64_t workspace_bytes, float* step_logits, float* state_out, spwgnn_stream_t stream) {
     return forward_state(params, batch, run, workspace, workspace_bytes, step_logits, state_out, true, stream);
@@ -109,7 +122,7 @@ int32_t spwgnn_forward_steps(const float* params, const spwgnn_batch* batch, con
 static int32_t backward(const spwgnn_batch* batch, const spwgnn_run* run, void* workspace, int64_t workspace_bytes,
                         bool ok, const BwdCall& call, spwgnn_stream_t stream) {
     Ws w;
-    if (int32_t stt = enter(batch, run, workspace, workspace_bytes, true, ok, w)) return stt;
+    if (int32_t stt = enter(batch, run, workspace, workspace_bytes, true, ok, w, call.gates != nullptr)) return stt;
     return run_backward(batch, run, w, static_cast<char*>(workspace), call, static_cast<hipStream_t>(stream));
 }
 
@@ -124,6 +137,16 @@ int32_t spwgnn_backward_state(const float* params, const spwgnn_batch* batch, co
                               float* dprop, spwgnn_stream_t stream) {
     const bool ok = params && dlogits && grads && !mis16(dstate);
     return backward(batch, run, workspace, workspace_bytes, ok, {dlogits, grads, dprop, nullptr, dstate}, stream);
+}
+
+// gates null: spwgnn_backward_state itself; the gates hold what the forward's held (the caller's contract)
+int32_t spwgnn_backward_gated(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                              int64_t workspace_bytes, const float* gates, const float* dlogits, const float* dstate,
+                              float* grads, float* dprop, spwgnn_stream_t stream) {
+    const bool ok = params && dlogits && grads && !mis16(dstate) && !mis16(gates);
+    BwdCall call{dlogits, grads, dprop, nullptr, dstate};
+    call.gates = gates;
+    return backward(batch, run, workspace, workspace_bytes, ok, call, stream);
 }
 
 int32_t spwgnn_backward_steps(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,

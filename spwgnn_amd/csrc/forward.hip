@@ -89,7 +89,7 @@ static EncEdgeArgs enc_edge_args(const Ctx& c, const spwgnn_batch* b, const spwg
     return ee;
 }
 
-static EdgeFwdArgs edge_fwd_args(const Ctx& c, const spwgnn_batch* b, const Path& p, int s) {
+static EdgeFwdArgs edge_fwd_args(const Ctx& c, const spwgnn_batch* b, const Path& p, int s, const float* gates = nullptr) {
     const Ws& w = c.w;
     EdgeFwdArgs ef{};
     ef.n_wtiles = b->n_wtiles;
@@ -115,6 +115,7 @@ static EdgeFwdArgs edge_fwd_args(const Ctx& c, const spwgnn_batch* b, const Path
     ef.uv_zero = s == 0 && !b->prop;   // 'propagation' = 0 (spwgnn.h): P0 = U0 = V0 = 0
     ef.gather_desc = p.gd_edge_fwd;
     ef.node_bytes = (uint32_t)(ef.gather_desc ? w.RN * kRowE * 4 : 0);
+    ef.gates = gates;
     return ef;
 }
 
@@ -157,6 +158,7 @@ static NodeFwdArgs node_fwd_args(const Ctx& c, const spwgnn_batch* b, const Path
 int32_t run_forward(const float* params, const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, char* base,
                     const FwdCall& call, hipStream_t st) {
     const Ctx c{w, base, r->math != MATH_F32};
+    const WideCall wide(call.gates != nullptr);   // a gated call: the wide kernels at every batch size (§3zz)
     const Path p = make_path(b, r, w);
     if (int32_t e = prep(c, params, r, st)) return e;
     const EncNodeArgs en = enc_node_args(c, b, r, p);
@@ -195,7 +197,7 @@ int32_t run_forward(const float* params, const spwgnn_batch* b, const spwgnn_run
         SPW_TIMED(prof, SPWGNN_K_ENC_EDGE, launch_enc_edge(ee, p.enc_edge, st));
     }
     for (int s = 0; s < S; ++s) {
-        SPW_TIMED(prof, SPWGNN_K_EDGE_FWD, launch_edge_fwd(edge_fwd_args(c, b, p, s), p.edge_fwd, st));
+        SPW_TIMED(prof, SPWGNN_K_EDGE_FWD, launch_edge_fwd(edge_fwd_args(c, b, p, s, call.gates), p.edge_fwd, st));
         SPW_TIMED(prof, SPWGNN_K_NODE_FWD, launch_node_fwd(node_fwd_args(c, b, p, call, s), p.node_fwd, st));
     }
     return SPWGNN_OK;

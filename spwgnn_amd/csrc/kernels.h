@@ -148,6 +148,7 @@ struct EdgeFwdArgs {
     int uv_zero;       // step 0 of a null 'propagation': the U, V rows are all zero (§3zh)
     int gather_desc;   // 1: A, U, V rows through buffer descriptors (§3zk; the ≤ 16-node wide kernels)
     uint32_t node_bytes;   // gather_desc: bytes of one step's fp32 node array (RN · kRowE · 4 < 2^31)
+    const float* gates;    // relation gates [32·n_eblocks] in edge-slot order (§3zz), or null: k_edge_fwd_x6<GATE>
 };
 
 struct NodeFwdArgs {
@@ -213,6 +214,7 @@ struct EdgeBwdArgs {
                        // DESIGN.md §3zi); null = not kept
     int gather_desc;   // 1: G3 rows through a buffer descriptor (§3zk; the wide x6 / bf16 kernels)
     uint32_t node_bytes;   // gather_desc: bytes of one step's G3 array (RN · kRowE · 4 < 2^31)
+    const float* gates;    // relation gates [32·n_eblocks] (§3zz), or null: dh2pre_k carries gates[k]
 };
 
 struct DaArgs {           // k_dA_x6: dA = Σ_s dh1pre_s, recomputed per 32-edge block
@@ -229,6 +231,7 @@ struct DaArgs {           // k_dA_x6: dA = Σ_s dh1pre_s, recomputed per 32-edge
     int n_stored;
     int64_t slab_step;
     const float* slab;
+    const float* gates;   // relation gates [32·n_eblocks] (§3zz), or null: the rebuilt steps' dh2pre carries them
 };
 
 struct EncEdgeBwdArgs {
@@ -300,6 +303,7 @@ struct WgradArgs {
     int gather_desc;               // 1: U, V, G3 rows through buffer descriptors (each step's array < 2^31 bytes)
     int uv_zero;                   // 1: a null 'propagation' — U_0 = V_0 = 0, step 0's stages need not read them
     float* slab;           // [chunks][kx_pad][ny_pad]
+    const float* gates;    // YM_DH2 (k_w2grad_ws): relation gates [32·n_eblocks] (§3zz), or null
 };
 struct WgWsArgs {          // k_wgrad_ws: stages (s, nb) of a [S][nbs] grid of 32-row blocks
     const float* x;        // chunk-major
@@ -572,6 +576,19 @@ hipError_t launch_plan_device(const PlanDevArgs& a, bool dense, hipStream_t st);
 #endif
 constexpr int kTeamMaxBlocks = SPWGNN_TEAM_MAX_BLOCKS;
 bool team_blocks(int n_blocks);   // 32-row blocks of the launch (edge or node blocks)
+// A gated call (relation gates) takes the wide kernels at every batch size: while a WideCall
+// with on = true lives on the calling thread, team_blocks answers false there — to make_path and to every
+// launcher of the call — as spwgnn_team_max_blocks(0) makes it answer for the whole process. The process-wide
+// limit is not touched, and other threads' calls do not see it.
+struct WideCall {
+    explicit WideCall(bool on);
+    ~WideCall();
+    WideCall(const WideCall&) = delete;
+    WideCall& operator=(const WideCall&) = delete;
+    static bool active();   // on this thread
+private:
+    bool prev_;
+};
 int team_max_blocks(int set);      // set >= 0: the new limit (returns the previous one); < 0: query
 int da_stored_steps(int set);      // stored dh1pre steps of the x6 dA sum (spwgnn_da_stored_steps), same form
 hipError_t launch_enc_node_team(const EncNodeArgs& a, int math, hipStream_t st);

@@ -350,7 +350,9 @@ __device__ __forceinline__ void segsum_walk_b(const float* st, float* nacc, uint
 // B16 (bf16 math on wave-tiles of 17–32 nodes, which only this kernel serves): the products' operands
 // dh2pre and W2ᵀ rounded to bf16 and the sender/receiver sums adding bf16(dh1pre) — the bf16
 // arithmetic of the split-bf16 kernels on the fp32 matrix core; dA stays Σ fp32.
-template <bool ONEHOT, bool ACCUM, bool B16 = false>
+// GATE (relation gates): dh2pre_k = gates[k] · [h2_k > 0] ⊙ G3[dst_k], one gate per lane (edge);
+// a padding slot's gate is never read
+template <bool ONEHOT, bool ACCUM, bool B16 = false, bool GATE = false>
 __global__ __launch_bounds__(ONEHOT ? 512 : 256, ONEHOT ? 1 : 2) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_edge_bwd(EdgeBwdArgs a) {
     const int lane = threadIdx.x & 63, h = lane >> 5, i = lane & 31;
@@ -401,6 +403,8 @@ void k_edge_bwd(EdgeBwdArgs a) {
         const int d = cur.d;
         const bool valid = d >= 0;
         const int dc = valid ? d : n0;
+        float gw = 0.f;
+        if constexpr (GATE) gw = valid ? a.gates[e] : 0.f;
         // dh1 mask words (used after the GEMM: the load has the whole GEMM to land)
         const uint32_t* m1 = a.mask1 + (int64_t)blk * kLdE + i;
         uint32_t m1w[5];
@@ -429,6 +433,10 @@ void k_edge_bwd(EdgeBwdArgs a) {
             xv[1] = (bits & 2u) ? g.y : 0.f;
             xv[2] = (bits & 4u) ? g.z : 0.f;
             xv[3] = (bits & 8u) ? g.w : 0.f;
+            if constexpr (GATE) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) xv[k] *= gw;
+            }
             if (a.dh2_out) *reinterpret_cast<float4*>(dh2cm + 256 * q) = make_float4(xv[0], xv[1], xv[2], xv[3]);
             if (B16) {
 #pragma unroll
@@ -832,8 +840,11 @@ __device__ __forceinline__ float4 slab_load(const float4* p) {
 // 4's lanes i ≥ 24 — features past 151, always zero — left out), beside the one-hot MFMAs.
 // DESC (§3zk): the G3 rows through a buffer descriptor — a lane keeps the 32-bit byte offset of its
 // receiver's row and the chunk goes into the load's scalar offset (no 64-bit add per piece)
+// GATE (relation gates): dh2pre_k = gates[k] · [h2_k > 0] ⊙ G3[dst_k], one gate per lane (edge),
+// loaded a block ahead with the indices; a padding slot's gate is never used (its lane takes 0). A stored
+// dh1pre step (SLAB) then carries the gate too
 template <bool ACCUM, bool NODA = false, int NP = 3, int DBG = 0, bool N16 = false, bool SLAB = false,   // DBG 3 (diagnosis): G3 rows of the tile's first node
-          bool DESC = false>
+          bool DESC = false, bool GATE = false>
 __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_edge_bwd_x6(EdgeBwdArgs a) {
     static_assert(!SLAB || (NODA && NP >= 2 && !N16), "stored dh1pre steps: the x6 / x3 rebuild form only");
     constexpr int PF = NP == 1 ? SPWGNN_EBWD_PF_B16 : SPWGNN_EBWD_PF, kWaves = 8;   // bf16: see k_dA_x6
@@ -845,13 +856,14 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const int4* wtiles = reinterpret_cast<const int4*>(a.wtile);
     const int wstep = gridDim.x * kWaves;
     const WlBases wlb(wl + lane);
-    struct Pre { int d, s; uint32_t w[5]; };
+    struct Pre { int d, s; uint32_t w[5]; float gw; };
     auto load_pre = [&](int blk) {
         Pre p;
         const int64_t e = (int64_t)blk * 32 + i;
         p.d = a.edst[e];
         p.s = a.esrc[e];
         load_m2(a.mask2 + (int64_t)blk * kM2Blk, i, p.w);
+        if constexpr (GATE) p.gw = a.gates[e];
         return p;
     };
     struct GRow { const float4* p; int vo; };   // a receiver's G3 row: pointer, or (DESC) byte offset
@@ -893,6 +905,8 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         const int d = cur.d;
         const bool valid = d >= 0;
         const uint32_t* m1 = a.mask1 + (int64_t)blk * kLdE + i;
+        [[maybe_unused]] float gw = 0.f;
+        if constexpr (GATE) gw = valid ? cur.gw : 0.f;
         uint32_t m1w[5];   // loaded a few k-blocks before the dh1pre masking uses them
         uint32_t w[5];
 #pragma unroll
@@ -949,6 +963,10 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 xv[4 * c + 1] = mask_bit(cr.g[c].y, bits, 1);
                 xv[4 * c + 2] = mask_bit(cr.g[c].z, bits, 2);
                 xv[4 * c + 3] = mask_bit(cr.g[c].w, bits, 3);
+            }
+            if constexpr (GATE) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) xv[k] *= gw;
             }
             uint32_t hw[4], mw[4], lw[4];
 #pragma unroll
@@ -1074,6 +1092,22 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 }
 
 hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st) {
+    if (a.gates) {   // relation gates: the wide kernels of the split maths alone, the pointer form of the G3 rows
+        if (!math_split32(math) || a.n16 || team_blocks(a.n_wtiles) || (a.dh1_slab && (a.nw_max > 16 || !a.no_dA)))
+            return hipErrorInvalidValue;
+        if (a.nw_max <= 16) {
+            if (!a.no_dA) return hipErrorInvalidValue;   // dA is rebuilt after the step loop (k_dA_x6<GATE>)
+            const dim3 g(edge_grid(a.n_wtiles, 8)), b(512);
+            if (a.dh1_slab) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_bwd_x6<false, true, NP, 0, false, true, false, true>), g, b, 0, st, a));
+            else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_bwd_x6<false, true, NP, 0, false, false, false, true>), g, b, 0, st, a));
+        } else {
+            const size_t lds = edge_bwd_lds_per_wave(a.nw_max) * a.wpg;
+            const dim3 g((a.n_wtiles + a.wpg - 1) / a.wpg), b(64 * a.wpg);
+            if (a.dA_accumulate) hipLaunchKernelGGL((k_edge_bwd<false, true, false, true>), g, b, lds, st, a);
+            else hipLaunchKernelGGL((k_edge_bwd<false, false, false, true>), g, b, lds, st, a);
+        }
+        return hipGetLastError();
+    }
     // a stored dh1pre step: the wide x6 / x3 rebuild form only (k_dA_x6<NP, false, true> is its one reader)
     if (a.dh1_slab && (!math_split32(math) || a.nw_max > 16 || !a.no_dA || team_blocks(a.n_wtiles))) return hipErrorInvalidValue;
     if (math != MATH_F32 && a.nw_max <= 16 && a.no_dA && team_blocks(a.n_wtiles))   // small batches
@@ -1146,7 +1180,9 @@ hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st) {
 // rebuild loop are then steps S−1−n_stored .. 0 of every block (step 0 is never stored: n_stored < S),
 // and the G3 ring carries over between those pairs as before; a block's stored steps are read ahead
 // of its first rebuilt pair, where the accumulators are zero and acc is free.
-template <int NP = 3, bool B16 = false, bool SLAB = false>
+// GATE (relation gates): the rebuilt steps' dh2pre carries the edge's gate as in
+// k_edge_bwd_x6<GATE> (the stored steps already do): one value per lane and block, read with the receiver index
+template <int NP = 3, bool B16 = false, bool SLAB = false, bool GATE = false>
 __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_dA_x6(DaArgs a) {
     static_assert(!SLAB || (NP >= 2 && !B16), "stored dh1pre steps: x6 / x3 only");
     // bf16 math (NP = 1): a k-block is 5 MFMAs, so the G3 rows run further ahead to cover HBM latency
@@ -1218,6 +1254,8 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const int s_top = SLAB ? a.S - 1 - a.n_stored : a.S - 1;   // a block's first rebuilt step
     int blk = b0, s = s_top;
     int d = a.edst[(int64_t)blk * 32 + i];
+    [[maybe_unused]] float gw = 0.f;   // the block's gate of this lane's edge (0 on a padding slot, whatever it holds)
+    if constexpr (GATE) gw = d >= 0 ? a.gates[(int64_t)blk * 32 + i] : 0.f;
     Pair cur = load_pair(blk, s, d);
     KB ring[PF];
 #pragma unroll
@@ -1263,6 +1301,10 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         const int nblk = last_step ? (blk + kStride < b1 ? blk + kStride : blk) : blk;
         const int ns = last_step ? s_top : s - 1;
         const int nd = last_step ? a.edst[(int64_t)nblk * 32 + i] : d;
+        [[maybe_unused]] float ngw = gw;
+        if constexpr (GATE) {
+            if (last_step) ngw = nd >= 0 ? a.gates[(int64_t)nblk * 32 + i] : 0.f;
+        }
         const Pair nxt = load_pair(nblk, max(ns, 0), nd);
         const uint64_t mlo = h == 0 ? ((uint64_t)cur.w[1] << 32 | cur.w[0])
                                     : ((uint64_t)cur.w[4] << 52 | (uint64_t)cur.w[3] << 20 | (cur.w[2] >> 12));
@@ -1281,6 +1323,10 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 xv[4 * c + 1] = mask_bit(cr.g[c].y, bits, 1);
                 xv[4 * c + 2] = mask_bit(cr.g[c].z, bits, 2);
                 xv[4 * c + 3] = mask_bit(cr.g[c].w, bits, 3);
+            }
+            if constexpr (GATE) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) xv[k] *= gw;
             }
             uint32_t hw[4], mw[4], lw[4];
 #pragma unroll
@@ -1336,6 +1382,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         blk = nblk;
         s = ns;
         d = nd;
+        gw = ngw;
         cur = nxt;
     }
 #if SPWGNN_DA_INTERLEAVE && SPWGNN_DA_LOCKSTEP
@@ -1344,6 +1391,14 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 }
 
 hipError_t launch_dA(const DaArgs& a, int math, hipStream_t st) {
+    if (a.gates) {   // relation gates: the wide rebuild of the split maths alone
+        if (!math_split32(math) || a.b16 || team_blocks(a.n_eblocks) || (a.n_stored > 0 && (a.n_stored >= a.S || !a.slab)))
+            return hipErrorInvalidValue;
+        const dim3 g(edge_grid(a.n_eblocks, 8)), b(512);
+        if (a.n_stored > 0) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_dA_x6<NP, false, true, true>), g, b, 0, st, a));
+        else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_dA_x6<NP, false, false, true>), g, b, 0, st, a));
+        return hipGetLastError();
+    }
     if (a.n_stored > 0 && (!math_split32(math) || team_blocks(a.n_eblocks))) return hipErrorInvalidValue;
     if ((math_split32(math) || math == MATH_BF16) && team_blocks(a.n_eblocks)) return launch_dA_team(a, math, st);
     const dim3 g(edge_grid(a.n_eblocks, 8)), b(512);

@@ -1015,8 +1015,10 @@ struct NodeSum16X6 {
 // DESC (§3zk): the A rows and the gathered U, V rows through buffer descriptors — the block's A base
 // and the node arrays are wave-uniform, a lane keeps one 32-bit offset per row and the chunk goes
 // into the load's scalar offset (the pointer form adds 64·q·16 bytes to a 64-bit pointer per piece)
+// GATE (relation gates): the h2 row of edge k — its degree column included — is scaled by
+// EdgeFwdArgs::gates[k] just before the receiver sum; the stored h2 > 0 bits stay the ungated h2's
 template <bool NW16, int DBG = 0, Np NP = 3, bool AB16 = false, bool W8 = false, bool N16 = false,   // AB16: A stored as bf16 (§3g)
-          bool UV0 = false, bool DESC = false>
+          bool UV0 = false, bool DESC = false, bool GATE = false>
 __global__ __launch_bounds__((NW16 || W8) ? 512 : 256, 1) __attribute__((amdgpu_waves_per_eu((NW16 || W8) ? 2 : 1, (NW16 || W8) ? 2 : 1)))
 void k_edge_fwd_x6(EdgeFwdArgs a) {
     // bf16 math (NP = 1): a k-block is 5 MFMAs, too short to cover a load one k-block ahead
@@ -1240,6 +1242,26 @@ void k_edge_fwd_x6(EdgeFwdArgs a) {
                 }
 #pragma unroll
             for (int k = 0; k < 4; ++k) m2row[64 * k + lane] = mw2[k];
+        }
+        if constexpr (GATE) {
+            // reg r of a C tile is edge rho(r, h): the block's 32 gates sit at a wave-uniform address (scalar
+            // loads, no vector register held across the product loop) and a lane picks its half's; a padding
+            // slot's bits are masked to +0, never multiplied
+            const float* __restrict__ gr = a.gates + (int64_t)blk * 32;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float w0 = gr[rho(r, 0)], w1 = gr[rho(r, 1)];
+                const float wr = mask_bit(h ? w1 : w0, vh, rho(r, 0));
+#pragma unroll
+                for (int t = 0; t < 5; ++t) {
+                    // the rounded fp32 product is the value the receiver sum splits, as an ungated h2 is: behind an
+                    // opaque copy, so the multiply is not contracted into the split's residual (x − hi as one
+                    // mixed-precision fma of the unrounded product, which the f16 form then rounds a second way)
+                    float v = acc[t][r] * wr;
+                    asm volatile("" : "+v"(v));
+                    acc[t][r] = v;
+                }
+            }
         }
         nsum.add(acc, d, NW16 ? lane : h);
         cur_sd = nsd;
@@ -1508,6 +1530,14 @@ hipError_t launch_enc_edge(const EncEdgeArgs& a, int math, hipStream_t st) {
 #endif
 constexpr bool kEfwdUv0 = SPWGNN_EFWD_UV0 != 0;
 // the ≤ 16-node wide forms: buffer-descriptor loads (EdgeFwdArgs::gather_desc) or 64-bit pointers
+// a gated call (EdgeFwdArgs::gates): split maths, fp32 rows, the 64-bit pointer form of the gathers at every size
+template <Np NP>
+static void launch_edge_fwd_gated(const EdgeFwdArgs& a, hipStream_t st) {
+    const dim3 g(edge_grid(a.n_wtiles, 8)), b(512);
+    if (a.nw_max > 16) hipLaunchKernelGGL((k_edge_fwd_x6<false, 0, NP, false, true, false, false, false, true>), g, b, 0, st, a);
+    else if (kEfwdUv0 && a.uv_zero) hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, NP, false, false, false, true, false, true>), g, b, 0, st, a);
+    else hipLaunchKernelGGL((k_edge_fwd_x6<true, 0, NP, false, false, false, false, false, true>), g, b, 0, st, a);
+}
 template <Np NP, bool AB16, bool N16, bool UV0>
 static void launch_edge_fwd16(const EdgeFwdArgs& a, hipStream_t st) {
     const dim3 g(edge_grid(a.n_wtiles, 8)), b(512);
@@ -1517,6 +1547,11 @@ static void launch_edge_fwd16(const EdgeFwdArgs& a, hipStream_t st) {
 hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
     if (a.nw_max > kNwMaxLimit) return hipErrorInvalidValue;  // one-hot rows: ≤ 32 nodes per wave-tile
     if ((a.uv16 == kUvB16) != (a.n16 != 0)) return hipErrorInvalidValue;   // bf16 U, V: the N16 kernel reads them
+    if (a.gates) {   // relation gates: the wide one-hot kernels of the split maths alone (no team, no column-sum form)
+        if (!math_split32(math) || a.n16 || a.a_b16 || a.recv_blocks || team_blocks(a.n_wtiles)) return hipErrorInvalidValue;
+        SPW_SPLIT32F(math, NP, (launch_edge_fwd_gated<NP>(a, st)));
+        return hipGetLastError();
+    }
     // small batches: a workgroup of five waves per wave-tile, one output tile per wave (kernels_team.hip)
     if ((math_split32(math) || math == MATH_BF16) && a.nw_max <= 16 && team_blocks(a.n_wtiles))
         return a.n16 ? hipErrorInvalidValue : launch_edge_fwd_team(a, math, st);   // team kernels: fp32 H2s

@@ -1434,7 +1434,13 @@ int team_max_blocks(int set) {
     return set >= 0 ? g_team_max.exchange(set) : g_team_max.load(std::memory_order_relaxed);
 }
 
+static thread_local bool t_wide_call = false;
+WideCall::WideCall(bool on) : prev_(t_wide_call) { t_wide_call = prev_ || on; }
+WideCall::~WideCall() { t_wide_call = prev_; }
+bool WideCall::active() { return t_wide_call; }
+
 bool team_blocks(int n_blocks) {
+    if (t_wide_call) return false;
 #ifdef SPWGNN_DIAG   // A/B: SPWGNN_NO_TEAM=1 keeps the one-wave-per-block kernels at every size
     static const bool off = getenv("SPWGNN_NO_TEAM") && atoi(getenv("SPWGNN_NO_TEAM"));
     if (off) return false;

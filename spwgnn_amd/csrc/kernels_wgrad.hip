@@ -571,15 +571,19 @@ struct W2gSet {
     uint2 ah[5];   // A rows stored as bf16 (AB16): unpacked where they are used (build)
     uint32_t m[5];
     int in;
+    float gw;      // GATE: the edge's relation gate (0 on a padding slot)
 };
 
 // DBG (diagnosis builds, SPWGNN_W2G_DBG): 1 no MFMAs, 2 gathers from stage 0, 4 no staging
 // arithmetic, 8 matrix waves at s_setprio 1, 32 no gathers
 // DESC: U, V, G3 rows through per-step buffer descriptors, the lane's node offsets and the block's
 // src / dst read once per 32-edge block (§3zk); false: per-stage 64-bit pointers (arrays ≥ 2^31 bytes)
-template <int dbg, int NP = 3, bool AB16 = false, bool DESC = true>   // AB16: A stored as bf16 (bf16 math, §3g)
+// GATE (relation gates; the pointer form): the staged Y row is dh2pre_k = gates[k] · [h2_k > 0] ⊙
+// G3[dst_k]; X = [h1 | 1] is ungated
+template <int dbg, int NP = 3, bool AB16 = false, bool DESC = true, bool GATE = false>   // AB16: A stored as bf16 (bf16 math, §3g)
 __device__ __forceinline__ void w2grad_ws_body(const WgradArgs& a, int64_t blk_per_wg, int bid,
                                                char (*buf)[2 * kW2gImg]) {   // [stage parity][X | Y]
+    static_assert(!GATE || (!DESC && !AB16 && dbg == 0), "gated W2 gradient: the split maths' pointer form");
     using IM = X6Img<160>;
     const int tid = threadIdx.x;
     const int S = a.S;
@@ -670,6 +674,7 @@ __device__ __forceinline__ void w2grad_ws_body(const WgradArgs& a, int64_t blk_p
         int64_t b; int s;
         stage_of(t, b, s);
         R.in = idx.x >= 0;
+        if constexpr (GATE) R.gw = R.in ? a.gates[32 * b + rr] : 0.f;
         const int sn = R.in ? idx.x : 0, dn = R.in ? idx.y : 0;
         const int64_t ns = (int64_t)s * nstep_n;
         const float* pu = a.U + ns + (int64_t)(sn >> 5) * kCmBlk + (sn & 31) * 4;
@@ -699,11 +704,12 @@ __device__ __forceinline__ void w2grad_ws_body(const WgradArgs& a, int64_t blk_p
             // dh2pre = G3 ⊙ [h2 > 0]: sign-extended single-bit fields as AND masks
             const int w = (int)(R.in ? R.m[k] : 0u);
             const float4 gv = R.g[k];
-            const float4 y = make_float4(
+            float4 y = make_float4(
                 __int_as_float(__float_as_int(gv.x) & __builtin_amdgcn_sbfe(w, 4 * c0, 1)),
                 __int_as_float(__float_as_int(gv.y) & __builtin_amdgcn_sbfe(w, 4 * c0 + 1, 1)),
                 __int_as_float(__float_as_int(gv.z) & __builtin_amdgcn_sbfe(w, 4 * c0 + 2, 1)),
                 __int_as_float(__float_as_int(gv.w) & __builtin_amdgcn_sbfe(w, 4 * c0 + 3, 1)));
+            if constexpr (GATE) y = make_float4(y.x * R.gw, y.y * R.gw, y.z * R.gw, y.w * R.gw);
             IM::template put<NP>(Xs, rr, c0 + 8 * k, x);
             IM::template put<NP>(Ys, rr, c0 + 8 * k, y);
         }
@@ -857,11 +863,11 @@ __device__ __forceinline__ void w2grad_ws_body(const WgradArgs& a, int64_t blk_p
     }
     __syncthreads();   // the matrix waves' last stage
 }
-template <int dbg, int NP = 3, bool AB16 = false, bool DESC = true>
+template <int dbg, int NP = 3, bool AB16 = false, bool DESC = true, bool GATE = false>
 __global__ __launch_bounds__(kW2gThreads, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_w2grad_ws(WgradArgs a, int64_t blk_per_wg) {
     __shared__ __attribute__((aligned(16))) char buf[2][2 * kW2gImg];
-    w2grad_ws_body<dbg, NP, AB16, DESC>(a, blk_per_wg, blockIdx.x, buf);
+    w2grad_ws_body<dbg, NP, AB16, DESC, GATE>(a, blk_per_wg, blockIdx.x, buf);
 }
 
 // W2 gradient with the node rows staged in LDS per (wave-tile, step) — bf16 math. The per-edge
@@ -1845,6 +1851,11 @@ hipError_t launch_w2grad_ws(const WgradArgs& a, int wgs, int64_t blk_per_wg, int
     constexpr int dbg = 0;
 #endif
     const dim3 g(wgs), b(kW2gThreads);
+    if (a.gates) {   // relation gates: the split maths' pointer form, its Y rows gated
+        if (!math_split32(math) || a.a_b16 || a.uv16 || dbg) return hipErrorInvalidValue;
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_w2grad_ws<0, NP, false, false, true>), g, b, 0, st, a, blk_per_wg));
+        return hipGetLastError();
+    }
     if (a.uv16 && (math != MATH_BF16 || (dbg && dbg < 100))) return hipErrorInvalidValue;
     if (math == MATH_BF16) {
 #ifdef SPWGNN_DIAG

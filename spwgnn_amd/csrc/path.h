@@ -16,6 +16,7 @@ struct BwdCall {
     const BceArgs* bce = nullptr;     // spwgnn_bce_backward: the loss of the same call
     const float* dstate = nullptr;    // spwgnn_backward_state: the cotangent of P_S, row-major
     int64_t dl_step = 0;
+    const float* gates = nullptr;     // spwgnn_backward_gated: the forward's relation gates (§3zz)
 };
 
 // Diagnosis switches (A/B of superseded kernels): environment variables read per call in -DSPWGNN_DIAG
@@ -56,6 +57,9 @@ struct Path {
     bool gd_w2, gd_edge_fwd, gd_edge_bwd;   // node rows through buffer descriptors (§3zk), per kernel
     bool recv_blocks;            // the receiver-block edge forward
     bool team_edges;             // team_blocks(n_eblocks): a small batch's gradients share launches
+    // a gated call (relation gates, §3zz; the caller holds a WideCall): no team_* kernel, fused loop or enc_pair
+    // at any batch size, the one-hot edge forward on a receiver-block plan, pointer-form gathers in the gated kernels
+    bool gated;
     // a backward only (make_path with a BwdCall)
     bool ws_skip0;      // null prop: the k_wgrad_ws jobs over P leave step 0's stages out (§3zh)
     bool skip_eb0;      // ... and step 0's edge backward, which would write only dU_0 / dV_0, is not launched

@@ -61,6 +61,9 @@ Path make_path(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, const Bw
     p.diag = {getenv_flag("SPWGNN_WG_OLD"),      getenv_flag("SPWGNN_FUSED_ENC"),    getenv_flag("SPWGNN_DA_PAIR"),
               getenv_flag("SPWGNN_W2G_GATHER"),  getenv_flag("SPWGNN_W2G_OLD"),      getenv_flag("SPWGNN_NO_W2_MERGE"),
               getenv_flag("SPWGNN_WS_UNBATCHED"), getenv_flag("SPWGNN_WS_NOGROUP"), getenv_flag("SPWGNN_NO_POS3_MERGE")};
+    // a gated call (the caller's WideCall): team_blocks answers false below and in every launcher, which turns
+    // off team_*, the fused loops and enc_pair for this call alone
+    p.gated = WideCall::active();
     const bool team_tiles = team_blocks(b->n_wtiles), team_nodes = team_blocks((b->n_nodes + 31) / 32);
     const bool recv_plan = (b->flags & SPWGNN_BATCH_RECV_BLOCKS) != 0;
     p.team_edges = team_blocks(b->n_eblocks);
@@ -86,7 +89,8 @@ Path make_path(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, const Bw
                  !getenv_flag("SPWGNN_NO_ENC_PAIR");
     p.wide_node_side = r->math != MATH_F32 && p.node_fwd != MATH_F32 && !team_nodes &&
                        (!r->training || (p.node_bwd != MATH_F32 && p.wgrad != MATH_F32 && !p.diag.wg_old));
-    p.recv_blocks = recv_plan && math_split32(p.edge_fwd) && b->n_eblocks == b->n_nodes && !getenv_flag("SPWGNN_RB_ONEHOT");
+    p.recv_blocks = recv_plan && math_split32(p.edge_fwd) && b->n_eblocks == b->n_nodes && !getenv_flag("SPWGNN_RB_ONEHOT") &&
+                    !p.gated;   // the column-sum kernel is not gated: the one-hot edge forward serves the plan
 
     // the wide x6 edge backward keeps dh1pre in dz4, dz3, dz2, dz1 — one chunk-major block per 32-edge
     // block, exactly a stored block's size — which nothing writes or reads between the previous backward's

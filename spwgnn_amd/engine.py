@@ -139,6 +139,7 @@ class Workspace:
         self.fwd_batch = None                  # weakref to the batch that forward ran on
         self.bwd_key: Optional[tuple] = None   # fwd_key once a backward of that forward has run (backward_inputs)
         self.has_state = False                 # that forward returned the final state (backward's dstate needs it)
+        self.gate_key: Optional[tuple] = None  # that forward's relation gates (pointer, version), None: ungated
 
     @staticmethod
     def key(batch: TowerBatch, run: "RunConfig") -> tuple:
@@ -155,8 +156,9 @@ class Workspace:
         return (self.buf is not None and self.fwd_batch is not None and self.fwd_batch() is batch
                 and self.fwd_key == Workspace.key(batch, run))
 
-    def stored(self, batch: TowerBatch, run: "RunConfig", ok: bool, has_state: bool):
+    def stored(self, batch: TowerBatch, run: "RunConfig", ok: bool, has_state: bool, gates=None):
         """What a forward that returned `ok` left here (a failed one: nothing a backward may read)."""
+        self.gate_key = _gate_key(gates) if ok else None
         self.fwd_key = Workspace.key(batch, run) if ok else None
         self.fwd_batch = weakref.ref(batch) if ok else None
         self.bwd_key = None
@@ -169,6 +171,41 @@ class Workspace:
             if POISON_WORKSPACE:   # debugging: every fresh workspace byte 0xFF (NaN as fp32)
                 self.buf.fill_(0xFF)
         return self.buf
+
+
+def _gate_key(gates: Optional[torch.Tensor]) -> Optional[tuple]:
+    """What identifies a gate tensor's values between a forward and its backward: the storage address and the
+    tensor's version counter (an in-place write bumps it)."""
+    return None if gates is None else (gates.data_ptr(), int(gates._version))
+
+
+def gates_supported(math) -> bool:
+    """Whether `forward` / `backward` take ``gates=`` in this math — a `MATH_MODES` name or a SPWGNN_MATH_* id
+    (spwgnn_gates_supported): x6, x3 and h3 do, f32 and bf16 do not."""
+    if isinstance(math, str):
+        if math not in MATH_MODES:
+            raise ValueError(f"math must be one of {sorted(MATH_MODES)}")
+        math = MATH_MODES[math]
+    st = int(_lib.lib().spwgnn_gates_supported(int(math)))
+    if st < 0:
+        raise ValueError(f"unknown math id {math}")
+    return st == 1
+
+
+def _check_gates(batch: TowerBatch, run: "RunConfig", gates: torch.Tensor) -> torch.Tensor:
+    """A relation-gate tensor of `forward` / `backward`, validated before the library call: (32·n_eblocks,) fp32,
+    contiguous, 16-byte aligned, on the GPU, in a math that takes gates. Returns it detached."""
+    if not gates_supported(run.math):
+        raise ValueError(f"relation gates are not supported in math {run.math} (spwgnn_gates_supported: x6, x3 and h3 "
+                         "take them, f32 and bf16 do not)")
+    slots = 32 * batch.n_eblocks
+    if not isinstance(gates, torch.Tensor) or tuple(gates.shape) != (slots,):
+        raise ValueError(f"gates must be a ({slots},) tensor in the plan's edge-slot order (TowerBatch.edge_gates "
+                         f"builds it; got {tuple(getattr(gates, 'shape', ()))})")
+    _require_gpu(gates, "gates")
+    if gates.dtype != torch.float32 or not gates.is_contiguous() or gates.data_ptr() % 16:
+        raise ValueError("gates must be a contiguous, 16-byte aligned fp32 tensor")
+    return gates.detach()
 
 
 def workspace_bytes(batch: TowerBatch, run: RunConfig) -> int:
@@ -303,10 +340,14 @@ def _check_sums(total3: Optional[torch.Tensor], weights3: Optional[torch.Tensor]
         assert total3.dtype == torch.float64 and weights3.dtype == torch.float64
 
 
-def _forward(symbol: str, takes_state: bool, flat_params, batch, run, ws, out, shape, what, return_state, state):
+def _forward(symbol: str, takes_state: bool, flat_params, batch, run, ws, out, shape, what, return_state, state,
+             gates=None):
     """`forward` / `forward_steps`: ``out`` (or a fresh buffer) of `shape` written by the library's `symbol`,
-    whose argument list has a state pointer when `takes_state`."""
+    whose argument list has a state pointer when `takes_state` (and, in front of the outputs, a gate pointer
+    with ``gates``)."""
     _check_params(flat_params)
+    if gates is not None:
+        gates = _check_gates(batch, run, gates)
     buf = ws.get(workspace_bytes(batch, run))
     if out is None:
         out = _poison(torch.empty(shape, dtype=torch.float32, device=batch.device))
@@ -322,20 +363,29 @@ def _forward(symbol: str, takes_state: bool, flat_params, batch, run, ws, out, s
     b = batch.cstruct()
     r = run.cstruct(with_prologue=True)
     tail = (state.data_ptr() if return_state else None,) if takes_state else ()
+    head = (gates.data_ptr(),) if gates is not None else ()
     st = getattr(_lib.lib(), symbol)(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
-                                     out.data_ptr(), *tail, _stream(batch.device))
-    ws.stored(batch, run, st == 0, return_state)
+                                     *head, out.data_ptr(), *tail, _stream(batch.device))
+    ws.stored(batch, run, st == 0, return_state, gates)
     _lib.check(st, symbol)
     return (out, state) if return_state else out
 
 
 def forward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
             logits: Optional[torch.Tensor] = None, return_state: bool = False,
-            state: Optional[torch.Tensor] = None):
+            state: Optional[torch.Tensor] = None, gates: Optional[torch.Tensor] = None):
     """Logits (n_nodes,). With ``return_state`` also the final propagation state P_S, (n_nodes, 100) fp32
     in the plan's node order (spwgnn_forward_state) — what the next call takes as its ``prop`` — as
     ``(logits, state)``; the logits are the same bits either way. ``state``: the buffer to write it to
-    (a captured forward's static output, like ``logits``)."""
+    (a captured forward's static output, like ``logits``).
+    ``gates`` (spwgnn_forward_gated): one relation gate per edge slot, (32·n_eblocks,) fp32 in the plan's
+    edge-slot order (`TowerBatch.edge_gates` builds it), any finite values; edge k's message is scaled by
+    gates[k] in the receiver sum of Networks.py:88 alone, padding slots are never read. A gated call runs
+    the wide kernels at every batch size, in x6, x3 and h3 (`gates_supported`); its backward must be given
+    the same tensor, unchanged."""
+    if gates is not None:
+        return _forward("spwgnn_forward_gated", True, flat_params, batch, run, ws, logits, (batch.n_nodes,), "logits",
+                        return_state, state, gates)
     return _forward("spwgnn_forward_state" if return_state else "spwgnn_forward", return_state, flat_params, batch,
                     run, ws, logits, (batch.n_nodes,), "logits", return_state, state)
 
@@ -352,10 +402,17 @@ def forward_steps(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, 
 
 
 def _backward(symbol: str, takes_dstate: bool, flat_params, batch, run, ws, dlogits, rows, grads, want_dprop, dstate,
-              dprop):
+              dprop, gates=None):
     """`backward` / `backward_steps` through the library's `symbol`, whose argument list has a state
-    cotangent when `takes_dstate`. `rows`: the (mp_steps, n_nodes) shape ``dlogits`` must have, or None."""
+    cotangent when `takes_dstate` (and a gate pointer in front of ``dlogits`` with ``gates``). `rows`: the
+    (mp_steps, n_nodes) shape ``dlogits`` must have, or None."""
+    if gates is not None:
+        gates = _check_gates(batch, run, gates)
     dstate = _training_forward(ws, batch, run, dstate)
+    if ws.gate_key != _gate_key(gates):
+        # the library's contract (spwgnn_backward_gated): the backward's gates hold what the forward's held
+        raise ValueError("backward needs the relation gates of the forward on this workspace: the same tensor, "
+                         f"unchanged since (forward {ws.gate_key}, backward {_gate_key(gates)}; None = ungated)")
     if rows is not None and (not isinstance(dlogits, torch.Tensor) or tuple(dlogits.shape) != rows):
         raise ValueError(f"dstep_logits must be a {rows} tensor: one row of logit cotangents per propagation step "
                          f"(got {tuple(getattr(dlogits, 'shape', ()))})")
@@ -368,8 +425,9 @@ def _backward(symbol: str, takes_dstate: bool, flat_params, batch, run, ws, dlog
     r = run.cstruct()
     buf = ws.buf
     mid = (dstate.data_ptr() if dstate is not None else None,) if takes_dstate else ()
+    head = (gates.data_ptr(),) if gates is not None else ()
     st = getattr(_lib.lib(), symbol)(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
-                                     dlogits.data_ptr(), *mid, grads.data_ptr(),
+                                     *head, dlogits.data_ptr(), *mid, grads.data_ptr(),
                                      dprop.data_ptr() if dprop is not None else None, _stream(batch.device))
     ws.bwd_key = ws.fwd_key if st == 0 else None
     _lib.check(st, symbol)
@@ -378,12 +436,18 @@ def _backward(symbol: str, takes_dstate: bool, flat_params, batch, run, ws, dlog
 
 def backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace, dlogits: torch.Tensor,
              grads: Optional[torch.Tensor] = None, want_dprop: bool = False, dstate: Optional[torch.Tensor] = None,
-             dprop: Optional[torch.Tensor] = None):
+             dprop: Optional[torch.Tensor] = None, gates: Optional[torch.Tensor] = None):
     """Gradients of Σ dlogits·z — and, with ``dstate`` ((n_nodes, 100) fp32 on the batch's device, plan node
     order), of Σ dlogits·z + Σ dstate·P_S in the same single pass (spwgnn_backward_state); the forward on
     this workspace must then have been ``forward(..., return_state=True)``. A caller with a loss on the
     state alone passes zero ``dlogits``. ``dprop``: the (n_nodes, 100) buffer to write d/d'propagation' to
-    (it implies ``want_dprop``). Returns (grads, dprop)."""
+    (it implies ``want_dprop``). Returns (grads, dprop).
+    ``gates`` (spwgnn_backward_gated): the gate tensor the forward on this workspace ran with — the same
+    tensor, not written since; other gates, or none after a gated forward (or gates after an ungated one),
+    raise ValueError. `backward_relations` then returns the gradient with respect to these gates."""
+    if gates is not None:
+        return _backward("spwgnn_backward_gated", True, flat_params, batch, run, ws, dlogits, None, grads, want_dprop,
+                         dstate, dprop, gates)
     return _backward("spwgnn_backward_state" if dstate is not None else "spwgnn_backward", dstate is not None,
                      flat_params, batch, run, ws, dlogits, None, grads, want_dprop, dstate, dprop)
 
@@ -433,9 +497,10 @@ def backward_relations(flat_params: torch.Tensor, batch: TowerBatch, run: RunCon
     """d(loss)/d(relation gate) of the last `backward` / `bce_backward` on this workspace
     (spwgnn_backward_relations): (32·n_eblocks,) fp32 in the plan's edge-slot order (``batch.edge_src`` /
     ``edge_dst``'s; `TowerBatch.edges_to_input` maps it back), 0 in padding slots. Entry k is the gradient
-    of a scalar gate on edge k in the receiver sum of Networks.py:88 alone, taken at the all-ones gate — in
+    of a scalar gate on edge k in the receiver sum of Networks.py:88 alone, taken at the run's gates (all ones
+    after an ungated forward, the ``gates=`` of `forward` / `backward` after a gated one) — in
     reference terms d loss / d receiver_relations[b, dst_k, k] through line 88, not through the gathers of
-    lines 33 and 85; the forward is never gated. One extra launch that only reads the workspace: the
+    lines 33 and 85. One extra launch that only reads the workspace: the
     gradients `backward` returned and `backward_inputs` are untouched, in either call order.
     ``drel``: the buffer to write to. With ``per_step`` returns ``(drel, drel_steps)``, drel_steps
     (mp_steps, 32·n_eblocks) holding each propagation step's share (their sum over steps is drel);

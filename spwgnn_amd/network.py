@@ -20,35 +20,46 @@ from .batch import TowerBatch
 class _PropagationFn(torch.autograd.Function):
     """Forward/backward of the whole graph through the C-ABI; gradients w.r.t. the flat parameter
     buffer, the propagation input and the objects (the (n_nodes, 3) rows in the plan's node order;
-    the relation set is a constant of the graph and is not differentiated). With ``want_state`` a second
+    the relation set is a constant of the graph and is not differentiated) — and, with ``gates`` (one relation
+    gate per edge slot, `engine.forward`'s), the gates: d loss / d gate comes from `engine.backward_relations`
+    after the gated backward. With ``want_state`` a second
     output, the final state (n_nodes, 100), whose gradient enters the same backward pass as ``dstate``.
     With ``want_steps`` the first output is every step's logits (mp_steps, n_nodes) (`engine.forward_steps`)
     and its gradient goes back through `engine.backward_steps`, still one pass over the step loop."""
 
     @staticmethod
     def forward(ctx, flat, prop_dummy, obj_dummy, batch: TowerBatch, run: E.RunConfig, ws: E.Workspace,
-                want_state: bool = False, want_steps: bool = False):
+                want_state: bool = False, want_steps: bool = False, gates: Optional[torch.Tensor] = None):
         ctx.batch, ctx.run, ctx.ws = batch, run, ws
-        ctx.save_for_backward(flat)
+        ctx.gated = gates is not None
+        ctx.save_for_backward(*((flat, gates) if ctx.gated else (flat,)))
         ctx.want_prop = prop_dummy.requires_grad
         ctx.want_obj = obj_dummy.requires_grad
         ctx.want_state = want_state
         ctx.want_steps = want_steps
         ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None, not as zeros
+        if ctx.gated:   # forward_batch refuses gates with want_steps
+            return E.forward(flat, batch, run, ws, return_state=want_state, gates=gates)
         return (E.forward_steps if want_steps else E.forward)(flat, batch, run, ws, return_state=want_state)
 
     @staticmethod
     def backward(ctx, dlogits, dstate=None):
-        (flat,) = ctx.saved_tensors
+        flat, gates = ctx.saved_tensors if ctx.gated else (*ctx.saved_tensors, None)
         if dstate is not None:
             dstate = dstate.to(torch.float32).contiguous()
         if dlogits is None:   # a loss on the state alone: the library still takes a dlogits array
             shape = (ctx.run.mp_steps, ctx.batch.n_nodes) if ctx.want_steps else (ctx.batch.n_nodes,)
             dlogits = torch.zeros(shape, dtype=torch.float32, device=flat.device)
-        grads, dprop = (E.backward_steps if ctx.want_steps else E.backward)(
-            flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop, dstate=dstate)
+        if ctx.gated:
+            grads, dprop = E.backward(flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop, dstate=dstate,
+                                      gates=gates)
+        else:
+            grads, dprop = (E.backward_steps if ctx.want_steps else E.backward)(
+                flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop, dstate=dstate)
         dobj = E.backward_inputs(flat, ctx.batch, ctx.run, ctx.ws) if ctx.want_obj else None
-        return grads, dprop, dobj, None, None, None, None, None
+        # d loss / d gate at the run's gates, 0 in padding slots (one more launch that only reads the workspace)
+        dgates = E.backward_relations(flat, ctx.batch, ctx.run, ctx.ws) if ctx.gated and ctx.needs_input_grad[8] else None
+        return grads, dprop, dobj, None, None, None, None, None, dgates
 
 
 class _TowerLossFn(torch.autograd.Function):
@@ -132,8 +143,17 @@ class GraphNetwork(nn.Module):
                            math=self.math)
 
     def forward_batch(self, batch: TowerBatch, prop: Optional[torch.Tensor] = None,
-                      objects: Optional[torch.Tensor] = None, return_state: bool = False, return_steps: bool = False):
+                      objects: Optional[torch.Tensor] = None, return_state: bool = False, return_steps: bool = False,
+                      relation_weights: Optional[torch.Tensor] = None):
         """Logits (n_nodes,) for a compact batch (the reference returns sigmoid of these).
+
+        ``relation_weights``: soft relations — one gate per active relation, as
+        `TowerBatch.edge_gates` takes them: a dense (B, N, N) tensor indexed [tower, sender, receiver] for towers
+        of one size, or a 1-D tensor in the input's edge order. Relation k's message is scaled by its gate in the
+        receiver sum of Networks.py:88 alone (the gathers of lines 33 and 85 stay ungated); any finite value,
+        0 and negative ones included. Autograd reaches the weights, ``prop``, ``objects`` AND the gates (the gate
+        gradient is `engine.backward_relations` after the gated backward). Runs the wide kernels at every batch
+        size, in x6, x3 and h3; combines with ``return_state``, not with ``return_steps``.
 
         ``return_steps``: instead of the last step's logits, every step's, (mp_steps, n_nodes) — row s is
         the readout after s + 1 propagation steps (the network's column 0 at that step, Networks.py:89-94),
@@ -155,7 +175,15 @@ class GraphNetwork(nn.Module):
         want_obj = objects is not None and torch.is_grad_enabled() and objects.requires_grad
         # a carried state that has a gradient path needs this call's backward even under frozen weights
         want_prop = return_state and prop is not None and torch.is_grad_enabled() and prop.requires_grad
-        run = self._run(want_obj or want_prop)
+        gates = None
+        if relation_weights is not None:
+            if return_steps:
+                raise ValueError("relation_weights do not combine with return_steps (per-step logits are not gated)")
+            if not E.gates_supported(self.math):
+                raise ValueError(f'relation_weights are not supported in math "{self.math}" (x6, x3 and h3 take them)')
+            gates = batch.edge_gates(relation_weights)   # torch indexing: autograd reaches relation_weights
+        want_rel = gates is not None and torch.is_grad_enabled() and gates.requires_grad
+        run = self._run(want_obj or want_prop or want_rel)
         ws = E.Workspace(self.device)
         if prop is not None:
             batch = batch.with_prop(prop)
@@ -172,10 +200,13 @@ class GraphNetwork(nn.Module):
             odummy = dummy.new_zeros(0)
         if not run.training:
             with torch.no_grad():
-                out = (E.forward_steps if return_steps else E.forward)(self.flat.detach(), batch, run, ws,
-                                                                       return_state=return_state)
+                if gates is not None:
+                    out = E.forward(self.flat.detach(), batch, run, ws, return_state=return_state, gates=gates)
+                else:
+                    out = (E.forward_steps if return_steps else E.forward)(self.flat.detach(), batch, run, ws,
+                                                                           return_state=return_state)
         else:
-            out = _PropagationFn.apply(self.flat, dummy, odummy, batch, run, ws, return_state, return_steps)
+            out = _PropagationFn.apply(self.flat, dummy, odummy, batch, run, ws, return_state, return_steps, gates)
         if return_steps and batch.node_perm is not None:   # rows of a packed plan back in the input's node order
             steps = batch.to_input_order((out[0] if return_state else out).t()).t()
             return (steps, out[1]) if return_state else steps
@@ -211,8 +242,11 @@ class GraphNetwork(nn.Module):
         return TowerBatch.from_dense_device(objects, sender_relations, receiver_relations, propagation)
 
     def forward_logits(self, objects, sender_relations, receiver_relations, propagation=None,
-                       plan: str = "host", return_state: bool = False, return_steps: bool = False):
-        """``return_steps``: (S, B, N) — every step's logits (see `forward_batch`) in place of the last step's.
+                       plan: str = "host", return_state: bool = False, return_steps: bool = False,
+                       relation_weights: Optional[torch.Tensor] = None):
+        """``relation_weights``: a (B, N, N) [tower, sender, receiver] tensor of relation gates (soft relations:
+        see `forward_batch`); entries without a relation are not read. Autograd reaches it.
+        ``return_steps``: (S, B, N) — every step's logits (see `forward_batch`) in place of the last step's.
         (B, N) logits; with ``return_state`` ``(logits, state)``, state (B, N, 100) (see `forward_batch`). A torch ``objects`` that requires grad receives d/d objects (B, N, 3) on
         backward (see `forward_batch`; the relations are constants).
         ``plan``: "host" converts the relation matrices on the host (`TowerBatch.from_dense`: a copy to
@@ -225,7 +259,7 @@ class GraphNetwork(nn.Module):
         if propagation is not None:
             prop = torch.as_tensor(propagation, dtype=torch.float32, device=self.device).reshape(batch.n_nodes, 100)
         z = self.forward_batch(batch, prop, objects if isinstance(objects, torch.Tensor) else None,
-                               return_state=return_state, return_steps=return_steps)
+                               return_state=return_state, return_steps=return_steps, relation_weights=relation_weights)
         shape = (self.mp_steps, *batch.node_shape) if return_steps else batch.node_shape
         if return_state:
             z, state = z
@@ -233,13 +267,14 @@ class GraphNetwork(nn.Module):
         return z.reshape(shape)
 
     def forward(self, objects, sender_relations, receiver_relations, propagation=None, plan: str = "host",
-                return_state: bool = False, return_steps: bool = False):
+                return_state: bool = False, return_steps: bool = False,
+                relation_weights: Optional[torch.Tensor] = None):
         """(B, N, 1) probabilities: sigmoid(x[:, :, :1]) of the last step (Networks.py:93-96);
-        differentiable in a torch ``objects`` like `forward_logits` (``plan`` as there). With
+        differentiable in a torch ``objects`` like `forward_logits` (``plan`` and ``relation_weights`` as there). With
         ``return_state`` ``(probabilities, state)``, state (B, N, 100). With ``return_steps`` the
         probabilities of every step, (S, B, N, 1): how the predicted stabilities settle over the steps."""
         z = self.forward_logits(objects, sender_relations, receiver_relations, propagation, plan, return_state,
-                                return_steps)
+                                return_steps, relation_weights)
         if return_state:
             return torch.sigmoid(z[0])[..., None], z[1]
         return torch.sigmoid(z)[..., None]
@@ -250,8 +285,8 @@ class GraphNetwork(nn.Module):
         holds r_k at [b, dst_k, k] for every active relation column k of tower b and zero elsewhere
         (`engine.backward_relations`). r_k is the gradient of a scalar gate on relation k in
         the receiver sum of Networks.py:88 ALONE, at the all-ones gate: d L / d receiver_relations[b, dst_k, k]
-        through line 88, not through the gathers of lines 33 and 85 that read the same tensors. The forward
-        is not gated (soft relations / DropEdge are not built).
+        through line 88, not through the gathers of lines 33 and 85 that read the same tensors. (The gradient at
+        other gates is the ``.grad`` of a ``relation_weights`` leaf of `forward_logits`.)
         L is Σ dlogits·z for a ``dlogits`` (B, N) tensor, or ``loss(z)`` for a callable taking the (B, N)
         logits and returning a scalar (its d/dz by torch autograd), or — neither given — Σ sigmoid(z), the
         stability readout. One training forward with dropout 0 (the inference values, activations kept),
@@ -303,7 +338,8 @@ class GraphNetwork(nn.Module):
 
     def forward_positions(self, raw: torch.Tensor, threshold: Optional[float] = 170.0, divisor: float = 170.0,
                           tower_nodes=None, nw_max: Optional[int] = None, edge_cap=None, tower_ids=None,
-                          propagation: Optional[torch.Tensor] = None, check: bool = False, return_state: bool = False):
+                          propagation: Optional[torch.Tensor] = None, check: bool = False, return_state: bool = False,
+                          soft_tau: Optional[float] = None):
         """Logits from raw-pixel positions on the device, (B, N) for ``raw`` (B, N, 3) or (n_nodes,) for
         ragged towers ((n_nodes, 3) with ``tower_nodes``): the relation set (raw-pixel distance <
         ``threshold``, main.py:71-81) and the objects rows raw / ``divisor`` (main.py:91) are built on
@@ -311,8 +347,25 @@ class GraphNetwork(nn.Module):
         A ``raw`` that requires grad receives d/d raw = (d/d objects) / divisor on backward. The relation
         set is a CONSTANT of the graph: it is not differentiated, although it was computed from ``raw`` —
         the gradient is that of the network on the relation set the positions select, and it does not
-        see a relation appear or vanish as a box crosses the threshold."""
-        batch = TowerBatch.from_positions(raw, threshold, divisor, tower_nodes, nw_max, edge_cap, tower_ids, None, check)
+        see a relation appear or vanish as a box crosses the threshold.
+        ``soft_tau`` > 0 (raw pixels; equal towers, ``raw`` (B, N, 3)) makes the relation set of main.py:71-81
+        differentiable: the plan is fully connected and relation s → r carries the gate
+        sigmoid((threshold − ‖raw_s.xy − raw_r.xy‖) / soft_tau), computed in torch from ``raw`` — close to 1 well
+        inside the threshold, 1/2 on it, close to 0 far outside (as τ → 0 the hard relation set, up to the
+        gathers of Networks.py:33 and :85, which stay ungated). d/d raw then flows through the gates as well as
+        through the object rows."""
+        soft = soft_tau is not None and float(soft_tau) > 0.0
+        gates = None
+        if soft:
+            if threshold is None or raw.dim() != 3 or tower_nodes is not None:
+                raise ValueError("soft_tau needs a threshold and equal towers: raw (B, N, 3)")
+            xy = raw[..., :2].to(self.device, torch.float32)
+            d2 = ((xy[:, :, None, :] - xy[:, None, :, :]) ** 2).sum(-1)    # (B, N, N) [sender, receiver]
+            pos = d2 > 0   # the diagonal (and coincident boxes): sqrt has no derivative at 0; the diagonal is never read
+            dist = torch.where(pos, torch.sqrt(torch.where(pos, d2, torch.ones_like(d2))), torch.zeros_like(d2))
+            gates = torch.sigmoid((float(threshold) - dist) / float(soft_tau))
+        batch = TowerBatch.from_positions(raw, None if soft else threshold, divisor, tower_nodes, nw_max, edge_cap,
+                                          tower_ids, None, check)
         prop = None
         if propagation is not None:
             prop = torch.as_tensor(propagation, dtype=torch.float32, device=self.device).reshape(batch.n_nodes, 100)
@@ -321,7 +374,7 @@ class GraphNetwork(nn.Module):
             # the forward reads the batch's own rows (the kernel's raw / divisor); this node only carries
             # d/d objects back to raw through the division
             objects = raw.reshape(batch.n_nodes, raw.shape[-1])[:, :3] / divisor
-        z = self.forward_batch(batch, prop, objects, return_state=return_state)
+        z = self.forward_batch(batch, prop, objects, return_state=return_state, relation_weights=gates)
         if return_state:
             z, state = z
             if batch.node_shape is None:

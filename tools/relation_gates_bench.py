@@ -1,0 +1,94 @@
+#!/usr/bin/env python
+"""Time a gated training step's forward + backward (spwgnn_forward_gated / spwgnn_backward_gated)
+against the same tree's ungated run, in x6 math:
+
+  * the headline shape (65,536 fully connected six-box towers, S = 5, bench.py config 0): gated with random gates
+    against the ungated call, which takes the wide kernels there too — the cost of the gate itself (one multiply per
+    h2 and dh2pre element, pointer-form gathers in the gated kernels);
+  * batch 32 (the reference's training batch): the gated call's wide kernels against the ungated call's fused
+    small-batch path — the cost of the wide fallback.
+
+Alternating rounds (ungated, gated, ungated, …), `--calls` forward + loss-free backward pairs between two device
+events per round; reports each variant's per-round milliseconds, their min–max and the ratio of the minima. Prints
+one JSON line; `--out` also writes it to a file.
+
+    python tools/relation_gates_bench.py --out profiles/relation_gates_bench.json
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from spwgnn_amd import TowerBatch, data as D, engine as E, params as P  # noqa: E402
+
+
+def one_shape(args, towers, calls, math="x6"):
+    dev, S = "cuda:0", args.mp_steps
+    raw = D.synthetic_towers_fast(towers, args.nodes, seed=1000 + 97 * args.nodes)   # bench.py's towers
+    batch = TowerBatch.fully_connected((raw / D.RELATION_THRESHOLD).astype(np.float32), device=dev, nw_max=16)
+    flat = P.to_flat(P.glorot_uniform(0), device=dev)
+    gates = batch.edge_gates(torch.as_tensor(np.random.default_rng(5).uniform(0.25, 1.5, batch.n_edges).astype(np.float32),
+                                             device=dev))
+    run = E.RunConfig(S, training=True, dropout=0.1, seed=1, math=math)
+    dz = torch.as_tensor(np.random.default_rng(17).normal(0, 1e-3, batch.n_nodes).astype(np.float32), device=dev)
+    ws = {None: E.Workspace(dev), "gated": E.Workspace(dev)}
+    z = torch.empty(batch.n_nodes, dtype=torch.float32, device=dev)
+    grads = torch.empty_like(flat)
+
+    def step(kind):
+        g = gates if kind else None
+        E.forward(flat, batch, run, ws[kind], logits=z, gates=g)
+        E.backward(flat, batch, run, ws[kind], dz, grads=grads, gates=g)
+
+    times = {None: [], "gated": []}
+    for kind in (None, "gated"):
+        for _ in range(args.warmup):
+            step(kind)
+    for _ in range(args.rounds):
+        for kind in (None, "gated"):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            for _ in range(calls):
+                step(kind)
+            b.record()
+            torch.cuda.synchronize()
+            times[kind].append(a.elapsed_time(b) / calls)
+    assert bool(torch.isfinite(grads).all())
+    rnd = lambda xs: [round(x, 4) for x in xs]
+    return {"towers": towers, "n_nodes": batch.n_nodes, "n_eblocks": batch.n_eblocks, "math": math, "calls_per_round": calls,
+            "ungated_fused_path": E.fused_path(batch, run), "ungated_ms": rnd(times[None]), "gated_ms": rnd(times["gated"]),
+            "ungated_min_max": rnd([min(times[None]), max(times[None])]),
+            "gated_min_max": rnd([min(times["gated"]), max(times["gated"])]),
+            "ratio_of_minima": round(min(times["gated"]) / min(times[None]), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--towers", type=int, default=65536)
+    ap.add_argument("--small-towers", type=int, default=32)
+    ap.add_argument("--nodes", type=int, default=6)
+    ap.add_argument("--mp-steps", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--small-calls", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    res = {"tool": "relation_gates_bench", "device": torch.cuda.get_device_name(0), "nodes_per_tower": args.nodes,
+           "mp_steps": args.mp_steps, "rounds": args.rounds,
+           "runs": [one_shape(args, args.towers, args.calls), one_shape(args, args.small_towers, args.small_calls)]}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
