@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense; spwgnn_clip, spwgnn_adam_clipped, spwgnn_adam_clipped_dev, spwgnn_adam_lr_decayed, spwgnn_adam_lr_table_decay; spwgnn_forward_steps, spwgnn_backward_steps, spwgnn_step_weights, spwgnn_bce_steps; spwgnn_eval, spwgnn_eval_metrics; spwgnn_backward_relations; spwgnn_gates_supported, spwgnn_forward_gated, spwgnn_backward_gated); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
+#define SPWGNN_ABI_VERSION 8   /* 8: spwgnn_backward_inputs (+ added within 8: spwgnn_forward_state, spwgnn_backward_state; spwgnn_loss_weights, spwgnn_bce_weighted, spwgnn_bce_backward_weighted; SPWGNN_MATH_X3, spwgnn_math_products; SPWGNN_MATH_H3, spwgnn_math_products_bwd; spwgnn_plan_device, spwgnn_plan_device_positions, spwgnn_plan_device_dense; spwgnn_clip, spwgnn_adam_clipped, spwgnn_adam_clipped_dev, spwgnn_adam_lr_decayed, spwgnn_adam_lr_table_decay; spwgnn_forward_steps, spwgnn_backward_steps, spwgnn_step_weights, spwgnn_bce_steps; spwgnn_eval, spwgnn_eval_metrics; spwgnn_backward_relations; spwgnn_gates_supported, spwgnn_forward_gated, spwgnn_backward_gated; spwgnn_dropedge_gates, spwgnn_dropedge_keep_host; spwgnn_fused_path_gated); 7: spwgnn_da_stored_steps; 6: spwgnn_bce_backward; 5: spwgnn_team_max_blocks, spwgnn_host_device_ptr, spwgnn_plan_order, spwgnn_run.grads_early_event; 4: spwgnn_run.prologue; 3: spwgnn_batch.flags, receiver-block plans */
 
 #define SPWGNN_OK 0
 #define SPWGNN_E_ARG (-1)           /* bad argument (null pointer, negative size, …)          */
@@ -306,6 +306,7 @@ int32_t spwgnn_math_products_bwd(int32_t math);
 #define SPWGNN_K_PLAN_DEVICE 13 /* spwgnn_plan_device_positions / _dense's one launch (spwgnn_plan_device.prof_events) */
 #define SPWGNN_K_STATE 14      /* the layout launch of spwgnn_forward_state (P_S out) / spwgnn_backward_state (dstate in) */
 #define SPWGNN_K_REL_BWD 15    /* spwgnn_backward_relations' one launch */
+#define SPWGNN_K_DROPEDGE 16   /* spwgnn_dropedge_gates' one launch */
 
 /* Workspace bytes for (n_nodes, n_eblocks, mp_steps, training). */
 int64_t spwgnn_workspace_bytes(int32_t n_nodes, int32_t n_eblocks, int32_t mp_steps, int32_t training);
@@ -317,6 +318,10 @@ int64_t spwgnn_workspace_bytes(int32_t n_nodes, int32_t n_eblocks, int32_t mp_st
  * the same path as the plain calls of the batch: the fused loops run the seeded first step themselves
  * (their resource use is unchanged), so this answer holds for them too. */
 int32_t spwgnn_fused_path(const spwgnn_batch* batch, const spwgnn_run* run);
+/* (added within ABI 8) The same bits for a call of this batch and run WITH relation gates (spwgnn_forward_gated /
+ * spwgnn_backward_gated, below): a gated call takes the launches of the ungated one, in their gated forms.
+ * SPWGNN_E_SHAPE for a math spwgnn_gates_supported answers 0 to. spwgnn_fused_path itself is unchanged. */
+int32_t spwgnn_fused_path_gated(const spwgnn_batch* batch, const spwgnn_run* run);
 
 /* Batches of at most this many 32-row blocks (edge blocks, node blocks, wave-tiles; counted per
  * launch) run the latency-oriented team kernels, larger ones the wide kernels the large-batch step
@@ -432,9 +437,11 @@ int32_t spwgnn_backward_relations(const float* params, const spwgnn_batch* batch
  * the order of spwgnn_backward_relations' drel). A padding slot's value is never used: any bits there, NaN
  * included, leave every output unchanged.
  * gates == NULL: spwgnn_forward_state / spwgnn_backward_state bit for bit, with the same launches (the
- * team / fused small-batch path where it applies). With gates the call takes the wide kernels at every
- * batch size and the one-hot edge forward on a receiver-block plan; the team / fused forms and the
- * column-sum receiver-block kernel are not gated. Every plan kind (capacity, packed, device-filled with
+ * team / fused small-batch path where it applies). With gates the call takes the launches of the ungated call
+ * in their gated forms — the team kernels and the fused small-batch step loops included
+ * (spwgnn_fused_path_gated), with the results of the wide gated kernels bit for bit — except that a
+ * receiver-block plan runs the one-hot edge forward (the column-sum kernel is not gated), the wide gated kernels
+ * gather through 64-bit pointers, and a small batch's W2 gradient runs as its own launch. Every plan kind (capacity, packed, device-filled with
  * all-padding blocks, wave-tiles of up to 32 nodes), a null or non-null prop, with or without dprop /
  * state_out / dstate, training and inference, every spwgnn_da_stored_steps setting.
  * Maths: spwgnn_gates_supported(math) is 1 for X6, X3 and H3, 0 for F32 and BF16 — a gated call in those
@@ -455,6 +462,32 @@ int32_t spwgnn_backward_gated(const float* params, const spwgnn_batch* batch, co
                               const float* gates /* the forward's; NULL = ungated */,
                               const float* dlogits, const float* dstate /* as spwgnn_backward_state */,
                               float* grads, float* dprop, spwgnn_stream_t stream);
+
+/* DropEdge (added within ABI 8: new symbols only): the relation gates of a random edge subset,
+ * drawn per training step — the usual regulariser of a message-passing network, next to the feature dropout of
+ * Networks.py:77-78. One launch (kernel id SPWGNN_K_DROPEDGE), no workspace, no host synchronisation: capturable.
+ *   gates[k] = base[k] · (keep_k ? scale : 0)       for every edge slot k of the plan, base == NULL meaning 1,
+ *   scale    = 1/(1 − rate) in fp32 with SPWGNN_DROPEDGE_RESCALE, else 1,
+ *   keep_k   = mix32(rowkey(key, kind 3, tower, a, b) ^ 0) >= floor(rate·2^32)   (the feature dropout's key
+ *              functions with kind 3 and feature 0: independent of its two masks, kinds 1 and 2),
+ *   tower = node_tower[src_k], a = node_local[src_k], b = node_local[dst_k]; with SPWGNN_DROPEDGE_SYMMETRIC
+ *   (a, b) becomes (min, max): the two directions of a contact are kept or dropped together,
+ *   key = run->seed, or *run->seed_dev when set (a replayed step's device key word).
+ * The key names an edge by its tower's id and its two local node indices alone, so a tower's mask does not depend
+ * on plan order, packing, capacity padding, sharding or micro-batching. Every slot of gates [32·n_eblocks] (16-byte
+ * aligned, device fp32, the order of spwgnn_forward_gated's gates) is written, a padding slot (edge_src < 0 or
+ * edge_dst < 0) with +0 whatever base holds there. Of run only seed, seed_dev and the timing hook are read; of
+ * batch n_nodes, n_eblocks, edge_src, edge_dst, node_tower, node_local.
+ * SPWGNN_E_ARG before any device work: a null batch, run, gates or one of the four batch arrays, a misaligned
+ * pointer, an unknown flag bit, a rate that is NaN or outside [0, 1). rate 0 keeps every edge. */
+#define SPWGNN_DROPEDGE_SYMMETRIC 1
+#define SPWGNN_DROPEDGE_RESCALE 2
+int32_t spwgnn_dropedge_gates(const spwgnn_batch* batch, const spwgnn_run* run, float rate, int32_t flags,
+                              const float* base /* [32·n_eblocks], or NULL */,
+                              float* gates /* [32·n_eblocks], 16-byte aligned */, spwgnn_stream_t stream);
+/* The keep decision of one edge on the host (no device): 1 kept, 0 dropped, SPWGNN_E_ARG for a bad rate or flag.
+ * Only SPWGNN_DROPEDGE_SYMMETRIC changes the answer. */
+int32_t spwgnn_dropedge_keep_host(uint64_t key, uint32_t tower, uint32_t a, uint32_t b, float rate, int32_t flags);
 
 /* Keras binary_crossentropy on sigmoid(logits) (Networks.py:102), mean over n:
  * out3 = {loss, sum of correct (binary_accuracy numerator), n}; dlogits = dloss/dlogit.

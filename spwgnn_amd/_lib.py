@@ -102,6 +102,8 @@ class TowerLossC(C.Structure):
 K_EDGE_FWD, K_NODE_FWD, K_EDGE_BWD, K_NODE_BWD, K_ENC_EDGE, K_ENC_EDGE_BWD, K_WGRAD_W2, K_DA = 1, 2, 3, 4, 5, 6, 7, 8
 K_WGRAD_WS, K_ENC_NODE, K_ENC_NODE_BWD, K_INPUT_BWD, K_PLAN_DEVICE, K_STATE = 9, 10, 11, 12, 13, 14
 K_REL_BWD = 15
+K_DROPEDGE = 16
+DROPEDGE_SYMMETRIC, DROPEDGE_RESCALE = 1, 2   # spwgnn_dropedge_gates flags
 MATH_F32, MATH_X6, MATH_BF16, MATH_X3, MATH_H3 = 0, 1, 2, 3, 4
 E_ARG, E_WORKSPACE, E_NOTRAIN = -1, -4, -6   # SPWGNN_E_* statuses the bindings name
 E_SHAPE, E_RELATION, E_CAPACITY = -2, -3, -5
@@ -131,6 +133,7 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_plan_fill_recv": (i32, [i32, vp, vp, vp, vp, i32, C.POINTER(PlanSizes), vp, vp, vp, vp, vp]),
         "spwgnn_workspace_bytes": (i64, [i32, i32, i32, i32]),
         "spwgnn_fused_path": (i32, [C.POINTER(BatchC), C.POINTER(RunC)]),
+        "spwgnn_fused_path_gated": (i32, [C.POINTER(BatchC), C.POINTER(RunC)]),
         "spwgnn_team_max_blocks": (i32, [i32]),
         "spwgnn_da_stored_steps": (i32, [i32]),
         "spwgnn_math_products": (i32, [i32]),
@@ -150,6 +153,8 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_gates_supported": (i32, [i32]),
         "spwgnn_forward_gated": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp, vp]),
         "spwgnn_backward_gated": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp, vp, vp, vp]),
+        "spwgnn_dropedge_gates": (i32, [C.POINTER(BatchC), C.POINTER(RunC), f32, i32, vp, vp, vp]),
+        "spwgnn_dropedge_keep_host": (i32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, f32, i32]),
         "spwgnn_plan_device_positions": (i32, [C.POINTER(PlanDeviceC), vp, i32, f32, f32, vp]),
         "spwgnn_plan_device_dense": (i32, [C.POINTER(PlanDeviceC), vp, vp, i32, i32, vp]),
         "spwgnn_bce_scratch_bytes": (i64, [i64]),

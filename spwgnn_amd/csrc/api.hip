@@ -36,6 +36,16 @@ int32_t spwgnn_fused_path(const spwgnn_batch* batch, const spwgnn_run* run) {
     return (p.fwd_fused ? 1 : 0) | (run->training && p.bwd_fused ? 2 : 0);
 }
 
+// the same answer for a call of this batch and run with relation gates (spwgnn_forward_gated / _backward_gated)
+int32_t spwgnn_fused_path_gated(const spwgnn_batch* batch, const spwgnn_run* run) {
+    const int32_t stt = validate(batch, run);
+    if (stt) return stt;
+    if (!math_split32(run->math)) return SPWGNN_E_SHAPE;
+    const Path p = make_path(batch, run, make_ws(batch->n_nodes, batch->n_eblocks, run->mp_steps, run->training ? 1 : 0),
+                             nullptr, true);
+    return (p.fwd_fused ? 1 : 0) | (run->training && p.bwd_fused ? 2 : 0);
+}
+
 int32_t spwgnn_host_device_ptr(const void* host, void** dev) {
     if (!host || !dev) return SPWGNN_E_ARG;
     void* p = nullptr;
@@ -215,6 +225,49 @@ int32_t spwgnn_backward_relations(const float* params, const spwgnn_batch* batch
     a.drel_steps = drel_steps;
     const Prof prof{run, st};
     SPW_TIMED(prof, SPWGNN_K_REL_BWD, launch_rel_bwd(a, math_bwd(run->math), p.b16, p.n16, st));
+    return SPWGNN_OK;
+}
+
+// DropEdge. rate in [0, 1) → drop_keep's threshold, as set_dropout forms the feature dropout's
+static bool dropedge_thresh(float rate, uint32_t& thresh) {
+    if (!(rate >= 0.f && rate < 1.f)) return false;   // NaN included
+    thresh = (uint32_t)std::min(4294967295.0, std::floor((double)rate * 4294967296.0));
+    return true;
+}
+constexpr int32_t kDropEdgeFlags = SPWGNN_DROPEDGE_SYMMETRIC | SPWGNN_DROPEDGE_RESCALE;
+
+int32_t spwgnn_dropedge_keep_host(uint64_t key, uint32_t tower, uint32_t a, uint32_t b, float rate, int32_t flags) {
+    uint32_t thresh;
+    if (!dropedge_thresh(rate, thresh) || (flags & ~kDropEdgeFlags)) return SPWGNN_E_ARG;
+    return dropedge_keep(key, tower, a, b, (flags & SPWGNN_DROPEDGE_SYMMETRIC) != 0, thresh) ? 1 : 0;
+}
+
+int32_t spwgnn_dropedge_gates(const spwgnn_batch* batch, const spwgnn_run* run, float rate, int32_t flags,
+                              const float* base, float* gates, spwgnn_stream_t stream) {
+    if (!batch || !run || !gates) return SPWGNN_E_ARG;
+    DropEdgeArgs a{};
+    if (!dropedge_thresh(rate, a.thresh) || (flags & ~kDropEdgeFlags)) return SPWGNN_E_ARG;
+    if (batch->n_nodes < 1 || batch->n_eblocks < 1 || batch->n_eblocks > (INT32_MAX >> 5)) return SPWGNN_E_SHAPE;
+    if (!batch->edge_src || !batch->edge_dst || !batch->node_tower || !batch->node_local) return SPWGNN_E_ARG;
+    const auto mis = [](const void* q, uintptr_t al) { return reinterpret_cast<uintptr_t>(q) % al != 0; };
+    if (mis(gates, 16) || mis(base, 4) || mis(batch->edge_src, 4) || mis(batch->edge_dst, 4) ||
+        mis(batch->node_tower, 4) || mis(batch->node_local, 4) || mis(run->seed_dev, 8))
+        return SPWGNN_E_ARG;
+    a.slots = (int64_t)batch->n_eblocks * 32;
+    a.n_nodes = batch->n_nodes;
+    a.esrc = batch->edge_src;
+    a.edst = batch->edge_dst;
+    a.node_tower = batch->node_tower;
+    a.node_local = batch->node_local;
+    a.base = base;
+    a.gates = gates;
+    a.scale = (flags & SPWGNN_DROPEDGE_RESCALE) ? 1.0f / (1.0f - rate) : 1.0f;
+    a.symmetric = (flags & SPWGNN_DROPEDGE_SYMMETRIC) ? 1 : 0;
+    a.seed = run->seed;
+    a.seed_dev = run->seed_dev;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const Prof prof{run, st};
+    SPW_TIMED(prof, SPWGNN_K_DROPEDGE, launch_dropedge(a, st));
     return SPWGNN_OK;
 }
 

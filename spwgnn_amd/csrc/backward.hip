@@ -313,7 +313,9 @@ static int32_t run_wgrad(WgRun& q, const WgSpec& g) {
         }
         // a small x6 batch: the W2 gradient runs inside the batched weight-gradient launch
         // (the copy in the batched launch is the descriptor form: the pointer form runs as its own launch)
-        const bool w2_in_batch = ws && math_split32(math) && q.wsb && p.team_edges && a.gather_desc && !p.diag.no_w2_merge;
+        // (a gated call's too: k_w2grad_ws<…, GATE> is the pointer form)
+        const bool w2_in_batch = ws && math_split32(math) && q.wsb && p.team_edges && a.gather_desc && !a.gates &&
+                                 !p.diag.no_w2_merge;
         const bool timed = g.recompute && !w2_in_batch;
         if (timed) SPW_CHECK(q.prof.before(SPWGNN_K_WGRAD_W2));
         if (w2_in_batch) {
@@ -565,7 +567,6 @@ static int32_t reduce(const ReduceBatch& rb, int t_lo, int t_hi, const BceArgs* 
 int32_t run_backward(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, char* base, const BwdCall& call,
                      hipStream_t st) {
     const Ctx c{w, base, r->math != MATH_F32};
-    const WideCall wide(call.gates != nullptr);   // a gated call: the wide kernels at every batch size (§3zz)
     const Path p = make_path(b, r, w, &call);
     const int S = r->mp_steps;
     const Prof prof{r, st};
@@ -603,7 +604,7 @@ int32_t run_backward(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, ch
         }
         fa.tail = tl;
         fa.has_tail = call.dprop != nullptr;
-        fa.eb = edge_bwd_args(c, b, p, 0);
+        fa.eb = edge_bwd_args(c, b, p, 0, call.gates);
         fa.da = da;
         fa.eeb = eeb;
         fa.enb = enb;

@@ -158,8 +158,7 @@ static NodeFwdArgs node_fwd_args(const Ctx& c, const spwgnn_batch* b, const Path
 int32_t run_forward(const float* params, const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, char* base,
                     const FwdCall& call, hipStream_t st) {
     const Ctx c{w, base, r->math != MATH_F32};
-    const WideCall wide(call.gates != nullptr);   // a gated call: the wide kernels at every batch size (§3zz)
-    const Path p = make_path(b, r, w);
+    const Path p = make_path(b, r, w, nullptr, call.gates != nullptr);
     if (int32_t e = prep(c, params, r, st)) return e;
     const EncNodeArgs en = enc_node_args(c, b, r, p);
     const EncEdgeArgs ee = enc_edge_args(c, b, r, p);
@@ -170,7 +169,7 @@ int32_t run_forward(const float* params, const spwgnn_batch* b, const spwgnn_run
         FwdFusedArgs fa{};
         fa.ee = ee;
         fa.en = en;
-        fa.ef = edge_fwd_args(c, b, p, 0);
+        fa.ef = edge_fwd_args(c, b, p, 0, call.gates);
         fa.nf = node_fwd_args(c, b, p, call, 0);
         fa.S = S;
         fa.training = r->training;

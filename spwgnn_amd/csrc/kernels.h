@@ -547,6 +547,28 @@ struct RelBwdArgs {
 };
 // math: the backward's (math_bwd of the run's); b16 / n16: the run's storage (Path)
 hipError_t launch_rel_bwd(const RelBwdArgs& a, int math, bool b16, bool n16, hipStream_t st);
+// k_dropedge (kernels_rel.hip): a DropEdge mask as relation gates, one thread per edge slot
+struct DropEdgeArgs {
+    int64_t slots;                   // 32·n_eblocks
+    int n_nodes;
+    const int32_t *esrc, *edst;      // [slots] global sender / receiver, -1 = padding
+    const int32_t *node_tower, *node_local;   // [n_nodes] the key's tower id and local node index
+    const float* base;               // [slots] weights multiplied into the mask, or null = 1
+    float* gates;                    // [slots] out: every slot written, a padding slot with 0
+    uint32_t thresh;                 // floor(rate·2^32): drop_keep's threshold
+    float scale;                     // a kept edge's gate before base: 1/(1 − rate), or 1
+    int symmetric;                   // the key takes (min, max) of the two local indices
+    uint64_t seed;
+    const uint64_t* seed_dev;        // non-null: the key is read from device memory (replayable steps)
+};
+hipError_t launch_dropedge(const DropEdgeArgs& a, hipStream_t st);
+// the key's keep decision (host and device): kind 3, feature 0 of the row key
+constexpr uint32_t kDropEdgeKind = 3u;
+__host__ __device__ __forceinline__ bool dropedge_keep(uint64_t key, uint32_t tower, uint32_t la, uint32_t lb,
+                                                       bool symmetric, uint32_t thresh) {
+    const uint32_t a = symmetric && lb < la ? lb : la, b = symmetric && lb < la ? la : lb;
+    return drop_keep(drop_row_key(key, kDropEdgeKind, tower, a, b), 0u, thresh);
+}
 // k_plan_device (kernels_plan.hip): the data-dependent arrays of a capacity plan, filled on the device
 struct PlanDevArgs {
     int n_wtiles, n_eblocks, n_nodes, n_towers;
@@ -576,10 +598,10 @@ hipError_t launch_plan_device(const PlanDevArgs& a, bool dense, hipStream_t st);
 #endif
 constexpr int kTeamMaxBlocks = SPWGNN_TEAM_MAX_BLOCKS;
 bool team_blocks(int n_blocks);   // 32-row blocks of the launch (edge or node blocks)
-// A gated call (relation gates) takes the wide kernels at every batch size: while a WideCall
-// with on = true lives on the calling thread, team_blocks answers false there — to make_path and to every
-// launcher of the call — as spwgnn_team_max_blocks(0) makes it answer for the whole process. The process-wide
-// limit is not touched, and other threads' calls do not see it.
+// A call that must take the wide kernels at every batch size holds a WideCall: while one with on = true lives on
+// the calling thread, team_blocks answers false there — to make_path and to every launcher of the call — as
+// spwgnn_team_max_blocks(0) makes it answer for the whole process. The process-wide limit is not touched, and
+// other threads' calls do not see it. (Gated calls held one until the team / fused kernels took gates, §3zz.)
 struct WideCall {
     explicit WideCall(bool on);
     ~WideCall();

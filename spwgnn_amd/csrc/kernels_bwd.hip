@@ -1092,9 +1092,10 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 }
 
 hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st) {
-    if (a.gates) {   // relation gates: the wide kernels of the split maths alone, the pointer form of the G3 rows
-        if (!math_split32(math) || a.n16 || team_blocks(a.n_wtiles) || (a.dh1_slab && (a.nw_max > 16 || !a.no_dA)))
-            return hipErrorInvalidValue;
+    if (a.gates) {   // relation gates: the split maths alone; team kernels, or the wide ones' pointer form of the G3 rows
+        if (!math_split32(math) || a.n16 || (a.dh1_slab && (a.nw_max > 16 || !a.no_dA))) return hipErrorInvalidValue;
+        if (a.nw_max <= 16 && a.no_dA && team_blocks(a.n_wtiles))   // small batches
+            return a.dh1_slab ? hipErrorInvalidValue : launch_edge_bwd_team(a, math, st);
         if (a.nw_max <= 16) {
             if (!a.no_dA) return hipErrorInvalidValue;   // dA is rebuilt after the step loop (k_dA_x6<GATE>)
             const dim3 g(edge_grid(a.n_wtiles, 8)), b(512);
@@ -1391,9 +1392,10 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 }
 
 hipError_t launch_dA(const DaArgs& a, int math, hipStream_t st) {
-    if (a.gates) {   // relation gates: the wide rebuild of the split maths alone
-        if (!math_split32(math) || a.b16 || team_blocks(a.n_eblocks) || (a.n_stored > 0 && (a.n_stored >= a.S || !a.slab)))
+    if (a.gates) {   // relation gates: the rebuild of the split maths alone, team or wide
+        if (!math_split32(math) || a.b16 || (a.n_stored > 0 && (a.n_stored >= a.S || !a.slab || team_blocks(a.n_eblocks))))
             return hipErrorInvalidValue;
+        if (team_blocks(a.n_eblocks)) return launch_dA_team(a, math, st);
         const dim3 g(edge_grid(a.n_eblocks, 8)), b(512);
         if (a.n_stored > 0) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_dA_x6<NP, false, true, true>), g, b, 0, st, a));
         else SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_dA_x6<NP, false, false, true>), g, b, 0, st, a));

@@ -1547,8 +1547,9 @@ static void launch_edge_fwd16(const EdgeFwdArgs& a, hipStream_t st) {
 hipError_t launch_edge_fwd(const EdgeFwdArgs& a, int math, hipStream_t st) {
     if (a.nw_max > kNwMaxLimit) return hipErrorInvalidValue;  // one-hot rows: ≤ 32 nodes per wave-tile
     if ((a.uv16 == kUvB16) != (a.n16 != 0)) return hipErrorInvalidValue;   // bf16 U, V: the N16 kernel reads them
-    if (a.gates) {   // relation gates: the wide one-hot kernels of the split maths alone (no team, no column-sum form)
-        if (!math_split32(math) || a.n16 || a.a_b16 || a.recv_blocks || team_blocks(a.n_wtiles)) return hipErrorInvalidValue;
+    if (a.gates) {   // relation gates: the one-hot kernels of the split maths alone (team or wide; no column-sum form)
+        if (!math_split32(math) || a.n16 || a.a_b16 || a.recv_blocks) return hipErrorInvalidValue;
+        if (a.nw_max <= 16 && team_blocks(a.n_wtiles)) return launch_edge_fwd_team(a, math, st);   // small batches
         SPW_SPLIT32F(math, NP, (launch_edge_fwd_gated<NP>(a, st)));
         return hipGetLastError();
     }

@@ -268,4 +268,32 @@ hipError_t launch_rel_bwd(const RelBwdArgs& a, int math, bool b16, bool n16, hip
     return hipGetLastError();
 }
 
+// DropEdge: the relation gates of one training step's random edge subset. Thread e is edge
+// slot e: gates[e] = base[e] · (keep ? scale : 0), keep drawn from the run's dropout key with kind 3 on (tower id,
+// sender's local index, receiver's local index) — in ascending order under `symmetric`, so the two directions of
+// a contact share one draw. The key names the edge by tower id and local indices alone: a tower's mask does not
+// depend on where the plan put its edges. A padding slot (an index outside [0, n_nodes)) reads no node row and no
+// base entry and gets +0. Reads esrc, edst, base at e < slots and node rows at checked indices; writes gates[e].
+__global__ __launch_bounds__(256) void k_dropedge(DropEdgeArgs a) {
+    const uint64_t key = run_seed(a);
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.slots; e += (int64_t)gridDim.x * 256) {
+        const int s = a.esrc[e], d = a.edst[e];
+        float g = 0.f;
+        if (s >= 0 && d >= 0 && s < a.n_nodes && d < a.n_nodes) {
+            const bool keep = dropedge_keep(key, (uint32_t)a.node_tower[s], (uint32_t)a.node_local[s],
+                                            (uint32_t)a.node_local[d], a.symmetric != 0, a.thresh);
+            g = keep ? a.scale : 0.f;
+            if (a.base) g = a.base[e] * g;
+        }
+        a.gates[e] = g;
+    }
+}
+
+hipError_t launch_dropedge(const DropEdgeArgs& a, hipStream_t st) {
+    if (a.slots <= 0) return hipSuccess;
+    const dim3 g((unsigned)std::min<int64_t>((a.slots + 255) / 256, 1024)), b(256);
+    hipLaunchKernelGGL(k_dropedge, g, b, 0, st, a);
+    return hipGetLastError();
+}
+
 }  // namespace spw

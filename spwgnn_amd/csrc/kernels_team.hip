@@ -753,9 +753,12 @@ __global__ __launch_bounds__(256, 1) void k_node_bwd_team(NodeBwdArgs a) {
 // after a barrier every wave runs its output tile's ten k-blocks on it (team_lds_gemm). One memory
 // latency per block instead of one per k-block, and each operand element loaded once, not 5×.
 // dh2pre = G3[receiver] ⊙ [h2 > 0] (the edge backward and the dA rebuild), as k_edge_bwd_x6 builds it.
-template <int NP>
+// GATE (relation gates): dh2pre_k = gw · [h2_k > 0] ⊙ G3[dst_k], gw the gate of the lane's edge (lane
+// i is edge i; the caller loads it with the receiver index, 0 on a padding slot), multiplied in before the split
+// as k_edge_bwd_x6<GATE> / k_dA_x6<GATE> do
+template <int NP, bool GATE = false>
 __device__ __forceinline__ void team_dh2_kblocks(const float* __restrict__ G3, const uint32_t* __restrict__ m2row,
-                                                 int d, int n0, int T, int lane, uint4* buf) {
+                                                 int d, int n0, int T, int lane, uint4* buf, float gw = 0.f) {
     const int h = lane >> 5, i = lane & 31;
     const bool valid = d >= 0;
     uint32_t w[5];
@@ -783,6 +786,10 @@ __device__ __forceinline__ void team_dh2_kblocks(const float* __restrict__ G3, c
             xv[4 * c + 1] = mask_bit(gv.y, bits, 1);
             xv[4 * c + 2] = mask_bit(gv.z, bits, 2);
             xv[4 * c + 3] = mask_bit(gv.w, bits, 3);
+        }
+        if constexpr (GATE) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xv[e] *= gw;
         }
         uint32_t sp[3][4];
 #pragma unroll
@@ -830,7 +837,10 @@ __device__ __forceinline__ f32x16 team_lds_gemm(const uint4* buf, const uint4 (&
 // the one-hot receiver sum of tile T are k_edge_fwd_x6's (mfma32_x6 / NodeSum16X6), so H2s and both
 // masks are bit-identical. Wave T writes the h2 > 0 word of tile T (wave 0 also the padding words).
 // hs: two buffers of 10 k-blocks × 3 parts × 64 lanes (uint4), 60 KiB, blocks alternate.
-template <Np NPT, bool AB16>
+// GATE (relation gates): as k_edge_fwd_x6<GATE> — register r of tile T, edge rho(r, h) of the block
+// with its degree column, is scaled by EdgeFwdArgs::gates[32·blk + rho(r, h)] after the h2 > 0 words are taken
+// (the stored bits stay the ungated h2's) and before the receiver sum; a padding slot's gate is masked to +0
+template <Np NPT, bool AB16, bool GATE = false>
 __device__ __forceinline__ void edge_fwd_team_body(const EdgeFwdArgs& a, int wt, uint4* hs, float* h2l = nullptr) {
     constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     const int lane = opaque_lane(), h = lane >> 5, i = lane & 31;
@@ -953,6 +963,20 @@ __device__ __forceinline__ void edge_fwd_team_body(const EdgeFwdArgs& a, int wt,
 #pragma unroll
                 for (int k = 0; k < 4; ++k) m2row[64 * k + lane] = t7 == T ? mw2[k] : 0u;
         }
+        if constexpr (GATE) {
+            // the block's 32 gates sit at a wave-uniform address (scalar loads); a lane picks its half's. The
+            // rounded fp32 product is what the receiver sum splits: behind an opaque copy, so the multiply is not
+            // contracted into the split's residual (k_edge_fwd_x6<GATE>, §3zz)
+            const float* __restrict__ gr = a.gates + (int64_t)__builtin_amdgcn_readfirstlane(blk) * 32;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float w0 = gr[rho(r, 0)], w1 = gr[rho(r, 1)];
+                const float wr = mask_bit(h ? w1 : w0, vh, rho(r, 0));
+                float v = acc[r] * wr;
+                asm volatile("" : "+v"(v));
+                acc[r] = v;
+            }
+        }
         TEAM_STAMP(20);
         // receiver sum of tile T (NodeSum16X6::add for t = T)
         {
@@ -1024,11 +1048,11 @@ constexpr int kTeamHsU4 = 2 * 10 * 3 * 64;   // edge bodies' split-operand buffe
 // LDS of a launch that runs edge bodies and five-tile exchanges (TeamAct<5>) one after the other
 template <int NP>
 constexpr int kTeamLdsU4 = kTeamHsU4 > 2 * kTeamEdge * 2 * NP * 64 ? kTeamHsU4 : 2 * kTeamEdge * 2 * NP * 64;
-template <Np NPT, bool AB16>
+template <Np NPT, bool AB16, bool GATE = false>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_edge_fwd_team(EdgeFwdArgs a) {
     constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     __shared__ uint4 hs[kTeamHsU4];
-    if ((int)blockIdx.x < a.n_wtiles) edge_fwd_team_body<NPT, AB16>(a, blockIdx.x, hs);
+    if ((int)blockIdx.x < a.n_wtiles) edge_fwd_team_body<NPT, AB16, GATE>(a, blockIdx.x, hs);
 }
 
 // ---- a small batch's forward step loop in one launch (FwdFusedArgs, kernels.h) ----
@@ -1052,7 +1076,8 @@ __device__ __forceinline__ void opaque(T*& p) {
 // STEPS (spwgnn_forward_steps, §3zr): every step stores its logit row, step s at logits + s·logit_step.
 // A template parameter, like the backward's: the loops are at their register limit and sensitive to
 // what the step prologue computes (§3zl), so spwgnn_forward keeps the instantiations it had
-template <bool TRAIN, Np NPT, bool AB16, bool STEPS = false>
+// GATE: the edge side of every step is edge_fwd_team_body<…, GATE> on a.ef.gates (one gate per edge, every step)
+template <bool TRAIN, Np NPT, bool AB16, bool STEPS = false, bool GATE = false>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_fwd_fused_team(FwdFusedArgs a) {
     constexpr int NP = NPT;   // the part count as a plain constant (Np: device_common.h)
     __shared__ uint4 act_s[kTeamLdsU4<NP>];
@@ -1078,7 +1103,7 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_fwd_fused_team(FwdFusedArgs 
         if (ef.mask1) ef.mask1 += s * a.m1_step;
         if (ef.mask2) ef.mask2 += s * a.m2_step;
         if (s == 0) TEAM_STAMP(11);
-        edge_fwd_team_body<NPT, AB16>(ef, wt, act_s, h2l);
+        edge_fwd_team_body<NPT, AB16, GATE>(ef, wt, act_s, h2l);
         if (s == 0) TEAM_STAMP(12);
         __syncthreads();   // H2s of step s
         NodeFwdArgs nf = a.nf;
@@ -1121,7 +1146,8 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_fwd_fused_team(FwdFusedArgs 
 // (block, tile T, register, lane) across the steps, s = S−1 first (dacc_first) — the rebuild's order
 // and products, so the same bits as k_dA_team's
 constexpr int kTeamDaBlocks = 4;
-template <int NP>
+// GATE: dh2pre carries EdgeBwdArgs::gates (team_dh2_kblocks<NP, GATE>); the LDS dA sums with it
+template <int NP, bool GATE = false>
 __device__ __forceinline__ void edge_bwd_team_body(const EdgeBwdArgs& a, int wt, uint4* hs, float* dacc = nullptr,
                                                    bool dacc_first = false) {
     const int lane = opaque_lane(), h = lane >> 5, i = lane & 31;
@@ -1141,7 +1167,9 @@ __device__ __forceinline__ void edge_bwd_team_body(const EdgeBwdArgs& a, int wt,
         const int64_t e = (int64_t)blk * 32 + i;
         const int d = a.edst[e], s_ = a.esrc[e];
         const uint32_t m1w = a.mask1[(int64_t)blk * kLdE + i + 32 * T];
-        team_dh2_kblocks<NP>(a.G3, a.mask2 + (int64_t)blk * kM2Blk, d, n0, T, lane, buf);
+        float gw = 0.f;
+        if constexpr (GATE) gw = d >= 0 ? a.gates[e] : 0.f;
+        team_dh2_kblocks<NP, GATE>(a.G3, a.mask2 + (int64_t)blk * kM2Blk, d, n0, T, lane, buf, gw);
         team_sync();   // the block's split dh2pre (the other buffer is free)
         f32x16 acc = team_lds_gemm<NP>(buf, wf, lane);
         // dh1pre = dh1 ⊙ [h1 > 0]  (C layout: lane = feature 32T+i, rows = edges rho(r,h))
@@ -1205,15 +1233,16 @@ __device__ __forceinline__ void edge_bwd_team_body(const EdgeBwdArgs& a, int wt,
         }
     }
 }
-template <int NP>
+template <int NP, bool GATE = false>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_edge_bwd_team(EdgeBwdArgs a) {
     __shared__ uint4 hs[kTeamHsU4];
-    if ((int)blockIdx.x < a.n_wtiles) edge_bwd_team_body<NP>(a, blockIdx.x, hs);
+    if ((int)blockIdx.x < a.n_wtiles) edge_bwd_team_body<NP, GATE>(a, blockIdx.x, hs);
 }
 
 // ---- dA = Σ_s dh1pre_s (k_dA_x6), team form: five waves per 32-edge block, wave T owns feature
 // tile T; the same products, per-accumulator order and step order (S−1 first) as k_dA_x6.
-template <int NP, bool B16>
+// GATE: every rebuilt step's dh2pre carries DaArgs::gates (one value per lane, loaded once per block)
+template <int NP, bool B16, bool GATE = false>
 __device__ __forceinline__ void dA_team_body(const DaArgs& a, int blk, uint4* hs) {
     const int lane = opaque_lane(), h = lane >> 5, i = lane & 31;
     const int T = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1223,11 +1252,14 @@ __device__ __forceinline__ void dA_team_body(const DaArgs& a, int blk, uint4* hs
 #pragma unroll
         for (int p = 0; p < NP; ++p) wf[kb][p] = a.x_w2t[((kb * 5 + T) * 3 + p) * 64 + lane];
     const int d = a.edst[(int64_t)blk * 32 + i];
+    float gw = 0.f;
+    if constexpr (GATE) gw = d >= 0 ? a.gates[(int64_t)blk * 32 + i] : 0.f;
     f32x16 dacc = zero16();
     for (int s = a.S - 1; s >= 0; --s) {
         uint4* const buf = hs + (s & 1) * (10 * 3 * 64);
         const uint32_t m1w = a.mask1[s * a.m1_step + (int64_t)blk * kLdE + i + 32 * T];
-        team_dh2_kblocks<NP>(a.G3 + s * a.g3_step, a.mask2 + s * a.m2_step + (int64_t)blk * kM2Blk, d, 0, T, lane, buf);
+        team_dh2_kblocks<NP, GATE>(a.G3 + s * a.g3_step, a.mask2 + s * a.m2_step + (int64_t)blk * kM2Blk, d, 0, T, lane,
+                                   buf, gw);
         team_sync();   // step s's split dh2pre (the other buffer is free)
         const f32x16 acc = team_lds_gemm<NP>(buf, wf, lane);
         const uint32_t mh = m1w >> (4 * h);
@@ -1244,10 +1276,10 @@ __device__ __forceinline__ void dA_team_body(const DaArgs& a, int blk, uint4* hs
         for (int r = 0; r < 16; ++r) dArow[rho(r, h) * kLdE + 32 * T] = dacc[r];
     }
 }
-template <int NP, bool B16>
+template <int NP, bool B16, bool GATE = false>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_dA_team(DaArgs a) {
     __shared__ uint4 hs[kTeamHsU4];
-    if ((int)blockIdx.x < a.n_eblocks) dA_team_body<NP, B16>(a, blockIdx.x, hs);
+    if ((int)blockIdx.x < a.n_eblocks) dA_team_body<NP, B16, GATE>(a, blockIdx.x, hs);
 }
 
 // ---- object-encoder backward (k_enc_node_bwd_x6), team form: four waves per 32-node block, wave T
@@ -1324,7 +1356,8 @@ static_assert(sizeof(uint4) * kTeamLdsU4<3> + sizeof(float) * kTeamDaBlocks * 5 
 #error "libspwgnn_hip targets gfx950 (160 KiB LDS per CU): the fused small-batch backward needs it"
 #endif
 // STEPS (spwgnn_backward_steps, §3zr): step s reads its own cotangent row nb.dlogits + s·dl_step
-template <int NP, bool B16, bool STEPS = false>
+// GATE: the edge bodies of the loop and the dA rebuilds are the gated ones (a.eb.gates, a.da.gates: one tensor)
+template <int NP, bool B16, bool STEPS = false, bool GATE = false>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_bwd_fused_team(BwdFusedArgs a) {
     __shared__ uint4 act_s[kTeamLdsU4<NP>];
     __shared__ float dacc_s[kTeamDaBlocks * 5 * 16 * 64];   // 80 KiB: dA of ≤ 4 blocks across the steps
@@ -1367,7 +1400,7 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_bwd_fused_team(BwdFusedArgs 
         eb.G3 = nb.G3;
         eb.dU += sE;
         eb.dV += sE;
-        edge_bwd_team_body<NP>(eb, wt, act_s, da_loop ? dacc_s : nullptr, first);
+        edge_bwd_team_body<NP, GATE>(eb, wt, act_s, da_loop ? dacc_s : nullptr, first);
         __syncthreads();   // dU, dV of step s
     }
     if (a.has_tail) node_bwd_team_body<NP, 5>(a.tail, R, act_s);   // dP0 (reads only)
@@ -1389,14 +1422,14 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_bwd_fused_team(BwdFusedArgs 
         }
     } else if (a.dA_in_loop) {   // a tile of more blocks: the rebuild, here
         for (int b = 0; b < info.y; ++b) {
-            dA_team_body<NP, B16>(a.da, info.x + b, act_s);
+            dA_team_body<NP, B16, GATE>(a.da, info.x + b, act_s);
             __syncthreads();   // its last operand buffer may be the next block's first
         }
     }
     if (!a.encoders) return;   // else k_bwd_enc_pair_team runs the rest, edge and node side by side
     if (!a.dA_in_loop) {
         for (int b = 0; b < info.y; ++b) {
-            dA_team_body<NP, B16>(a.da, info.x + b, act_s);
+            dA_team_body<NP, B16, GATE>(a.da, info.x + b, act_s);
             __syncthreads();   // the block's dA rows; its last operand buffer may be the next block's first
         }
     }
@@ -1410,14 +1443,14 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_bwd_fused_team(BwdFusedArgs 
 // After the fused step loop: workgroups [0, n_eblocks) rebuild dA of their block and run the
 // relation-encoder backward on it, the others the object-encoder backward of a 32-node block —
 // independent, so side by side (as the forward's k_enc_pair_team) instead of one after the other.
-template <int NP, bool B16>
+template <int NP, bool B16, bool GATE = false>
 __global__ __launch_bounds__(64 * kTeamEdge) void k_bwd_enc_pair_team(DaArgs da, EncEdgeBwdArgs eeb, EncNodeBwdArgs enb,
                                                                     int with_dA) {
     __shared__ uint4 act_s[kTeamLdsU4<NP>];
     const int blk = blockIdx.x;
     if (blk < da.n_eblocks) {
         if (with_dA) {   // else the fused backward left dA in place
-            dA_team_body<NP, B16>(da, blk, act_s);
+            dA_team_body<NP, B16, GATE>(da, blk, act_s);
             __syncthreads();   // the block's dA rows, written feature tile by feature tile
         }
         enc_edge_bwd_team_body<NP, B16>(eeb, blk, act_s);
@@ -1451,6 +1484,11 @@ bool team_blocks(int n_blocks) {
 hipError_t launch_edge_fwd_team(const EdgeFwdArgs& a, int math, hipStream_t st) {
     if (a.nw_max > 16 || a.uv16 == kUvB16) return hipErrorInvalidValue;   // team kernels: fp32 U, V
     const dim3 g(a.n_wtiles), b(64 * kTeamEdge);
+    if (a.gates) {   // relation gates: the split maths, fp32 rows
+        if (!math_split32(math) || a.a_b16) return hipErrorInvalidValue;
+        SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_edge_fwd_team<NP, false, true>), g, b, 0, st, a));
+        return hipGetLastError();
+    }
     if (math == MATH_BF16) {
         if (a.a_b16) hipLaunchKernelGGL((k_edge_fwd_team<1, true>), g, b, 0, st, a);
         else hipLaunchKernelGGL((k_edge_fwd_team<1, false>), g, b, 0, st, a);
@@ -1464,6 +1502,11 @@ hipError_t launch_edge_fwd_team(const EdgeFwdArgs& a, int math, hipStream_t st) 
 hipError_t launch_edge_bwd_team(const EdgeBwdArgs& a, int math, hipStream_t st) {
     if (a.nw_max > 16 || !a.no_dA) return hipErrorInvalidValue;
     const dim3 g(a.n_wtiles), b(64 * kTeamEdge);
+    if (a.gates) {
+        if (!math_split32(math)) return hipErrorInvalidValue;
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_bwd_team<NP, true>), g, b, 0, st, a));
+        return hipGetLastError();
+    }
     if (math == MATH_BF16) hipLaunchKernelGGL((k_edge_bwd_team<1>), g, b, 0, st, a);
     else if (math_split32(math)) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_edge_bwd_team<NP>), g, b, 0, st, a));
     else return hipErrorInvalidValue;
@@ -1471,6 +1514,11 @@ hipError_t launch_edge_bwd_team(const EdgeBwdArgs& a, int math, hipStream_t st) 
 }
 hipError_t launch_dA_team(const DaArgs& a, int math, hipStream_t st) {
     const dim3 g(a.n_eblocks), b(64 * kTeamEdge);
+    if (a.gates) {
+        if (!math_split32(math) || a.b16) return hipErrorInvalidValue;
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_dA_team<NP, false, true>), g, b, 0, st, a));
+        return hipGetLastError();
+    }
     if (math == MATH_BF16 && a.b16) hipLaunchKernelGGL((k_dA_team<1, true>), g, b, 0, st, a);
     else if (math == MATH_BF16) hipLaunchKernelGGL((k_dA_team<1, false>), g, b, 0, st, a);
     else if (math_split32(math)) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_dA_team<NP, false>), g, b, 0, st, a));
@@ -1532,6 +1580,12 @@ hipError_t launch_fwd_fused_team(const FwdFusedArgs& a, int math, bool train, hi
         a.nf.uv16 == kUvB16 || a.ef.uv16 == kUvB16)
         return hipErrorInvalidValue;
     const dim3 g(a.ef.n_wtiles), b(64 * kTeamEdge);
+    if (a.ef.gates) {   // relation gates: the split maths, fp32 rows, the last step's logits (STEPS stays ungated)
+        if (a.logit_step || !math_split32(math) || a.ee.b16) return hipErrorInvalidValue;
+        if (train) SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_fwd_fused_team<true, NP, false, false, true>), g, b, 0, st, a));
+        else SPW_SPLIT32F(math, NP, hipLaunchKernelGGL((k_fwd_fused_team<false, NP, false, false, true>), g, b, 0, st, a));
+        return hipGetLastError();
+    }
     if (a.logit_step) {   // per-step logit rows: the STEPS instantiations
         if (math == MATH_BF16) {
             if (train && a.ee.b16) hipLaunchKernelGGL((k_fwd_fused_team<true, 1, true, true>), g, b, 0, st, a);
@@ -1565,6 +1619,11 @@ hipError_t launch_bwd_fused_team(const BwdFusedArgs& a, int math, hipStream_t st
         return hipErrorInvalidValue;
     const dim3 g(a.eb.n_wtiles), b(64 * kTeamEdge);
     if (!a.nb.dlogits || (a.dl_step && a.nb.bce_logits)) return hipErrorInvalidValue;
+    if (a.eb.gates || a.da.gates) {   // relation gates: the split maths, fp32 rows, one cotangent row
+        if (a.eb.gates != a.da.gates || a.dl_step || !math_split32(math) || a.da.b16) return hipErrorInvalidValue;
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_bwd_fused_team<NP, false, false, true>), g, b, 0, st, a));
+        return hipGetLastError();
+    }
     if (a.dl_step) {   // per-step cotangent rows: the STEPS instantiations
         if (math == MATH_BF16 && a.da.b16) hipLaunchKernelGGL((k_bwd_fused_team<1, true, true>), g, b, 0, st, a);
         else if (math == MATH_BF16) hipLaunchKernelGGL((k_bwd_fused_team<1, false, true>), g, b, 0, st, a);
@@ -1583,6 +1642,11 @@ hipError_t launch_bwd_enc_pair_team(const DaArgs& da, const EncEdgeBwdArgs& eeb,
     if (!team_blocks(da.n_eblocks) || !team_blocks((enb.n_nodes + 31) / 32) || da.b16 != eeb.b16 || !enb.wo1ct)
         return hipErrorInvalidValue;
     const dim3 g(da.n_eblocks + (enb.n_nodes + 31) / 32), b(64 * kTeamEdge);
+    if (da.gates && with_dA) {   // the rebuild here is the gated one (without it the kernel reads no gate)
+        if (!math_split32(math) || da.b16) return hipErrorInvalidValue;
+        SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_bwd_enc_pair_team<NP, false, true>), g, b, 0, st, da, eeb, enb, with_dA));
+        return hipGetLastError();
+    }
     if (math == MATH_BF16 && da.b16) hipLaunchKernelGGL((k_bwd_enc_pair_team<1, true>), g, b, 0, st, da, eeb, enb, with_dA);
     else if (math == MATH_BF16) hipLaunchKernelGGL((k_bwd_enc_pair_team<1, false>), g, b, 0, st, da, eeb, enb, with_dA);
     else if (math_split32(math) && !da.b16) SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_bwd_enc_pair_team<NP, false>), g, b, 0, st, da, eeb, enb, with_dA));

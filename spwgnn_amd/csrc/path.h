@@ -57,8 +57,9 @@ struct Path {
     bool gd_w2, gd_edge_fwd, gd_edge_bwd;   // node rows through buffer descriptors (§3zk), per kernel
     bool recv_blocks;            // the receiver-block edge forward
     bool team_edges;             // team_blocks(n_eblocks): a small batch's gradients share launches
-    // a gated call (relation gates, §3zz; the caller holds a WideCall): no team_* kernel, fused loop or enc_pair
-    // at any batch size, the one-hot edge forward on a receiver-block plan, pointer-form gathers in the gated kernels
+    // a gated call (relation gates, §3zz): the kernels of the ungated call — team, fused or wide — in their GATE
+    // forms; the one-hot edge forward on a receiver-block plan, pointer-form gathers in the wide gated kernels, and
+    // the small-batch W2 gradient as its own launch (the merged batch job is the descriptor form)
     bool gated;
     // a backward only (make_path with a BwdCall)
     bool ws_skip0;      // null prop: the k_wgrad_ws jobs over P leave step 0's stages out (§3zh)
@@ -68,6 +69,8 @@ struct Path {
     DiagSwitches diag;
 };
 
-Path make_path(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, const BwdCall* call = nullptr);
+// gated: a forward with relation gates (a backward's are call->gates)
+Path make_path(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, const BwdCall* call = nullptr,
+               bool gated = false);
 
 }  // namespace spw

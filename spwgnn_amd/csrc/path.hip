@@ -47,7 +47,7 @@ static bool gather_desc_fits(int64_t rows_padded) {
     return rows_padded * kRowE * (int64_t)sizeof(float) < (int64_t(1) << 31);
 }
 
-Path make_path(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, const BwdCall* call) {
+Path make_path(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, const BwdCall* call, bool gated) {
     Path p{};
     const int mask = kernel_mask(), mb = math_bwd(r->math);
     const auto family = [&](int bit, int m) { return (r->math != MATH_F32 && (mask & bit)) ? m : (int)MATH_F32; };
@@ -61,9 +61,9 @@ Path make_path(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, const Bw
     p.diag = {getenv_flag("SPWGNN_WG_OLD"),      getenv_flag("SPWGNN_FUSED_ENC"),    getenv_flag("SPWGNN_DA_PAIR"),
               getenv_flag("SPWGNN_W2G_GATHER"),  getenv_flag("SPWGNN_W2G_OLD"),      getenv_flag("SPWGNN_NO_W2_MERGE"),
               getenv_flag("SPWGNN_WS_UNBATCHED"), getenv_flag("SPWGNN_WS_NOGROUP"), getenv_flag("SPWGNN_NO_POS3_MERGE")};
-    // a gated call (the caller's WideCall): team_blocks answers false below and in every launcher, which turns
-    // off team_*, the fused loops and enc_pair for this call alone
-    p.gated = WideCall::active();
+    // a gated call takes the path of the ungated one; what differs is listed at Path::gated. (Under a WideCall
+    // team_blocks answers false below and in every launcher: the wide kernels for that call alone.)
+    p.gated = gated || (call && call->gates);
     const bool team_tiles = team_blocks(b->n_wtiles), team_nodes = team_blocks((b->n_nodes + 31) / 32);
     const bool recv_plan = (b->flags & SPWGNN_BATCH_RECV_BLOCKS) != 0;
     p.team_edges = team_blocks(b->n_eblocks);

@@ -208,6 +208,53 @@ def _check_gates(batch: TowerBatch, run: "RunConfig", gates: torch.Tensor) -> to
     return gates.detach()
 
 
+def check_dropedge(rate) -> float:
+    """A DropEdge rate: a float in [0, 1) (0 = off), what spwgnn_dropedge_gates refuses otherwise."""
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:   # False for a NaN
+        raise ValueError(f"dropedge must be in [0, 1) (got {rate})")
+    return rate
+
+
+def dropedge_gates(batch: TowerBatch, run: RunConfig, rate: float, *, symmetric: bool = True, rescale: bool = False,
+                   base: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The relation gates of a DropEdge draw (spwgnn_dropedge_gates): (32·n_eblocks,) fp32 in the plan's edge-slot
+    order, what ``forward(..., gates=)`` / ``backward(..., gates=)`` take. Edge k is dropped (gate 0) with
+    probability ``rate``, drawn from the run's dropout key (``run.seed``, or the device word ``run.seed_dev``) with
+    a kind of its own on (tower id, sender's local index, receiver's local index): independent of the feature
+    dropout's masks, and the same for a tower wherever a plan, a shard or a micro-batch puts it. ``symmetric``: both
+    directions of a contact share one draw. ``rescale``: a kept edge's gate is 1/(1 − rate) instead of 1.
+    ``base``: (32·n_eblocks,) fp32 weights multiplied into the mask (`TowerBatch.edge_gates` builds them).
+    Padding slots get 0. One launch, no host sync; ``out``: the buffer to write (a captured step's static one)."""
+    rate = check_dropedge(rate)
+    slots = 32 * batch.n_eblocks
+    if base is not None:
+        base = _check_gates(batch, run, base)
+    if out is None:
+        out = _poison(torch.empty(slots, dtype=torch.float32, device=batch.device))
+    else:
+        _out_buffer(out, (slots,), "out")
+    if batch.node_tower is None or batch.node_local is None:
+        raise ValueError("dropedge_gates needs the batch's node_tower and node_local (the key's tower id and node index)")
+    b = batch.cstruct()
+    r = run.cstruct()
+    flags = (_lib.DROPEDGE_SYMMETRIC if symmetric else 0) | (_lib.DROPEDGE_RESCALE if rescale else 0)
+    st = _lib.lib().spwgnn_dropedge_gates(C.byref(b), C.byref(r), rate, flags,
+                                          base.data_ptr() if base is not None else None, out.data_ptr(),
+                                          _stream(batch.device))
+    _lib.check(st, "spwgnn_dropedge_gates")
+    return out
+
+
+def dropedge_keep_host(key: int, tower: int, a: int, b: int, rate: float, symmetric: bool = True) -> bool:
+    """Whether DropEdge keeps edge (tower, sender a → receiver b) under `key` (spwgnn_dropedge_keep_host; no device)."""
+    st = int(_lib.lib().spwgnn_dropedge_keep_host(int(key) & 0xFFFFFFFFFFFFFFFF, int(tower), int(a), int(b), float(rate),
+                                                  _lib.DROPEDGE_SYMMETRIC if symmetric else 0))
+    if st < 0:
+        _lib.check(st, "spwgnn_dropedge_keep_host")
+    return st == 1
+
+
 def workspace_bytes(batch: TowerBatch, run: RunConfig) -> int:
     n = int(_lib.lib().spwgnn_workspace_bytes(batch.n_nodes, batch.n_eblocks, run.mp_steps, 1 if run.training else 0))
     if n < 0:
@@ -215,14 +262,16 @@ def workspace_bytes(batch: TowerBatch, run: RunConfig) -> int:
     return n
 
 
-def fused_path(batch: TowerBatch, run: RunConfig) -> int:
+def fused_path(batch: TowerBatch, run: RunConfig, gated: bool = False) -> int:
     """The library's own answer to which launches this batch and run take (spwgnn_fused_path): bit 0 =
-    the forward's fused small-batch step loop, bit 1 = the backward's. No device work."""
+    the forward's fused small-batch step loop, bit 1 = the backward's. ``gated``: for a call with relation gates
+    (spwgnn_fused_path_gated). No device work."""
     b = batch.cstruct()
     r = run.cstruct()
-    st = _lib.lib().spwgnn_fused_path(C.byref(b), C.byref(r))
+    symbol = "spwgnn_fused_path_gated" if gated else "spwgnn_fused_path"
+    st = getattr(_lib.lib(), symbol)(C.byref(b), C.byref(r))
     if st < 0:
-        _lib.check(st, "spwgnn_fused_path")
+        _lib.check(st, symbol)
     return int(st)
 
 
@@ -380,9 +429,10 @@ def forward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Wo
     (a captured forward's static output, like ``logits``).
     ``gates`` (spwgnn_forward_gated): one relation gate per edge slot, (32·n_eblocks,) fp32 in the plan's
     edge-slot order (`TowerBatch.edge_gates` builds it), any finite values; edge k's message is scaled by
-    gates[k] in the receiver sum of Networks.py:88 alone, padding slots are never read. A gated call runs
-    the wide kernels at every batch size, in x6, x3 and h3 (`gates_supported`); its backward must be given
-    the same tensor, unchanged."""
+    gates[k] in the receiver sum of Networks.py:88 alone, padding slots are never read. A gated call takes
+    the ungated call's launches in their gated forms (`fused_path(gated=True)`; the results are the wide gated
+    kernels' bit for bit), in x6, x3 and h3 (`gates_supported`); its backward must be given the same tensor,
+    unchanged."""
     if gates is not None:
         return _forward("spwgnn_forward_gated", True, flat_params, batch, run, ws, logits, (batch.n_nodes,), "logits",
                         return_state, state, gates)

@@ -111,7 +111,8 @@ class KerasModel:
 
     def __init__(self, net: GraphNetwork, n_objects: int, object_dim: int = 3, lr: float = 5e-4,
                  l2: float = 0.0, clipnorm: float = 0.0, clipvalue: float = 0.0, decay: float = 0.0,
-                 skip_nonfinite: bool = False, step_loss_weights=None, tower_loss: float = 0.0, node_loss: float = 1.0):
+                 skip_nonfinite: bool = False, step_loss_weights=None, tower_loss: float = 0.0, node_loss: float = 1.0,
+                 dropedge: float = 0.0, dropedge_symmetric: bool = True, dropedge_rescale: bool = False):
         if object_dim != 3:
             # Networks.py:70-73 + main.py:28-31/59-63: the object_dim=2 path of the reference is
             # broken (om gets 1 feature, boxes[...,2] is out of range); only the Jenga layout runs.
@@ -137,6 +138,15 @@ class KerasModel:
                                  "is not built)")
             self._path = TowerLossPath(dev, net.mp_steps, self.tower_loss, self.node_loss, totals=True)
         self.step_loss_weights = self._path.lam
+        # DropEdge: every training step (train_on_batch, fit) drops a random subset of the
+        # relations, drawn from the step's dropout key; predict and evaluate draw nothing. 0 = off, the calls of before
+        self.dropedge = E.check_dropedge(dropedge)
+        self.dropedge_symmetric, self.dropedge_rescale = bool(dropedge_symmetric), bool(dropedge_rescale)
+        if self.dropedge > 0:
+            if not E.gates_supported(net.math):
+                raise ValueError(f"dropedge needs a math that takes relation gates (x6, x3, h3), not {net.math}")
+            if self.step_loss_weights is not None:
+                raise ValueError("dropedge and step_loss_weights do not combine (gated per-step logits are not built)")
         self._tot_s = None if step_loss_weights is None else torch.zeros(net.mp_steps, 3, dtype=torch.float64, device=dev)
         self.m = torch.zeros_like(net.flat.data)
         self.v = torch.zeros_like(net.flat.data)
@@ -155,6 +165,17 @@ class KerasModel:
     clipnorm, clipvalue, decay, skip_nonfinite = (delegated("opt", k) for k in
                                                   ("clipnorm", "clipvalue", "decay", "skip_nonfinite"))
     step_out3 = property(lambda self: self._path.out3s)   # the last loss's (S, 3) per-step rows (step_loss_weights)
+
+    def _dropedge_options(self):
+        """(rate, symmetric, rescale) of a DropEdge model, None without it (replay.step_body's argument)."""
+        return (self.dropedge, self.dropedge_symmetric, self.dropedge_rescale) if self.dropedge > 0 else None
+
+    def _dropedge_gates(self, batch, run):
+        """A training step's DropEdge mask as relation gates, {} without DropEdge (the calls of before)."""
+        if not self.dropedge > 0:
+            return {}
+        return {"gates": E.dropedge_gates(batch, run, self.dropedge, symmetric=self.dropedge_symmetric,
+                                          rescale=self.dropedge_rescale)}
 
     def _every_step(self) -> DeepLossPath:
         """A path over every step's rows whatever the model trains on: λ = e_{S−1} gives the plain loss's bits."""
@@ -206,7 +227,8 @@ class KerasModel:
         net, path = self.net, self._path
         net._step_seed += 1
         run = net.run_config(True, dropout=net.dropout, seed=net._step_seed)
-        z = path.forward(net.flat.data, batch, run, self._ws)
+        gated = self._dropedge_gates(batch, run)
+        z = path.forward(net.flat.data, batch, run, self._ws, **gated)
         if self.tower_loss > 0:
             out3, dz = path.loss(z, target, node_weights=self._dev_weights(node_weights), batch=batch,
                                  tower_targets=self._dev_weights(tower_targets),
@@ -215,7 +237,7 @@ class KerasModel:
             if tower_targets is not None:
                 raise ValueError("tower_targets need a model with tower_loss > 0")
             out3, dz = path.loss(z, target, node_weights=self._dev_weights(node_weights))
-        path.backward(net.flat.data, batch, run, self._ws, dz, self._grads)
+        path.backward(net.flat.data, batch, run, self._ws, dz, self._grads, **gated)
         self.iterations += 1
         self.opt.update(net.flat.data, self._grads, self.m, self.v, self.iterations)
         return out3
@@ -249,7 +271,7 @@ class KerasModel:
         net = self.net
         return step_body(net.flat.data, self._grads, self.m, self.v, self._path, self.opt, self._ctr,
                          lambda **kw: net.run_config(True, dropout=net.dropout, **kw), _lib.STEP_KEY_COUNTER,
-                         sums=(self._tot, self._tot_s, self._w3))
+                         sums=(self._tot, self._tot_s, self._w3), dropedge=self._dropedge_options())
 
     def evaluate_batch(self, batch: TowerBatch, target: torch.Tensor, node_weights=None, norm=None, tower_targets=None):
         """out3 = [loss, correct, n] of an inference forward ([Σ_s λ_s·loss_s, the last step's correct, n] with
@@ -363,6 +385,9 @@ class KerasModel:
                                    sample_weight, class_weight)
         if "tower_target" in y:
             raise ValueError("y['tower_target'] needs a model with tower_loss > 0")
+        if "relation_weights" in x:
+            raise ValueError("x['relation_weights'] is not part of fit (replayed steps carry no base weights); "
+                             "Trainer.step(relation_weights=) and GraphNetwork take them")
         objects = np.asarray(x["objects"], np.float32)
         target = np.asarray(y["target"], np.float32).reshape(objects.shape[0], -1)
         B = objects.shape[0]
@@ -396,7 +421,7 @@ class KerasModel:
             self._ctr.set(key=self.net._step_seed, step=self.iterations, lr=self.lr, beta1=self.beta1,
                           beta2=self.beta2, decay=self.decay)
         # the clip options are baked into a geometry's launches (and its captured graph)
-        opts = (graph, weighted, self.clipnorm, self.clipvalue, self.skip_nonfinite, clip_on)
+        opts = (graph, weighted, self.clipnorm, self.clipvalue, self.skip_nonfinite, clip_on, self._dropedge_options())
         if lam is not None:
             opts += (lam,)
         if self._replays is None or self._replay_graph != opts:
@@ -491,9 +516,10 @@ class KerasModel:
         net, path, ctr = self.net, self._path, self._ctr
         E.step_advance(ctr.key, ctr.step, _lib.STEP_KEY_COUNTER, 0, 0)
         run = net.run_config(True, dropout=net.dropout, seed_dev=ctr.key)
-        z = path.forward(net.flat.data, batch, run, self._ws)
+        gated = self._dropedge_gates(batch, run)
+        z = path.forward(net.flat.data, batch, run, self._ws, **gated)
         path.loss_backward(net.flat.data, batch, run, self._ws, z, target, None, None, self._grads, node_weights=w,
-                           tower_targets=tt, node_loss=0.0 if target is None else None)
+                           tower_targets=tt, node_loss=0.0 if target is None else None, **gated)
         self.opt.update_dev(net.flat.data, self._grads, self.m, self.v, ctr, self.opt.totals)
 
     def _fit_tower(self, x, y, batch_size, epochs, validation_split, shuffle, verbose, seed, graph, sample_weight,
@@ -535,12 +561,16 @@ class KerasModel:
         else:
             self._ctr.set(key=self.net._step_seed, step=self.iterations, lr=self.lr, beta1=self.beta1,
                           beta2=self.beta2, decay=self.decay)
-        opts = (graph, "tower", self.tower_loss, alpha, self.clipnorm, self.clipvalue, self.skip_nonfinite, clip_on)
+        if "relation_weights" in x:
+            raise ValueError("x['relation_weights'] is not part of fit (replayed steps carry no base weights)")
+        opts = (graph, "tower", self.tower_loss, alpha, self.clipnorm, self.clipvalue, self.skip_nonfinite, clip_on,
+                self._dropedge_options())
         if replayed and (self._replays is None or self._replay_graph != opts):
             net = self.net
             self._replays = ReplayCache(dev, lambda: step_body(
                 net.flat.data, self._grads, self.m, self.v, path, self.opt, self._ctr,
-                lambda **kw: net.run_config(True, dropout=net.dropout, **kw), _lib.STEP_KEY_COUNTER), graph=graph)
+                lambda **kw: net.run_config(True, dropout=net.dropout, **kw), _lib.STEP_KEY_COUNTER,
+                dropedge=self._dropedge_options()), graph=graph)
             self._replay_graph = opts
         ep_tot = torch.zeros(epochs, 6, dtype=torch.float64, device=dev)
         ep_val = torch.zeros(epochs, 6, dtype=torch.float32, device=dev)
@@ -666,7 +696,8 @@ class PropagationNetwork:
 
     def __init__(self, device="cuda", seed: int = 0, mp_steps: int = E.REF_MP_STEPS, dropout: float = E.REF_DROPOUT,
                  math: str = "x6", clipnorm: float = 0.0, clipvalue: float = 0.0, decay: float = 0.0,
-                 skip_nonfinite: bool = False, step_loss_weights=None, tower_loss: float = 0.0, node_loss: float = 1.0):
+                 skip_nonfinite: bool = False, step_loss_weights=None, tower_loss: float = 0.0, node_loss: float = 1.0,
+                 dropedge: float = 0.0, dropedge_symmetric: bool = True, dropedge_rescale: bool = False):
         # Networks.py:101 Adam(lr=0.0005, decay=0.0); clipnorm / clipvalue are Keras 2.x Optimizer kwargs
         E.check_clip_options(clipnorm, clipvalue, decay)
         if step_loss_weights is not None:   # deep supervision (KerasModel): one weight per propagation step
@@ -675,9 +706,16 @@ class PropagationNetwork:
         if tower_loss > 0 and step_loss_weights is not None:
             raise ValueError("tower_loss and step_loss_weights do not combine")
         self._opt = dict(clipnorm=clipnorm, clipvalue=clipvalue, decay=decay, skip_nonfinite=skip_nonfinite,
-                         step_loss_weights=step_loss_weights, tower_loss=tower_loss, node_loss=node_loss)
+                         step_loss_weights=step_loss_weights, tower_loss=tower_loss, node_loss=node_loss,
+                         dropedge=E.check_dropedge(dropedge), dropedge_symmetric=dropedge_symmetric,
+                         dropedge_rescale=dropedge_rescale)
         if math not in E.MATH_MODES:
             raise ValueError(f"math must be one of {sorted(E.MATH_MODES)}")
+        if self._opt["dropedge"] > 0:   # DropEdge (KerasModel): refused here, at construction, where it cannot run
+            if not E.gates_supported(math):
+                raise ValueError(f"dropedge needs a math that takes relation gates (x6, x3, h3), not {math}")
+            if step_loss_weights is not None:
+                raise ValueError("dropedge and step_loss_weights do not combine")
         self._math = math   # every model's arithmetic (GraphNetwork.math); "x6": the fp32-class default
         self.Nets: Dict[int, KerasModel] = {}
         self.set_weights = False

@@ -103,13 +103,24 @@ class GraphNetwork(nn.Module):
     two encodings (Networks.py:77-78), active only in training mode. ``math`` ("x6" by default, the
     fp32-class parity path; "h3", "x3", "bf16", "f32": `engine.MATH_MODES`) is the arithmetic of the matrix
     products in training, inference and `forward_pooled`.
+
+    ``dropedge`` (a rate in [0, 1)): in train mode under autograd every forward drops a random
+    subset of the relations — `engine.dropedge_gates` with the step's dropout key, multiplied into the call's
+    ``relation_weights`` in torch, so the chain rule to a weights leaf stays autograd's. ``dropedge_symmetric``:
+    both directions of a contact share the draw; ``dropedge_rescale``: kept relations weigh 1/(1 − rate).
+    `eval()` and no-grad calls draw nothing. 0 = off.
     """
 
     def __init__(self, mp_steps: int = E.REF_MP_STEPS, dropout: float = E.REF_DROPOUT, seed: int = 0,
-                 device="cuda", params: Optional[Dict[str, np.ndarray]] = None, math: str = "x6"):
+                 device="cuda", params: Optional[Dict[str, np.ndarray]] = None, math: str = "x6",
+                 dropedge: float = 0.0, dropedge_symmetric: bool = True, dropedge_rescale: bool = False):
         super().__init__()
         if math not in E.MATH_MODES:
             raise ValueError(f"math must be one of {sorted(E.MATH_MODES)}")
+        self.dropedge = E.check_dropedge(dropedge)
+        self.dropedge_symmetric, self.dropedge_rescale = bool(dropedge_symmetric), bool(dropedge_rescale)
+        if self.dropedge > 0 and not E.gates_supported(math):
+            raise ValueError(f'dropedge is not supported in math "{math}" (x6, x3 and h3 take relation gates)')
         self.math = math          # the matrix-product arithmetic of every run this network builds (engine.RunConfig.math)
         self.mp_steps = mp_steps
         self.dropout = dropout
@@ -136,7 +147,7 @@ class GraphNetwork(nn.Module):
         need_grad = torch.is_grad_enabled() and (self.flat.requires_grad or input_grad)
         drop = self.training and self.dropout > 0 and need_grad
         seed = 0
-        if drop:
+        if drop or (self.training and self.dropedge > 0 and need_grad):   # a step that draws: the next key
             self._step_seed += 1
             seed = self._step_seed
         return E.RunConfig(self.mp_steps, training=need_grad, dropout=self.dropout if drop else 0.0, seed=seed,
@@ -184,6 +195,12 @@ class GraphNetwork(nn.Module):
             gates = batch.edge_gates(relation_weights)   # torch indexing: autograd reaches relation_weights
         want_rel = gates is not None and torch.is_grad_enabled() and gates.requires_grad
         run = self._run(want_obj or want_prop or want_rel)
+        if self.dropedge > 0 and self.training and run.training:
+            if return_steps:
+                raise ValueError("dropedge does not combine with return_steps (per-step logits are not gated)")
+            mask = E.dropedge_gates(batch, run, self.dropedge, symmetric=self.dropedge_symmetric,
+                                    rescale=self.dropedge_rescale)
+            gates = mask if gates is None else gates * mask   # in torch: autograd carries the mask to the weights leaf
         ws = E.Workspace(self.device)
         if prop is not None:
             batch = batch.with_prop(prop)

@@ -321,14 +321,22 @@ class ReplayCache:
 
 
 def step_body(params, grads, m, v, path, adam, counters: DeviceCounters, make_run: Callable, key_mode: int,
-              seed: int = 0, rank: int = 0, grad_scale: float = 1.0, sums: Optional[tuple] = None) -> Callable:
+              seed: int = 0, rank: int = 0, grad_scale: float = 1.0, sums: Optional[tuple] = None,
+              dropedge: Optional[tuple] = None) -> Callable:
     """The launches of one optimizer step for `ReplayStep`, the one body of every front end: the key/step
     advance in `key_mode` (with `seed`, `rank`), the forward, the loss with the backward, the gradient
     scale and Adam at the device step word. `path`: the front end's step.LossPath, `adam`: its
     step.AdamUpdate; `make_run(seed_dev=, prologue=)` builds the training RunConfig. `sums`: the epoch
     sums (total3, total3s or None, {towers of the batch: weights3}) the loss launch adds to. The buffers
-    are bound here, as a captured graph binds their addresses."""
+    are bound here, as a captured graph binds their addresses.
+    `dropedge` ((rate, symmetric, rescale), or None): a DropEdge step. The mask kernel reads the uploaded plan and
+    the advanced key, so this body does not fold the prologue: the upload (ReplayStep's copy_in) and
+    spwgnn_step_advance run as launches of their own, then the mask into a static gates buffer of the geometry,
+    then the gated forward / loss / backward on the device key — two launches more than the folded step."""
     path = path.for_replay()
+    if dropedge is not None:
+        return _dropedge_body(params, grads, m, v, path, adam, counters, make_run, key_mode, seed, rank, grad_scale,
+                              sums, dropedge)
     tot, tot_s, w3s = sums if sums is not None else (None, None, None)
 
     tower_kw = bool(getattr(path, "needs_towers", False))
@@ -351,6 +359,32 @@ def step_body(params, grads, m, v, path, adam, counters: DeviceCounters, make_ru
             grads.mul_(grad_scale)
         adam.update_dev(params, grads, m, v, counters, adam.totals)   # the epoch's clip sums ride in the update
     body.needs_towers = tower_kw   # ReplayStep then uploads the plan's tower offsets and their divisor
+    return body
+
+
+def _dropedge_body(params, grads, m, v, path, adam, counters, make_run, key_mode, seed, rank, grad_scale, sums,
+                   dropedge) -> Callable:
+    """`step_body` with DropEdge: no `pre` parameter, so ReplayStep issues the upload as its own launch."""
+    tot, tot_s, w3s = sums if sums is not None else (None, None, None)
+    tower_kw = bool(getattr(path, "needs_towers", False))
+    rate, symmetric, rescale = dropedge
+    static = {}   # the geometry's gates buffer: a captured graph binds its address
+
+    def body(batch, target, ws, bce, z, dz, weights=None, norm=None, norm_t=None):
+        E.step_advance(counters.key, counters.step, key_mode, seed, rank)
+        run = make_run(seed_dev=counters.key, prologue=None)
+        buf = static.get("gates")
+        if buf is None or buf.numel() != 32 * batch.n_eblocks:
+            buf = static["gates"] = torch.empty(32 * batch.n_eblocks, dtype=torch.float32, device=z.device)
+        gates = E.dropedge_gates(batch, run, rate, symmetric=symmetric, rescale=rescale, out=buf)
+        logits = path.forward(params, batch, run, ws, z, gates=gates)
+        path.loss_backward(params, batch, run, ws, logits, target, bce, dz, grads, tot,
+                           w3s[batch.n_towers] if w3s is not None else None, tot_s, weights, norm, gates,
+                           **({"norm_t": norm_t} if tower_kw else {}))
+        if grad_scale != 1.0:
+            grads.mul_(grad_scale)
+        adam.update_dev(params, grads, m, v, counters, adam.totals)
+    body.needs_towers = tower_kw
     return body
 
 

@@ -25,6 +25,17 @@ Optional (asked for only by the feature that needs it):
       node divisor (node_loss arrives scaled by its share of the global batch), norm_t the GLOBAL tower divisor;
       dlogits is the gradient of node_loss·L_node + tower_loss·L_tower with them, summed over ranks with weight 1
       (None with want_dlogits False: evaluate, which passes the micro-batch's own tower count as norm_t)
+  dropedge_gates(batch, run, rate, symmetric=True, rescale=False, base=None) -> gates
+      Trainer(dropedge=): one relation gate per edge slot of the plan ((32·n_eblocks,), 0 = dropped), drawn from
+      run.seed as engine.dropedge_gates draws it, `base` (a slot tensor or None) multiplied in
+  forward(params, batch, run, gates=gates) / backward(params, batch, run, dlogits, gates=gates)
+      Trainer(dropedge=) and step(relation_weights=): the gated calls (engine.forward / backward's ``gates=``); the
+      backward receives the tensor the forward of the same micro-batch ran with. Without DropEdge and without
+      relation weights neither call is ever given the keyword.
+
+Relation gates on the loss paths: `forward`, `backward` and `loss_backward` take ``gates=``. With gates,
+`loss_backward` is the loss launch followed by `engine.backward(gates=)` — spwgnn_bce_backward takes no gates, so
+the fused loss of the small-batch loop is not used. Per-step logits are not gated: `DeepLossPath` raises.
 """
 from __future__ import annotations
 
@@ -51,8 +62,10 @@ class LossPath:
         """The path a replayed geometry's body holds: one that may own static rows of that geometry."""
         return self
 
-    def forward(self, params, batch, run, ws, out=None):
+    def forward(self, params, batch, run, ws, out=None, gates=None):
         """The logits the loss takes; ``out``: a replayed step's static (n,) logits buffer."""
+        if gates is not None:
+            return E.forward(params, batch, run, ws, logits=out, gates=gates)
         return E.forward(params, batch, run, ws, logits=out)
 
     def loss(self, logits, target, total3=None, weights3=None, total3s=None, node_weights=None, norm=None):
@@ -60,13 +73,21 @@ class LossPath:
         return E.bce(logits, target, self.scratch, total3=total3, weights3=weights3, node_weights=node_weights,
                      norm=norm)
 
-    def backward(self, params, batch, run, ws, dlogits, grads):
+    def backward(self, params, batch, run, ws, dlogits, grads, gates=None):
+        if gates is not None:
+            return E.backward(params, batch, run, ws, dlogits, grads=grads, gates=gates)[0]
         return E.backward(params, batch, run, ws, dlogits, grads=grads)[0]
 
     def loss_backward(self, params, batch, run, ws, logits, target, scratch, dlogits, grads, total3=None,
-                      weights3=None, total3s=None, node_weights=None, norm=None):
+                      weights3=None, total3s=None, node_weights=None, norm=None, gates=None):
         """A replayed step's loss and backward on its static buffers: one library call here
-        (spwgnn_bce_backward: no loss launch of its own on the fused small-batch loop)."""
+        (spwgnn_bce_backward: no loss launch of its own on the fused small-batch loop). With ``gates`` the loss
+        launch (into this path's scratch) and then the gated backward."""
+        if gates is not None:
+            _, dz = E.bce(logits, target, scratch, dlogits=dlogits, total3=total3, weights3=weights3,
+                          node_weights=node_weights, norm=norm)
+            E.backward(params, batch, run, ws, dz, grads=grads, gates=gates)
+            return
         E.bce_backward(params, batch, run, ws, logits, target, scratch, dlogits=dlogits, total3=total3,
                        weights3=weights3, grads=grads, node_weights=node_weights, norm=norm)
 
@@ -89,7 +110,14 @@ class DeepLossPath(LossPath):
     def for_replay(self) -> "DeepLossPath":
         return DeepLossPath(self.device, self.mp_steps, self.lam)
 
-    def forward(self, params, batch, run, ws, out=None):
+    @staticmethod
+    def _ungated(gates):
+        if gates is not None:
+            raise ValueError("step_loss_weights and relation gates (DropEdge, relation_weights) do not combine: "
+                             "gated per-step logits are not built")
+
+    def forward(self, params, batch, run, ws, out=None, gates=None):
+        self._ungated(gates)
         if out is not None:   # a replayed step: the static rows in place of its (n,) buffer
             if self.rows is None:
                 self.rows = torch.empty(self.mp_steps, batch.n_nodes, dtype=torch.float32, device=out.device)
@@ -103,11 +131,13 @@ class DeepLossPath(LossPath):
             total3=total3, weights3=weights3, total3s=total3s, node_weights=node_weights, norm=norm)
         return out3, dlogits
 
-    def backward(self, params, batch, run, ws, dlogits, grads):
+    def backward(self, params, batch, run, ws, dlogits, grads, gates=None):
+        self._ungated(gates)
         return E.backward_steps(params, batch, run, ws, dlogits, grads=grads)[0]
 
     def loss_backward(self, params, batch, run, ws, logits, target, scratch, dlogits, grads, total3=None,
-                      weights3=None, total3s=None, node_weights=None, norm=None):
+                      weights3=None, total3s=None, node_weights=None, norm=None, gates=None):
+        self._ungated(gates)
         _, dlogits = self.loss(logits, target, total3, weights3, total3s, node_weights, norm)
         E.backward_steps(params, batch, run, ws, dlogits, grads=grads)
 
@@ -146,15 +176,18 @@ class TowerLossPath(LossPath):
                            norm=norm, total6=t.total6, weights6=t.weights6, want_dlogits=want_dlogits)
 
     def loss_backward(self, params, batch, run, ws, logits, target, scratch, dlogits, grads, total3=None,
-                      weights3=None, total3s=None, node_weights=None, norm=None, *, tower_targets=None, norm_t=None,
-                      node_loss=None):
+                      weights3=None, total3s=None, node_weights=None, norm=None, gates=None, *, tower_targets=None,
+                      norm_t=None, node_loss=None):
         """The loss launch followed by `engine.backward`. A replayed step derives its tower targets from the node
         targets; its tower offsets and its divisor (`norm_t`, a device float) come with the batch upload, since
         plans of one geometry may cut their nodes into different towers. total3 / weights3 of the plain paths
         are not taken (tower.total6 holds the sums)."""
         _, dz = self.loss(logits, target, node_weights=node_weights, norm=norm, batch=batch,
                           tower_targets=tower_targets, norm_t=norm_t, node_loss=node_loss, dlogits=dlogits)
-        E.backward(params, batch, run, ws, dz, grads=grads)
+        if gates is not None:
+            E.backward(params, batch, run, ws, dz, grads=grads, gates=gates)
+        else:
+            E.backward(params, batch, run, ws, dz, grads=grads)
 
 
 def loss_path(device, mp_steps: int, step_loss_weights=None, *, tower_loss: float = 0.0, node_loss: float = 1.0,

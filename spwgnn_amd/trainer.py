@@ -90,8 +90,12 @@ class HipEngine:
     bce_scratch = property(lambda self: self.path.scratch)
     out3s = property(lambda self: self.path.out3s)   # the last loss's per-step [loss, correct, n] (device, (mp_steps, 3))
 
-    def forward(self, params, batch: TowerBatch, run: E.RunConfig):
-        return self.path.forward(params, batch, run, self.ws)
+    def forward(self, params, batch: TowerBatch, run: E.RunConfig, gates=None):
+        return self.path.forward(params, batch, run, self.ws, gates=gates)
+
+    def dropedge_gates(self, batch: TowerBatch, run: E.RunConfig, rate, symmetric=True, rescale=False, base=None):
+        """The step's DropEdge mask as relation gates (engine.dropedge_gates), drawn from the run's key."""
+        return E.dropedge_gates(batch, run, rate, symmetric=symmetric, rescale=rescale, base=base)
 
     def loss(self, logits, target):
         return self.path.loss(logits, target)
@@ -99,10 +103,10 @@ class HipEngine:
     def loss_weighted(self, logits, target, weights, norm):
         return self.path.loss(logits, target, node_weights=weights, norm=norm)
 
-    def backward(self, params, batch, run, dlogits):
+    def backward(self, params, batch, run, dlogits, gates=None):
         if self.grads is None or self.grads.numel() != params.numel():
             self.grads = torch.empty_like(params)
-        return self.path.backward(params, batch, run, self.ws, dlogits, self.grads)
+        return self.path.backward(params, batch, run, self.ws, dlogits, self.grads, gates=gates)
 
     def eval_metrics(self, logits, target, tables, batch, weights=None, threshold=0.5):
         """The evaluation counts of `logits` (the rows `forward` returned) added to `tables` on the device
@@ -158,7 +162,12 @@ class Trainer:
                  beta2: float = 0.999, eps: float = 1e-7, l2: float = 0.0, group=None, math: str = "x6",
                  buckets: int = 1, overlap: bool = True, clipnorm: float = 0.0, clipvalue: float = 0.0,
                  decay: float = 0.0, skip_nonfinite: bool = False, step_loss_weights=None, tower_loss: float = 0.0,
-                 node_loss: float = 1.0):
+                 node_loss: float = 1.0, dropedge: float = 0.0, dropedge_symmetric: bool = True,
+                 dropedge_rescale: bool = False):
+        # dropedge (a rate in [0, 1)): every training step drops a random subset of the relations —
+        # gate 0 in the receiver sum, or 1/(1 − rate) on a kept one with dropedge_rescale — drawn from the step's
+        # dropout key with a kind of its own; dropedge_symmetric: both directions of a contact share the draw.
+        # Training only (`evaluate` draws nothing). 0: exactly the steps of before, no gated call.
         # tower_loss (mu > 0): the objective is node_loss·L_node + tower_loss·L_tower, L_tower the tower-level
         # BCE of engine.bce_tower; `step` then takes tower_targets= and sets `loss_parts`.
         # 0: exactly the steps of before (node_loss is then not read).
@@ -194,6 +203,18 @@ class Trainer:
                                  "spwgnn_amd/step.py)")
             if hasattr(self.engine, "set_tower_loss"):
                 self.engine.set_tower_loss(self.tower_loss, self.node_loss, mp_steps)
+        self.dropedge = E.check_dropedge(dropedge)
+        self.dropedge_symmetric, self.dropedge_rescale = bool(dropedge_symmetric), bool(dropedge_rescale)
+        if self.dropedge > 0:
+            if not E.gates_supported(math):
+                raise ValueError(f"dropedge needs a math that takes relation gates (spwgnn_gates_supported: x6, x3 and "
+                                 f"h3 do, {math} does not)")
+            if self.step_loss_weights is not None:
+                raise ValueError("dropedge and step_loss_weights do not combine (gated per-step logits are not built)")
+            if not hasattr(self.engine, "dropedge_gates"):
+                raise ValueError("dropedge needs an engine with dropedge_gates(batch, run, rate, symmetric, rescale, "
+                                 "base) and gates= on forward / backward (the engine protocol: spwgnn_amd/step.py)")
+        self._rel = None          # the current step's relation weights, one per micro-batch (step(relation_weights=))
         self.clip_stats = None    # the last clipped step's [norm, scale, skipped, clipped] (device tensor)
         self.m = torch.zeros_like(params)
         self.v = torch.zeros_like(params)
@@ -296,7 +317,7 @@ class Trainer:
             return E.RunConfig(self.mp_steps, training=True, dropout=self.dropout, math=self.math, **kw)
         return step_body(self.params, torch.empty_like(self.params), self.m, self.v, self.engine.path, self.opt,
                          self._ctr, make_run, _lib.STEP_KEY_SPLITMIX, self.seed, self.rank,
-                         grad_scale=n_nodes / (n_global or n_nodes))
+                         grad_scale=n_nodes / (n_global or n_nodes), dropedge=self._dropedge_options())
 
     def bucket_bounds(self, n: int):
         """[(start, end)) of the gradient buckets over a flat buffer of n floats (64-float aligned)."""
@@ -489,6 +510,21 @@ class Trainer:
                    tower_accuracy=lp[4] / lp[5] if lp[5] else float("nan"))
         return out
 
+    def _dropedge_options(self):
+        """(rate, symmetric, rescale) of a DropEdge trainer, None without it."""
+        return (self.dropedge, self.dropedge_symmetric, self.dropedge_rescale) if self.dropedge > 0 else None
+
+    def _gates(self, i: int, b, run):
+        """Micro-batch i's relation gates: its relation weights (a slot tensor, or what `TowerBatch.edge_gates`
+        takes) with the step's DropEdge mask multiplied in; None without either."""
+        base = None if self._rel is None else self._rel[i]
+        if base is not None and not (isinstance(base, torch.Tensor) and tuple(base.shape) == (32 * b.n_eblocks,)):
+            base = b.edge_gates(base)
+        if self.dropedge > 0:
+            return self.engine.dropedge_gates(b, run, self.dropedge, symmetric=self.dropedge_symmetric,
+                                              rescale=self.dropedge_rescale, base=base)
+        return base
+
     def _accumulate_and_update(self, batches, loss_of):
         """The micro-batch loop of `step`: forward, `loss_of(i, logits, batch) -> (dlogits, gradient weight)`,
         backward, the weighted gradient sum (the last one in two pieces when overlapped), the all-reduce and
@@ -497,10 +533,12 @@ class Trainer:
         acc = None
         for i, b in enumerate(batches):
             run = self.run_config(micro=i)
-            z = self.engine.forward(self.params, b, run)
+            gates = self._gates(i, b, run)
+            kw = {} if gates is None else {"gates": gates}   # an ungated step: the calls of before
+            z = self.engine.forward(self.params, b, run, **kw)
             dz, w = loss_of(i, z, b)
             ev = self._early(run) if i == len(batches) - 1 else None
-            g = self.engine.backward(self.params, b, run, dz)
+            g = self.engine.backward(self.params, b, run, dz, **kw)
             if acc is None:
                 # one batch: the engine's own buffer (HipEngine.grads), scaled in place; micro-batches: the
                 # engine writes every backward into that buffer, so the sum lives in the Trainer's accumulator
@@ -565,7 +603,7 @@ class Trainer:
         return self._tower_out3(lp)
 
     def step(self, batch, target, n_global: Optional[int] = None, weights=None, norm_global: Optional[int] = None, *,
-             tower_targets=None, towers_global: Optional[int] = None):
+             tower_targets=None, towers_global: Optional[int] = None, relation_weights=None):
         """One optimizer step. `batch`/`target` may be lists (micro-batches of this rank's shard);
         `n_global` = nodes in the whole global batch (all ranks, all micro-batches). Returns one
         [loss, correct, n] device tensor for this rank's shard: the node-weighted mean BCE over its
@@ -584,8 +622,27 @@ class Trainer:
         node term of that micro-batch. `towers_global`: the counted towers of the whole global batch
         (all-reduced when None). The result is [node_loss·L_node + tower_loss·L_tower, node correct, node
         count] of this rank's shard, and `loss_parts` holds its [L_node, node correct, node count, L_tower,
-        towers correct, towers counted]. The engine needs `loss_tower` (spwgnn_amd/step.py)."""
+        towers correct, towers counted]. The engine needs `loss_tower` (spwgnn_amd/step.py).
+
+        `relation_weights` (one per micro-batch): relation gates of the step (engine.forward's ``gates=``) — a
+        (32·n_eblocks,) tensor in the plan's edge-slot order, or what `TowerBatch.edge_gates` takes (one value per
+        active relation in the input's edge order, or (B, N, N)). With Trainer(dropedge=) the step's mask is
+        multiplied into them. Not differentiated here (`GraphNetwork` carries the chain rule to a weights leaf)."""
         batches, targets, weights = _micro_batches(batch, target, weights)
+        if relation_weights is not None:
+            relation_weights = relation_weights if isinstance(relation_weights, (list, tuple)) else [relation_weights]
+            if len(relation_weights) != len(batches):
+                raise ValueError("one relation weight tensor per micro-batch")
+            if self.step_loss_weights is not None:
+                raise ValueError("relation_weights and step_loss_weights do not combine (gated per-step logits are "
+                                 "not built)")
+        self._rel = relation_weights
+        try:
+            return self._step(batches, targets, weights, n_global, norm_global, tower_targets, towers_global)
+        finally:
+            self._rel = None
+
+    def _step(self, batches, targets, weights, n_global, norm_global, tower_targets, towers_global):
         if self.tower_loss <= 0 and (tower_targets is not None or towers_global is not None):
             raise ValueError("tower_targets / towers_global need Trainer(tower_loss > 0)")
         # micro-batch i counts k_i nodes — all of them, or those with w ≠ 0 — of `total` in the global batch:
