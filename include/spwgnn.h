@@ -92,7 +92,9 @@ int32_t spwgnn_plan_fill(int32_t n_towers, const int32_t* tower_nodes, const int
  * decreasing edge count, each into the open wave-tile (<= nw_max nodes) whose last 32-edge block has
  * room for its edges, else a new tile; order[k] = the k-th tower, each tile's towers consecutive.
  * Planned in this order a batch needs no more blocks than in its own order and usually far fewer
- * (BASELINE config 4's ragged 4-16-box thresholded towers: 67 % -> 78 % block fill).
+ * (BASELINE config 4's ragged 4-16-box thresholded towers: 67 % -> 78 % block fill):
+ * both orders are sized as spwgnn_plan_size would (same nw_max), and where the packed one needs more
+ * blocks the identity order[k] = k is returned.
  * The caller permutes its towers (node rows, edge lists, targets, propagation) and keeps each
  * tower's original id for the dropout key (TowerBatch tower_ids). Deterministic. Host memory. */
 int32_t spwgnn_plan_order(int32_t n_towers, const int32_t* tower_nodes, const int32_t* tower_edges, int32_t nw_max,

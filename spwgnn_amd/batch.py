@@ -291,10 +291,11 @@ class TowerBatch:
         """Per-edge-slot results (`engine.backward_relations`: last axis = the plan's 32·n_eblocks edge
         slots, numpy or torch, any leading axes such as the steps) → ``(src, dst, values)`` with the padding
         slots dropped: edge j is the j-th active relation (the order of ``self.src`` / ``self.dst``:
-        tower-major, sender-major inside a tower), its node ids in the INPUT's node order (through
+        tower-major, inside a tower the order the list was given in), its node ids in the INPUT's node order (through
         ``node_perm`` for packed plans), values[..., j] its value. With ``dense`` (towers of one size N
         only) instead one (..., B, N, N) array indexed [tower, sender, receiver] in the input's tower
-        order, zero where there is no relation."""
+        order, zero where there is no relation; a pair that appears twice in the edge list has two values
+        and one cell, so the dense form raises ValueError naming it (the 1-D form returns both)."""
         eid = np.asarray(self.edge_id)
         v = values.detach().cpu().numpy() if isinstance(values, torch.Tensor) else np.asarray(values)
         if v.shape[-1] != len(eid):
@@ -312,6 +313,13 @@ class TowerBatch:
         if len(tn) == 0 or np.any(tn != tn[0]):
             raise ValueError("the dense form needs towers of one size")
         N = int(tn[0])
+        cell, first, count = np.unique(src * N + dst % N, return_index=True, return_counts=True)
+        if len(cell) < len(src):   # a repeated pair: one cell cannot hold two values
+            k = int(np.argmax(count > 1))
+            j = int(first[k])
+            raise ValueError(f"the dense form has one cell per (tower, sender, receiver): relation {int(src[j]) % N} -> "
+                             f"{int(dst[j]) % N} of tower {int(src[j]) // N} appears {int(count[k])} times; use the "
+                             "1-D form")
         out = np.zeros(v.shape[:-1] + (len(tn), N, N), v.dtype)
         out[..., src // N, src % N, dst % N] = vals
         return out

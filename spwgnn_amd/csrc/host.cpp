@@ -185,8 +185,9 @@ static int32_t plan_pack(int32_t n_towers, const int32_t* tower_nodes, const int
 // A tower order that packs ragged towers into fewer 32-edge blocks (spwgnn_plan_order). Towers are
 // placed by decreasing edge count; each joins the open wave-tile whose last block its edges fit
 // without a new block (the tightest such slot, then the tightest node fit), else opens a new tile.
-// The order lists each tile's towers consecutively, tiles in opening order, so plan_pack's in-order
-// packing rebuilds those tiles or merges neighbours — never more blocks: ceil(a+b) <= ceil(a)+ceil(b).
+// The order lists each tile's towers consecutively, tiles in opening order; plan_pack's in-order packing
+// usually rebuilds those tiles or merges neighbours. Where it does not (see the end), the identity is returned:
+// planned in the returned order a batch never needs more blocks than in its own.
 static int32_t plan_order_impl(int32_t n_towers, const int32_t* tower_nodes, const int32_t* tower_edges,
                                int32_t nw_max, int32_t* order) {
     if (n_towers < 0 || (n_towers > 0 && (!tower_nodes || !tower_edges || !order)) || nw_max < 1 ||
@@ -236,6 +237,22 @@ static int32_t plan_order_impl(int32_t n_towers, const int32_t* tower_nodes, con
     int32_t k = 0;
     for (const auto& tt : tile_towers)
         for (const int32_t t : tt) order[k++] = t;
+    if (n_towers == 0) return SPWGNN_OK;
+    // plan_pack fills tiles greedily by node count and does not know the tiles chosen above: it may merge a
+    // tile's first towers into the tile before and so split it ((8,32), (8,30), (2,2) at nw_max 16 packs
+    // 16 nodes / 62 edges + 2 / 2 = 3 blocks, the order (8,30), (2,2), (8,32) 2). Size both orders as the
+    // planner will and keep the caller's own when this one needs more blocks.
+    std::vector<int32_t> pn(n_towers), pe(n_towers);
+    for (int32_t i = 0; i < n_towers; ++i) {
+        pn[i] = tower_nodes[order[i]];
+        pe[i] = tower_edges[order[i]];
+    }
+    int32_t nb_own = 0, nb_new = 0, used = 0;
+    int32_t st = plan_pack(n_towers, tower_nodes, tower_edges, nw_max, nullptr, &nb_own, &used);
+    if (st == SPWGNN_OK) st = plan_pack(n_towers, pn.data(), pe.data(), nw_max, nullptr, &nb_new, &used);
+    if (st) return st;
+    if (nb_new > nb_own)
+        for (int32_t i = 0; i < n_towers; ++i) order[i] = i;
     return SPWGNN_OK;
 }
 
