@@ -452,7 +452,8 @@ int32_t spwgnn_backward_relations(const float* params, const spwgnn_batch* batch
  * CONTRACT: the backward's gates hold the values the forward's held (the library cannot check it; the
  * Python layer does, engine.Workspace). After spwgnn_backward_gated, spwgnn_backward_inputs works as
  * before and spwgnn_backward_relations returns d loss / d w_k AT THESE GATES.
- * Per-step logits with gates, spwgnn_bce_backward with gates and per-step gates are not part of this. */
+ * Per-step logits with gates and spwgnn_bce_backward with gates are not part of this. Per-step gates, one
+ * w_{k,s} per edge and step, are spwgnn_forward_step_gated / spwgnn_backward_step_gated, below. */
 int32_t spwgnn_gates_supported(int32_t math);
 int32_t spwgnn_forward_gated(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
                              void* workspace, int64_t workspace_bytes,
@@ -464,6 +465,28 @@ int32_t spwgnn_backward_gated(const float* params, const spwgnn_batch* batch, co
                               const float* gates /* the forward's; NULL = ungated */,
                               const float* dlogits, const float* dstate /* as spwgnn_backward_state */,
                               float* grads, float* dprop, spwgnn_stream_t stream);
+
+/* Per-step relation gates (added within ABI 8: new symbols only): one gate w_{k,s} per active
+ * edge k AND propagation step s, any finite fp32:
+ *   eff_{i,s} = tanh(Σ_{k: dst_k = i} w_{k,s} · (h2_{k,s}·W3 + b3)),
+ * everything else as the shared gates above (ungated gathers, multiplying zeros, padding slots never used).
+ * gates: device fp32 [mp_steps][gate_step], row s in the order of spwgnn_forward_gated's gates; gate_step >=
+ * 32·n_eblocks and a multiple of 4 (every row 16-byte aligned), else SPWGNN_E_ARG before any device work. The
+ * slots [32·n_eblocks, gate_step) of a row are never read. gates == NULL (gate_step ignored): spwgnn_forward_state
+ * / spwgnn_backward_state bit for bit. mp_steps equal rows give spwgnn_forward_gated / _backward_gated bit for
+ * bit. The calls take the launches of the shared-gate calls (spwgnn_fused_path_gated), with their maths
+ * (spwgnn_gates_supported; SPWGNN_E_SHAPE otherwise), plan kinds and options, and their CONTRACT: the backward's
+ * gates hold what the forward's held. After spwgnn_backward_step_gated, spwgnn_backward_relations' drel_steps[s][k]
+ * is d loss / d w_{k,s} at these gates and drel[k] its sum over s. */
+int32_t spwgnn_forward_step_gated(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                                  void* workspace, int64_t workspace_bytes,
+                                  const float* gates /* [mp_steps][gate_step]; NULL = ungated */, int64_t gate_step,
+                                  float* logits, float* state_out, spwgnn_stream_t stream);
+int32_t spwgnn_backward_step_gated(const float* params, const spwgnn_batch* batch, const spwgnn_run* run,
+                                   void* workspace, int64_t workspace_bytes,
+                                   const float* gates /* the forward's; NULL = ungated */, int64_t gate_step,
+                                   const float* dlogits, const float* dstate, float* grads, float* dprop,
+                                   spwgnn_stream_t stream);
 
 /* DropEdge (added within ABI 8: new symbols only): the relation gates of a random edge subset,
  * drawn per training step — the usual regulariser of a message-passing network, next to the feature dropout of
@@ -490,6 +513,18 @@ int32_t spwgnn_dropedge_gates(const spwgnn_batch* batch, const spwgnn_run* run, 
 /* The keep decision of one edge on the host (no device): 1 kept, 0 dropped, SPWGNN_E_ARG for a bad rate or flag.
  * Only SPWGNN_DROPEDGE_SYMMETRIC changes the answer. */
 int32_t spwgnn_dropedge_keep_host(uint64_t key, uint32_t tower, uint32_t a, uint32_t b, float rate, int32_t flags);
+/* Layer-wise DropEdge: a fresh edge subset at every propagation step. One launch writes the
+ * run->mp_steps rows of gates [mp_steps][gate_step] (gate_step as spwgnn_forward_step_gated's): row s is
+ * spwgnn_dropedge_gates' mask drawn with feature s of the edge's row key in place of feature 0, so row 0 IS that
+ * mask and every row is as independent of the plan as it is. base_step == 0: one base row [32·n_eblocks] (or NULL)
+ * multiplied into every row; otherwise base is [mp_steps][base_step], base_step >= 32·n_eblocks and a multiple of
+ * 4. Padding slots get +0 in every row; the slots [32·n_eblocks, gate_step) of a row are not written.
+ * spwgnn_dropedge_keep_host_step is the host's keep decision of step `step` (step 0: spwgnn_dropedge_keep_host). */
+int32_t spwgnn_dropedge_step_gates(const spwgnn_batch* batch, const spwgnn_run* run, float rate, int32_t flags,
+                                   const float* base, int64_t base_step, float* gates, int64_t gate_step,
+                                   spwgnn_stream_t stream);
+int32_t spwgnn_dropedge_keep_host_step(uint64_t key, uint32_t tower, uint32_t a, uint32_t b, uint32_t step, float rate,
+                                       int32_t flags);
 
 /* Keras binary_crossentropy on sigmoid(logits) (Networks.py:102), mean over n:
  * out3 = {loss, sum of correct (binary_accuracy numerator), n}; dlogits = dloss/dlogit.

@@ -155,6 +155,12 @@ def _declare(lib: C.CDLL) -> None:
         "spwgnn_backward_gated": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, vp, vp, vp, vp, vp]),
         "spwgnn_dropedge_gates": (i32, [C.POINTER(BatchC), C.POINTER(RunC), f32, i32, vp, vp, vp]),
         "spwgnn_dropedge_keep_host": (i32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, f32, i32]),
+        "spwgnn_forward_step_gated": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, i64, vp, vp, vp]),
+        "spwgnn_backward_step_gated": (i32, [vp, C.POINTER(BatchC), C.POINTER(RunC), vp, i64, vp, i64, vp, vp, vp, vp,
+                                             vp]),
+        "spwgnn_dropedge_step_gates": (i32, [C.POINTER(BatchC), C.POINTER(RunC), f32, i32, vp, i64, vp, i64, vp]),
+        "spwgnn_dropedge_keep_host_step": (i32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32,
+                                                 i32]),
         "spwgnn_plan_device_positions": (i32, [C.POINTER(PlanDeviceC), vp, i32, f32, f32, vp]),
         "spwgnn_plan_device_dense": (i32, [C.POINTER(PlanDeviceC), vp, vp, i32, i32, vp]),
         "spwgnn_bce_scratch_bytes": (i64, [i64]),

@@ -133,6 +133,10 @@ class HostPlan:
         """`TowerBatch.edge_gates` of the batch this plan becomes, on ``device`` (default: where ``values`` is)."""
         return TowerBatch.edge_gates(self, values, fill, device)
 
+    def edge_step_gates(self, values, fill: float = 0.0, device=None) -> torch.Tensor:
+        """`TowerBatch.edge_step_gates` of the batch this plan becomes."""
+        return TowerBatch.edge_step_gates(self, values, fill, device)
+
     @staticmethod
     def build(pos, tower_nodes, src, dst, tower_edges, prop=None, nw_max=None, node_shape=None, tower_ids=None,
               edge_cap=None, recv_blocks=None, pack: bool = False) -> "HostPlan":
@@ -362,6 +366,16 @@ class TowerBatch:
         active = torch.as_tensor(eid >= 0, device=dev)
         got = v[torch.as_tensor(pick, device=dev)]
         return torch.where(active, got, torch.full_like(got, float(fill))).contiguous()
+
+    def edge_step_gates(self, values, fill: float = 0.0, device=None) -> torch.Tensor:
+        """Per-relation, per-step values → the (S, 32·n_eblocks) fp32 tensor that ``engine.forward(...,
+        step_gates=)`` takes: row s is `edge_gates` of ``values[s]``. ``values`` is (S, E) in the input's edge
+        order, or (S, B, N, N) indexed [step, tower, sender, receiver] for towers of one size (through
+        ``node_perm`` for packed plans). Built from torch indexing ops, so autograd reaches ``values``."""
+        v = values if isinstance(values, torch.Tensor) else torch.as_tensor(np.asarray(values))
+        if v.dim() not in (2, 4) or v.shape[0] < 1:
+            raise ValueError(f"values must be (S, E) in the input's edge order or (S, B, N, N), got {tuple(v.shape)}")
+        return torch.stack([self.edge_gates(v[s], fill, device) for s in range(v.shape[0])]).contiguous()
 
     @property
     def n_edges(self) -> int:

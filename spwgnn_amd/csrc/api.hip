@@ -94,13 +94,14 @@ int32_t spwgnn_forward(const float* params, const spwgnn_batch* batch, const spw
 // DESIGN.md §3zr): the forward, then the state's export
 static int32_t forward_state(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
                              int64_t workspace_bytes, float* logits, float* state_out, bool steps,
-                             spwgnn_stream_t stream, const float* gates = nullptr) {
+                             spwgnn_stream_t stream, const float* gates = nullptr, int64_t gate_step = 0,
+                             bool gate_step_ok = true) {
     Ws w;
     if (int32_t stt = enter(batch, run, workspace, workspace_bytes, false,
-                            params && logits && !mis16(state_out) && !mis16(gates), w, gates != nullptr))
+                            params && logits && !mis16(state_out) && !mis16(gates) && gate_step_ok, w, gates != nullptr))
         return stt;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const FwdCall call{logits, state_out != nullptr, steps ? batch->n_nodes : 0, gates};
+    const FwdCall call{logits, state_out != nullptr, steps ? batch->n_nodes : 0, gates, gate_step};
     const int32_t stt = run_forward(params, batch, run, w, static_cast<char*>(workspace), call, st);
     if (stt || !state_out) return stt;
     const Ctx c{w, static_cast<char*>(workspace), false};
@@ -120,6 +121,21 @@ int32_t spwgnn_forward_gated(const float* params, const spwgnn_batch* batch, con
                              int64_t workspace_bytes, const float* gates, float* logits, float* state_out,
                              spwgnn_stream_t stream) {
     return forward_state(params, batch, run, workspace, workspace_bytes, logits, state_out, false, stream, gates);
+}
+
+// per-step gates: a row's stride holds the plan's slots and keeps every row 16-byte aligned.
+// Asked only with gates; a null batch is enter's SPWGNN_E_ARG
+static bool gate_step_ok(const spwgnn_batch* batch, const float* gates, int64_t gate_step) {
+    return !gates || !batch || (gate_step % 4 == 0 && gate_step >= (int64_t)batch->n_eblocks * 32);
+}
+
+// gates null: spwgnn_forward_state itself. Otherwise spwgnn_forward_gated with row s of gates [mp_steps][gate_step]
+// at step s: the same checks (and gate_step's: SPWGNN_E_ARG) before any device work, the same launches
+int32_t spwgnn_forward_step_gated(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                                  int64_t workspace_bytes, const float* gates, int64_t gate_step, float* logits,
+                                  float* state_out, spwgnn_stream_t stream) {
+    return forward_state(params, batch, run, workspace, workspace_bytes, logits, state_out, false, stream, gates,
+                         gates ? gate_step : 0, gate_step_ok(batch, gates, gate_step));
 }
 
 int32_t spwgnn_forward_steps(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
@@ -156,6 +172,17 @@ int32_t spwgnn_backward_gated(const float* params, const spwgnn_batch* batch, co
     const bool ok = params && dlogits && grads && !mis16(dstate) && !mis16(gates);
     BwdCall call{dlogits, grads, dprop, nullptr, dstate};
     call.gates = gates;
+    return backward(batch, run, workspace, workspace_bytes, ok, call, stream);
+}
+
+// gates null: spwgnn_backward_state itself; row s of gates [mp_steps][gate_step] holds what the forward's held
+int32_t spwgnn_backward_step_gated(const float* params, const spwgnn_batch* batch, const spwgnn_run* run, void* workspace,
+                                   int64_t workspace_bytes, const float* gates, int64_t gate_step, const float* dlogits,
+                                   const float* dstate, float* grads, float* dprop, spwgnn_stream_t stream) {
+    const bool ok = params && dlogits && grads && !mis16(dstate) && !mis16(gates) && gate_step_ok(batch, gates, gate_step);
+    BwdCall call{dlogits, grads, dprop, nullptr, dstate};
+    call.gates = gates;
+    call.gate_step = gates ? gate_step : 0;
     return backward(batch, run, workspace, workspace_bytes, ok, call, stream);
 }
 
@@ -236,18 +263,30 @@ static bool dropedge_thresh(float rate, uint32_t& thresh) {
 }
 constexpr int32_t kDropEdgeFlags = SPWGNN_DROPEDGE_SYMMETRIC | SPWGNN_DROPEDGE_RESCALE;
 
-int32_t spwgnn_dropedge_keep_host(uint64_t key, uint32_t tower, uint32_t a, uint32_t b, float rate, int32_t flags) {
+int32_t spwgnn_dropedge_keep_host_step(uint64_t key, uint32_t tower, uint32_t a, uint32_t b, uint32_t step, float rate,
+                                       int32_t flags) {
     uint32_t thresh;
     if (!dropedge_thresh(rate, thresh) || (flags & ~kDropEdgeFlags)) return SPWGNN_E_ARG;
-    return dropedge_keep(key, tower, a, b, (flags & SPWGNN_DROPEDGE_SYMMETRIC) != 0, thresh) ? 1 : 0;
+    return dropedge_keep(key, tower, a, b, (flags & SPWGNN_DROPEDGE_SYMMETRIC) != 0, thresh, step) ? 1 : 0;
+}
+int32_t spwgnn_dropedge_keep_host(uint64_t key, uint32_t tower, uint32_t a, uint32_t b, float rate, int32_t flags) {
+    return spwgnn_dropedge_keep_host_step(key, tower, a, b, 0u, rate, flags);
 }
 
-int32_t spwgnn_dropedge_gates(const spwgnn_batch* batch, const spwgnn_run* run, float rate, int32_t flags,
-                              const float* base, float* gates, spwgnn_stream_t stream) {
+// steps rows of gates at stride gate_step (one row: spwgnn_dropedge_gates), base rows at stride base_step
+static int32_t dropedge_rows(const spwgnn_batch* batch, const spwgnn_run* run, float rate, int32_t flags,
+                             const float* base, int64_t base_step, float* gates, int steps, int64_t gate_step,
+                             spwgnn_stream_t stream) {
     if (!batch || !run || !gates) return SPWGNN_E_ARG;
     DropEdgeArgs a{};
     if (!dropedge_thresh(rate, a.thresh) || (flags & ~kDropEdgeFlags)) return SPWGNN_E_ARG;
     if (batch->n_nodes < 1 || batch->n_eblocks < 1 || batch->n_eblocks > (INT32_MAX >> 5)) return SPWGNN_E_SHAPE;
+    if (steps < 1) return SPWGNN_E_SHAPE;
+    if (steps > 1 || gate_step || base_step) {   // the per-step call's strides: whole rows, 16-byte aligned
+        const int64_t slots = (int64_t)batch->n_eblocks * 32;
+        if (gate_step < slots || gate_step % 4 || (base && base_step && (base_step < slots || base_step % 4)) || base_step < 0)
+            return SPWGNN_E_ARG;
+    }
     if (!batch->edge_src || !batch->edge_dst || !batch->node_tower || !batch->node_local) return SPWGNN_E_ARG;
     const auto mis = [](const void* q, uintptr_t al) { return reinterpret_cast<uintptr_t>(q) % al != 0; };
     if (mis(gates, 16) || mis(base, 4) || mis(batch->edge_src, 4) || mis(batch->edge_dst, 4) ||
@@ -261,6 +300,9 @@ int32_t spwgnn_dropedge_gates(const spwgnn_batch* batch, const spwgnn_run* run, 
     a.node_local = batch->node_local;
     a.base = base;
     a.gates = gates;
+    a.steps = steps;
+    a.gate_step = gate_step;
+    a.base_step = base ? base_step : 0;
     a.scale = (flags & SPWGNN_DROPEDGE_RESCALE) ? 1.0f / (1.0f - rate) : 1.0f;
     a.symmetric = (flags & SPWGNN_DROPEDGE_SYMMETRIC) ? 1 : 0;
     a.seed = run->seed;
@@ -269,6 +311,22 @@ int32_t spwgnn_dropedge_gates(const spwgnn_batch* batch, const spwgnn_run* run, 
     const Prof prof{run, st};
     SPW_TIMED(prof, SPWGNN_K_DROPEDGE, launch_dropedge(a, st));
     return SPWGNN_OK;
+}
+
+int32_t spwgnn_dropedge_gates(const spwgnn_batch* batch, const spwgnn_run* run, float rate, int32_t flags,
+                              const float* base, float* gates, spwgnn_stream_t stream) {
+    return dropedge_rows(batch, run, rate, flags, base, 0, gates, 1, 0, stream);
+}
+
+// one launch writes all mp_steps rows: row s drawn with feature s of the edge's row key, so row 0
+// is spwgnn_dropedge_gates' mask
+int32_t spwgnn_dropedge_step_gates(const spwgnn_batch* batch, const spwgnn_run* run, float rate, int32_t flags,
+                                   const float* base, int64_t base_step, float* gates, int64_t gate_step,
+                                   spwgnn_stream_t stream) {
+    if (!run) return SPWGNN_E_ARG;
+    if (run->mp_steps < 1) return SPWGNN_E_SHAPE;
+    if (gate_step <= 0) return SPWGNN_E_ARG;
+    return dropedge_rows(batch, run, rate, flags, base, base_step, gates, run->mp_steps, gate_step, stream);
 }
 
 // Argument checks of the device-plan calls (no device work): 0, or the status to return.

@@ -78,7 +78,9 @@ static NodeBwdArgs tail_args(const Ctx& c, const spwgnn_batch* b, const Path& p,
     return tl;
 }
 
-static EdgeBwdArgs edge_bwd_args(const Ctx& c, const spwgnn_batch* b, const Path& p, int s, const float* gates = nullptr) {
+// gates: step s's row of a gated call (the fused loop takes row 0 and advances it by gate_step), or null
+static EdgeBwdArgs edge_bwd_args(const Ctx& c, const spwgnn_batch* b, const Path& p, int s, const float* gates = nullptr,
+                                 int64_t gate_step = 0) {
     const Ws& w = c.w;
     const int k = w.S - 1 - s;   // steps S−1 .. S−n_stored keep their dh1pre (§3zi)
     EdgeBwdArgs eb{};
@@ -103,7 +105,8 @@ static EdgeBwdArgs edge_bwd_args(const Ctx& c, const spwgnn_batch* b, const Path
     eb.dh1_slab = k < p.n_stored ? c.f(w.dz4) + k * (w.dz3 - w.dz4) : nullptr;
     eb.gather_desc = p.gd_edge_bwd;
     eb.node_bytes = (uint32_t)(eb.gather_desc ? w.RN * kRowE * 4 : 0);
-    eb.gates = gates;
+    eb.gates = gates ? gates + s * gate_step : nullptr;
+    eb.gate_step = gate_step;
     return eb;
 }
 
@@ -202,6 +205,7 @@ struct WgRun {
     const Prof& prof;
     float* grads;
     const float* gates;   // a gated call's relation gates (the W2 gradient's Y rows carry them), or null
+    int64_t gate_step;    // ... a row per step (§3zzc), or 0
     WsBatch* wsb;      // the batched k_wgrad_ws launch being filled (null: one launch per gradient)
     ReduceBatch& rb;   // every gradient's reduction
     Pos3Batch& p3;     // the rm.0 / om.0 gradients (k_wgrad_pos3)
@@ -244,6 +248,7 @@ static int32_t run_wgrad(WgRun& q, const WgSpec& g) {
         a.w2_tile = !p.diag.w2g_gather;
         a.gather_desc = p.gd_w2;
         a.gates = q.gates;
+        a.gate_step = q.gate_step;
     }
     // stored chunk-major operands in x6 math: the warp-specialized kernel, one workgroup per CU
     if (math != MATH_F32 && a.xmode == XM_CM && (a.ymode == YM_CM || a.ymode == YM_ROW) && !p.diag.wg_old) {
@@ -575,6 +580,7 @@ int32_t run_backward(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, ch
     DaArgs da{};
     if (p.rebuild_dA) da = da_args(c, b, p);
     da.gates = call.gates;
+    da.gate_step = call.gate_step;
     const EncEdgeBwdArgs eeb = enc_edge_bwd_args(c, b, r, p);
     const EncNodeBwdArgs enb = enc_node_bwd_args(c, b, r, p);
 
@@ -604,7 +610,7 @@ int32_t run_backward(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, ch
         }
         fa.tail = tl;
         fa.has_tail = call.dprop != nullptr;
-        fa.eb = edge_bwd_args(c, b, p, 0, call.gates);
+        fa.eb = edge_bwd_args(c, b, p, 0, call.gates, call.gate_step);
         fa.da = da;
         fa.eeb = eeb;
         fa.enb = enb;
@@ -624,7 +630,7 @@ int32_t run_backward(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, ch
             SPW_TIMED(prof, SPWGNN_K_NODE_BWD,
                       launch_node_bwd(node_bwd_args(c, b, p, call, s), p.node_bwd, st, call.dl_step != 0));
             if (s == 0 && p.skip_eb0) break;   // dU_0 / dV_0 stay unwritten: nothing reads them
-            SPW_TIMED(prof, SPWGNN_K_EDGE_BWD, launch_edge_bwd(edge_bwd_args(c, b, p, s, call.gates), p.edge_bwd, st));
+            SPW_TIMED(prof, SPWGNN_K_EDGE_BWD, launch_edge_bwd(edge_bwd_args(c, b, p, s, call.gates, call.gate_step), p.edge_bwd, st));
         }
         if (call.dprop) SPW_CHECK(launch_node_bwd(tl, p.node_bwd, st));
         if (!p.split)
@@ -636,7 +642,7 @@ int32_t run_backward(const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, ch
     WsBatch wsb{}, wsb2{};   // (split: the early group's, then the late group's)
     ReduceBatch rb{};
     Pos3Batch p3{};
-    WgRun q{c, b, p, st, prof, call.grads, call.gates, p.diag.ws_unbatched ? nullptr : &wsb, rb, p3};
+    WgRun q{c, b, p, st, prof, call.grads, call.gates, call.gate_step, p.diag.ws_unbatched ? nullptr : &wsb, rb, p3};
     const BceArgs* const loss_row = p.bce_inline ? call.bce : nullptr;   // rides in the last reduction
     int32_t e = SPWGNN_OK;
     if (!p.split) {

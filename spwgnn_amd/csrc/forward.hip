@@ -89,7 +89,9 @@ static EncEdgeArgs enc_edge_args(const Ctx& c, const spwgnn_batch* b, const spwg
     return ee;
 }
 
-static EdgeFwdArgs edge_fwd_args(const Ctx& c, const spwgnn_batch* b, const Path& p, int s, const float* gates = nullptr) {
+// gates: step s's row of a gated call (the fused loop takes row 0 and advances it by gate_step), or null
+static EdgeFwdArgs edge_fwd_args(const Ctx& c, const spwgnn_batch* b, const Path& p, int s, const float* gates = nullptr,
+                                 int64_t gate_step = 0) {
     const Ws& w = c.w;
     EdgeFwdArgs ef{};
     ef.n_wtiles = b->n_wtiles;
@@ -115,7 +117,8 @@ static EdgeFwdArgs edge_fwd_args(const Ctx& c, const spwgnn_batch* b, const Path
     ef.uv_zero = s == 0 && !b->prop;   // 'propagation' = 0 (spwgnn.h): P0 = U0 = V0 = 0
     ef.gather_desc = p.gd_edge_fwd;
     ef.node_bytes = (uint32_t)(ef.gather_desc ? w.RN * kRowE * 4 : 0);
-    ef.gates = gates;
+    ef.gates = gates ? gates + s * gate_step : nullptr;
+    ef.gate_step = gate_step;
     return ef;
 }
 
@@ -169,7 +172,7 @@ int32_t run_forward(const float* params, const spwgnn_batch* b, const spwgnn_run
         FwdFusedArgs fa{};
         fa.ee = ee;
         fa.en = en;
-        fa.ef = edge_fwd_args(c, b, p, 0, call.gates);
+        fa.ef = edge_fwd_args(c, b, p, 0, call.gates, call.gate_step);
         fa.nf = node_fwd_args(c, b, p, call, 0);
         fa.S = S;
         fa.training = r->training;
@@ -196,7 +199,7 @@ int32_t run_forward(const float* params, const spwgnn_batch* b, const spwgnn_run
         SPW_TIMED(prof, SPWGNN_K_ENC_EDGE, launch_enc_edge(ee, p.enc_edge, st));
     }
     for (int s = 0; s < S; ++s) {
-        SPW_TIMED(prof, SPWGNN_K_EDGE_FWD, launch_edge_fwd(edge_fwd_args(c, b, p, s, call.gates), p.edge_fwd, st));
+        SPW_TIMED(prof, SPWGNN_K_EDGE_FWD, launch_edge_fwd(edge_fwd_args(c, b, p, s, call.gates, call.gate_step), p.edge_fwd, st));
         SPW_TIMED(prof, SPWGNN_K_NODE_FWD, launch_node_fwd(node_fwd_args(c, b, p, call, s), p.node_fwd, st));
     }
     return SPWGNN_OK;

@@ -149,6 +149,8 @@ struct EdgeFwdArgs {
     int gather_desc;   // 1: A, U, V rows through buffer descriptors (§3zk; the ≤ 16-node wide kernels)
     uint32_t node_bytes;   // gather_desc: bytes of one step's fp32 node array (RN · kRowE · 4 < 2^31)
     const float* gates;    // relation gates [32·n_eblocks] in edge-slot order (§3zz), or null: k_edge_fwd_x6<GATE>
+    int64_t gate_step;     // per-step gates (§3zzc): floats between two steps' rows, gates being this step's row
+                           //   (the fused loop advances it per step); 0: one row shared by every step
 };
 
 struct NodeFwdArgs {
@@ -215,6 +217,7 @@ struct EdgeBwdArgs {
     int gather_desc;   // 1: G3 rows through a buffer descriptor (§3zk; the wide x6 / bf16 kernels)
     uint32_t node_bytes;   // gather_desc: bytes of one step's G3 array (RN · kRowE · 4 < 2^31)
     const float* gates;    // relation gates [32·n_eblocks] (§3zz), or null: dh2pre_k carries gates[k]
+    int64_t gate_step;     // per-step gates (§3zzc): as EdgeFwdArgs::gate_step (gates is this step's row)
 };
 
 struct DaArgs {           // k_dA_x6: dA = Σ_s dh1pre_s, recomputed per 32-edge block
@@ -232,6 +235,7 @@ struct DaArgs {           // k_dA_x6: dA = Σ_s dh1pre_s, recomputed per 32-edge
     int64_t slab_step;
     const float* slab;
     const float* gates;   // relation gates [32·n_eblocks] (§3zz), or null: the rebuilt steps' dh2pre carries them
+    int64_t gate_step;    // per-step gates (§3zzc): step s reads gates + s·gate_step; 0: one row for every step
 };
 
 struct EncEdgeBwdArgs {
@@ -304,6 +308,7 @@ struct WgradArgs {
     int uv_zero;                   // 1: a null 'propagation' — U_0 = V_0 = 0, step 0's stages need not read them
     float* slab;           // [chunks][kx_pad][ny_pad]
     const float* gates;    // YM_DH2 (k_w2grad_ws): relation gates [32·n_eblocks] (§3zz), or null
+    int64_t gate_step;     // per-step gates (§3zzc): a stage of step s reads gates + s·gate_step; 0: one row
 };
 struct WgWsArgs {          // k_wgrad_ws: stages (s, nb) of a [S][nbs] grid of 32-row blocks
     const float* x;        // chunk-major
@@ -555,6 +560,8 @@ struct DropEdgeArgs {
     const int32_t *node_tower, *node_local;   // [n_nodes] the key's tower id and local node index
     const float* base;               // [slots] weights multiplied into the mask, or null = 1
     float* gates;                    // [slots] out: every slot written, a padding slot with 0
+    int steps;                       // rows written (§3zzc): row s at gates + s·gate_step, drawn with feature s of
+    int64_t gate_step, base_step;    //   the row key and multiplied by base + s·base_step (0: one base row)
     uint32_t thresh;                 // floor(rate·2^32): drop_keep's threshold
     float scale;                     // a kept edge's gate before base: 1/(1 − rate), or 1
     int symmetric;                   // the key takes (min, max) of the two local indices
@@ -562,12 +569,17 @@ struct DropEdgeArgs {
     const uint64_t* seed_dev;        // non-null: the key is read from device memory (replayable steps)
 };
 hipError_t launch_dropedge(const DropEdgeArgs& a, hipStream_t st);
-// the key's keep decision (host and device): kind 3, feature 0 of the row key
+// the key's keep decision (host and device): kind 3, feature `step` of the row key (0: the shared mask, which is
+// also row 0 of the per-step masks)
 constexpr uint32_t kDropEdgeKind = 3u;
-__host__ __device__ __forceinline__ bool dropedge_keep(uint64_t key, uint32_t tower, uint32_t la, uint32_t lb,
-                                                       bool symmetric, uint32_t thresh) {
+__host__ __device__ __forceinline__ uint32_t dropedge_row_key(uint64_t key, uint32_t tower, uint32_t la, uint32_t lb,
+                                                              bool symmetric) {
     const uint32_t a = symmetric && lb < la ? lb : la, b = symmetric && lb < la ? la : lb;
-    return drop_keep(drop_row_key(key, kDropEdgeKind, tower, a, b), 0u, thresh);
+    return drop_row_key(key, kDropEdgeKind, tower, a, b);
+}
+__host__ __device__ __forceinline__ bool dropedge_keep(uint64_t key, uint32_t tower, uint32_t la, uint32_t lb,
+                                                       bool symmetric, uint32_t thresh, uint32_t step = 0u) {
+    return drop_keep(dropedge_row_key(key, tower, la, lb, symmetric), step, thresh);
 }
 // k_plan_device (kernels_plan.hip): the data-dependent arrays of a capacity plan, filled on the device
 struct PlanDevArgs {

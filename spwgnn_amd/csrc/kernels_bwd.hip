@@ -1182,7 +1182,8 @@ hipError_t launch_edge_bwd(const EdgeBwdArgs& a, int math, hipStream_t st) {
 // and the G3 ring carries over between those pairs as before; a block's stored steps are read ahead
 // of its first rebuilt pair, where the accumulators are zero and acc is free.
 // GATE (relation gates): the rebuilt steps' dh2pre carries the edge's gate as in
-// k_edge_bwd_x6<GATE> (the stored steps already do): one value per lane and block, read with the receiver index
+// k_edge_bwd_x6<GATE> (the stored steps already do): one value per lane and block, read with the receiver index;
+// with DaArgs::gate_step (per-step gates, §3zzc) one per lane and (block, step) pair, read a pair ahead
 template <int NP = 3, bool B16 = false, bool SLAB = false, bool GATE = false>
 __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_dA_x6(DaArgs a) {
     static_assert(!SLAB || (NP >= 2 && !B16), "stored dh1pre steps: x6 / x3 only");
@@ -1256,7 +1257,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     int blk = b0, s = s_top;
     int d = a.edst[(int64_t)blk * 32 + i];
     [[maybe_unused]] float gw = 0.f;   // the block's gate of this lane's edge (0 on a padding slot, whatever it holds)
-    if constexpr (GATE) gw = d >= 0 ? a.gates[(int64_t)blk * 32 + i] : 0.f;
+    if constexpr (GATE) gw = d >= 0 ? a.gates[s * a.gate_step + (int64_t)blk * 32 + i] : 0.f;
     Pair cur = load_pair(blk, s, d);
     KB ring[PF];
 #pragma unroll
@@ -1304,7 +1305,8 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         const int nd = last_step ? a.edst[(int64_t)nblk * 32 + i] : d;
         [[maybe_unused]] float ngw = gw;
         if constexpr (GATE) {
-            if (last_step) ngw = nd >= 0 ? a.gates[(int64_t)nblk * 32 + i] : 0.f;
+            // per-step gates (§3zzc): every pair has its own row; a shared row is re-read only with the block
+            if (last_step || a.gate_step) ngw = nd >= 0 ? a.gates[max(ns, 0) * a.gate_step + (int64_t)nblk * 32 + i] : 0.f;
         }
         const Pair nxt = load_pair(nblk, max(ns, 0), nd);
         const uint64_t mlo = h == 0 ? ((uint64_t)cur.w[1] << 32 | cur.w[0])

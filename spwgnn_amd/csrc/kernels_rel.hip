@@ -274,18 +274,25 @@ hipError_t launch_rel_bwd(const RelBwdArgs& a, int math, bool b16, bool n16, hip
 // a contact share one draw. The key names the edge by tower id and local indices alone: a tower's mask does not
 // depend on where the plan put its edges. A padding slot (an index outside [0, n_nodes)) reads no node row and no
 // base entry and gets +0. Reads esrc, edst, base at e < slots and node rows at checked indices; writes gates[e].
+// Per-step masks (§3zzc): `steps` rows, row t at gates + t·gate_step drawn with feature t of the edge's row key
+// (row 0 is the one-row mask) and multiplied by base[t·base_step + e]; slots [slots, gate_step) of a row stay unwritten.
 __global__ __launch_bounds__(256) void k_dropedge(DropEdgeArgs a) {
     const uint64_t key = run_seed(a);
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.slots; e += (int64_t)gridDim.x * 256) {
         const int s = a.esrc[e], d = a.edst[e];
-        float g = 0.f;
-        if (s >= 0 && d >= 0 && s < a.n_nodes && d < a.n_nodes) {
-            const bool keep = dropedge_keep(key, (uint32_t)a.node_tower[s], (uint32_t)a.node_local[s],
-                                            (uint32_t)a.node_local[d], a.symmetric != 0, a.thresh);
-            g = keep ? a.scale : 0.f;
-            if (a.base) g = a.base[e] * g;
+        const bool active = s >= 0 && d >= 0 && s < a.n_nodes && d < a.n_nodes;
+        uint32_t rk = 0u;
+        if (active)
+            rk = dropedge_row_key(key, (uint32_t)a.node_tower[s], (uint32_t)a.node_local[s], (uint32_t)a.node_local[d],
+                                  a.symmetric != 0);
+        for (int t = 0; t < a.steps; ++t) {
+            float g = 0.f;
+            if (active) {
+                g = drop_keep(rk, (uint32_t)t, a.thresh) ? a.scale : 0.f;
+                if (a.base) g = a.base[t * a.base_step + e] * g;
+            }
+            a.gates[t * a.gate_step + e] = g;
         }
-        a.gates[e] = g;
     }
 }
 

@@ -1102,6 +1102,7 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_fwd_fused_team(FwdFusedArgs 
         ef.H2s += sE;
         if (ef.mask1) ef.mask1 += s * a.m1_step;
         if (ef.mask2) ef.mask2 += s * a.m2_step;
+        if constexpr (GATE) ef.gates += s * a.ef.gate_step;   // per-step gates (§3zzc); 0: one row
         if (s == 0) TEAM_STAMP(11);
         edge_fwd_team_body<NPT, AB16, GATE>(ef, wt, act_s, h2l);
         if (s == 0) TEAM_STAMP(12);
@@ -1241,7 +1242,8 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_edge_bwd_team(EdgeBwdArgs a)
 
 // ---- dA = Σ_s dh1pre_s (k_dA_x6), team form: five waves per 32-edge block, wave T owns feature
 // tile T; the same products, per-accumulator order and step order (S−1 first) as k_dA_x6.
-// GATE: every rebuilt step's dh2pre carries DaArgs::gates (one value per lane, loaded once per block)
+// GATE: every rebuilt step's dh2pre carries DaArgs::gates (one value per lane, loaded once per block; with
+// DaArgs::gate_step, per-step gates §3zzc, once per step)
 template <int NP, bool B16, bool GATE = false>
 __device__ __forceinline__ void dA_team_body(const DaArgs& a, int blk, uint4* hs) {
     const int lane = opaque_lane(), h = lane >> 5, i = lane & 31;
@@ -1257,6 +1259,9 @@ __device__ __forceinline__ void dA_team_body(const DaArgs& a, int blk, uint4* hs
     f32x16 dacc = zero16();
     for (int s = a.S - 1; s >= 0; --s) {
         uint4* const buf = hs + (s & 1) * (10 * 3 * 64);
+        if constexpr (GATE) {   // per-step gates (§3zzc): step s's own row
+            if (a.gate_step) gw = d >= 0 ? a.gates[s * a.gate_step + (int64_t)blk * 32 + i] : 0.f;
+        }
         const uint32_t m1w = a.mask1[s * a.m1_step + (int64_t)blk * kLdE + i + 32 * T];
         team_dh2_kblocks<NP, GATE>(a.G3 + s * a.g3_step, a.mask2 + s * a.m2_step + (int64_t)blk * kM2Blk, d, 0, T, lane,
                                    buf, gw);
@@ -1397,6 +1402,7 @@ __global__ __launch_bounds__(64 * kTeamEdge) void k_bwd_fused_team(BwdFusedArgs 
         opaque(eb.x_w2t);
         eb.mask1 += s * a.m1_step;
         eb.mask2 += s * a.m2_step;
+        if constexpr (GATE) eb.gates += s * a.eb.gate_step;   // per-step gates (§3zzc); 0: one row
         eb.G3 = nb.G3;
         eb.dU += sE;
         eb.dV += sE;
@@ -1620,7 +1626,7 @@ hipError_t launch_bwd_fused_team(const BwdFusedArgs& a, int math, hipStream_t st
     const dim3 g(a.eb.n_wtiles), b(64 * kTeamEdge);
     if (!a.nb.dlogits || (a.dl_step && a.nb.bce_logits)) return hipErrorInvalidValue;
     if (a.eb.gates || a.da.gates) {   // relation gates: the split maths, fp32 rows, one cotangent row
-        if (a.eb.gates != a.da.gates || a.dl_step || !math_split32(math) || a.da.b16) return hipErrorInvalidValue;
+        if (a.eb.gates != a.da.gates || a.eb.gate_step != a.da.gate_step || a.dl_step || !math_split32(math) || a.da.b16) return hipErrorInvalidValue;
         SPW_SPLIT32(math, NP, hipLaunchKernelGGL((k_bwd_fused_team<NP, false, false, true>), g, b, 0, st, a));
         return hipGetLastError();
     }

@@ -674,7 +674,7 @@ __device__ __forceinline__ void w2grad_ws_body(const WgradArgs& a, int64_t blk_p
         int64_t b; int s;
         stage_of(t, b, s);
         R.in = idx.x >= 0;
-        if constexpr (GATE) R.gw = R.in ? a.gates[32 * b + rr] : 0.f;
+        if constexpr (GATE) R.gw = R.in ? a.gates[s * a.gate_step + 32 * b + rr] : 0.f;   // the stage's step (§3zzc)
         const int sn = R.in ? idx.x : 0, dn = R.in ? idx.y : 0;
         const int64_t ns = (int64_t)s * nstep_n;
         const float* pu = a.U + ns + (int64_t)(sn >> 5) * kCmBlk + (sn & 31) * 4;

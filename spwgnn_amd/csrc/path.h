@@ -17,6 +17,7 @@ struct BwdCall {
     const float* dstate = nullptr;    // spwgnn_backward_state: the cotangent of P_S, row-major
     int64_t dl_step = 0;
     const float* gates = nullptr;     // spwgnn_backward_gated: the forward's relation gates (§3zz)
+    int64_t gate_step = 0;            // spwgnn_backward_step_gated: gates is [S][gate_step], a row per step (§3zzc)
 };
 
 // Diagnosis switches (A/B of superseded kernels): environment variables read per call in -DSPWGNN_DIAG

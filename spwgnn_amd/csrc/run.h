@@ -40,6 +40,7 @@ struct FwdCall {
     bool keep_state = false;   // spwgnn_forward_state with a buffer: the last step leaves P_S in P_at(S) on every path
     int64_t logit_step = 0;    // spwgnn_forward_steps: step s stores its own row
     const float* gates = nullptr;   // spwgnn_forward_gated: one relation gate per edge slot (§3zz)
+    int64_t gate_step = 0;          // spwgnn_forward_step_gated: gates is [S][gate_step], a row per step (§3zzc)
 };
 
 int32_t run_forward(const float* params, const spwgnn_batch* b, const spwgnn_run* r, const Ws& w, char* base,

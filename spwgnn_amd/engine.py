@@ -208,6 +208,36 @@ def _check_gates(batch: TowerBatch, run: "RunConfig", gates: torch.Tensor) -> to
     return gates.detach()
 
 
+def _check_step_gates(batch: TowerBatch, run: "RunConfig", step_gates: torch.Tensor) -> torch.Tensor:
+    """A per-step relation-gate tensor of `forward` / `backward` (``step_gates=``): (mp_steps, 32·n_eblocks) fp32,
+    contiguous, 16-byte aligned, on the GPU, in a math that takes gates. Returns it detached."""
+    if not gates_supported(run.math):
+        raise ValueError(f"relation gates are not supported in math {run.math} (spwgnn_gates_supported: x6, x3 and h3 "
+                         "take them, f32 and bf16 do not)")
+    shape = (int(run.mp_steps), 32 * batch.n_eblocks)
+    if not isinstance(step_gates, torch.Tensor) or tuple(step_gates.shape) != shape:
+        raise ValueError(f"step_gates must be a {shape} tensor, one row per propagation step in the plan's edge-slot "
+                         f"order (TowerBatch.edge_step_gates builds it; got {tuple(getattr(step_gates, 'shape', ()))})")
+    _require_gpu(step_gates, "step_gates")
+    if step_gates.dtype != torch.float32 or not step_gates.is_contiguous() or step_gates.data_ptr() % 16:
+        raise ValueError("step_gates must be a contiguous, 16-byte aligned fp32 tensor")
+    return step_gates.detach()
+
+
+def _gate_args(batch, run, gates, step_gates):
+    """The validated gate tensor of a call (shared or per-step, never both) and the arguments the library's
+    symbol takes for it: (pointer,) or (pointer, row stride)."""
+    if step_gates is not None:
+        if gates is not None:
+            raise ValueError("gates and step_gates are mutually exclusive: one gate per edge, or one per edge and step")
+        step_gates = _check_step_gates(batch, run, step_gates)
+        return step_gates, (step_gates.data_ptr(), int(step_gates.shape[1]))
+    if gates is not None:
+        gates = _check_gates(batch, run, gates)
+        return gates, (gates.data_ptr(),)
+    return None, ()
+
+
 def check_dropedge(rate) -> float:
     """A DropEdge rate: a float in [0, 1) (0 = off), what spwgnn_dropedge_gates refuses otherwise."""
     rate = float(rate)
@@ -217,7 +247,8 @@ def check_dropedge(rate) -> float:
 
 
 def dropedge_gates(batch: TowerBatch, run: RunConfig, rate: float, *, symmetric: bool = True, rescale: bool = False,
-                   base: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   base: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                   per_step: bool = False) -> torch.Tensor:
     """The relation gates of a DropEdge draw (spwgnn_dropedge_gates): (32·n_eblocks,) fp32 in the plan's edge-slot
     order, what ``forward(..., gates=)`` / ``backward(..., gates=)`` take. Edge k is dropped (gate 0) with
     probability ``rate``, drawn from the run's dropout key (``run.seed``, or the device word ``run.seed_dev``) with
@@ -225,20 +256,35 @@ def dropedge_gates(batch: TowerBatch, run: RunConfig, rate: float, *, symmetric:
     dropout's masks, and the same for a tower wherever a plan, a shard or a micro-batch puts it. ``symmetric``: both
     directions of a contact share one draw. ``rescale``: a kept edge's gate is 1/(1 − rate) instead of 1.
     ``base``: (32·n_eblocks,) fp32 weights multiplied into the mask (`TowerBatch.edge_gates` builds them).
-    Padding slots get 0. One launch, no host sync; ``out``: the buffer to write (a captured step's static one)."""
+    Padding slots get 0. One launch, no host sync; ``out``: the buffer to write (a captured step's static one).
+    ``per_step`` (layer-wise DropEdge, spwgnn_dropedge_step_gates): a fresh subset at every propagation step,
+    (mp_steps, 32·n_eblocks) fp32 for ``forward(..., step_gates=)``; row 0 is the mask without ``per_step``. ``base``
+    is then one row multiplied into every step's, or a (mp_steps, 32·n_eblocks) tensor of per-step weights."""
     rate = check_dropedge(rate)
     slots = 32 * batch.n_eblocks
+    shape = (int(run.mp_steps), slots) if per_step else (slots,)
+    base_step = 0
     if base is not None:
-        base = _check_gates(batch, run, base)
+        if per_step and isinstance(base, torch.Tensor) and base.dim() == 2:
+            base = _check_step_gates(batch, run, base)
+            base_step = slots
+        else:
+            base = _check_gates(batch, run, base)
     if out is None:
-        out = _poison(torch.empty(slots, dtype=torch.float32, device=batch.device))
+        out = _poison(torch.empty(shape, dtype=torch.float32, device=batch.device))
     else:
-        _out_buffer(out, (slots,), "out")
+        _out_buffer(out, shape, "out")
     if batch.node_tower is None or batch.node_local is None:
         raise ValueError("dropedge_gates needs the batch's node_tower and node_local (the key's tower id and node index)")
     b = batch.cstruct()
     r = run.cstruct()
     flags = (_lib.DROPEDGE_SYMMETRIC if symmetric else 0) | (_lib.DROPEDGE_RESCALE if rescale else 0)
+    if per_step:
+        st = _lib.lib().spwgnn_dropedge_step_gates(C.byref(b), C.byref(r), rate, flags,
+                                                   base.data_ptr() if base is not None else None, base_step,
+                                                   out.data_ptr(), slots, _stream(batch.device))
+        _lib.check(st, "spwgnn_dropedge_step_gates")
+        return out
     st = _lib.lib().spwgnn_dropedge_gates(C.byref(b), C.byref(r), rate, flags,
                                           base.data_ptr() if base is not None else None, out.data_ptr(),
                                           _stream(batch.device))
@@ -246,12 +292,24 @@ def dropedge_gates(batch: TowerBatch, run: RunConfig, rate: float, *, symmetric:
     return out
 
 
-def dropedge_keep_host(key: int, tower: int, a: int, b: int, rate: float, symmetric: bool = True) -> bool:
-    """Whether DropEdge keeps edge (tower, sender a → receiver b) under `key` (spwgnn_dropedge_keep_host; no device)."""
-    st = int(_lib.lib().spwgnn_dropedge_keep_host(int(key) & 0xFFFFFFFFFFFFFFFF, int(tower), int(a), int(b), float(rate),
-                                                  _lib.DROPEDGE_SYMMETRIC if symmetric else 0))
+def dropedge_keep_host(key: int, tower: int, a: int, b: int, rate: float, symmetric: bool = True,
+                       step: Optional[int] = None) -> bool:
+    """Whether DropEdge keeps edge (tower, sender a → receiver b) under `key` (spwgnn_dropedge_keep_host; no device).
+    ``step``: the draw of propagation step `step` of a per-step mask (spwgnn_dropedge_keep_host_step; step 0 is the
+    shared mask's draw)."""
+    flags = _lib.DROPEDGE_SYMMETRIC if symmetric else 0
+    if step is None:
+        symbol = "spwgnn_dropedge_keep_host"
+        st = int(_lib.lib().spwgnn_dropedge_keep_host(int(key) & 0xFFFFFFFFFFFFFFFF, int(tower), int(a), int(b),
+                                                      float(rate), flags))
+    else:
+        if int(step) < 0:
+            raise ValueError(f"step must be >= 0 (got {step})")
+        symbol = "spwgnn_dropedge_keep_host_step"
+        st = int(_lib.lib().spwgnn_dropedge_keep_host_step(int(key) & 0xFFFFFFFFFFFFFFFF, int(tower), int(a), int(b),
+                                                           int(step), float(rate), flags))
     if st < 0:
-        _lib.check(st, "spwgnn_dropedge_keep_host")
+        _lib.check(st, symbol)
     return st == 1
 
 
@@ -390,13 +448,12 @@ def _check_sums(total3: Optional[torch.Tensor], weights3: Optional[torch.Tensor]
 
 
 def _forward(symbol: str, takes_state: bool, flat_params, batch, run, ws, out, shape, what, return_state, state,
-             gates=None):
+             gates=None, step_gates=None):
     """`forward` / `forward_steps`: ``out`` (or a fresh buffer) of `shape` written by the library's `symbol`,
     whose argument list has a state pointer when `takes_state` (and, in front of the outputs, a gate pointer
-    with ``gates``)."""
+    with ``gates``, or a gate pointer and its row stride with ``step_gates``)."""
     _check_params(flat_params)
-    if gates is not None:
-        gates = _check_gates(batch, run, gates)
+    gates, head = _gate_args(batch, run, gates, step_gates)
     buf = ws.get(workspace_bytes(batch, run))
     if out is None:
         out = _poison(torch.empty(shape, dtype=torch.float32, device=batch.device))
@@ -412,7 +469,6 @@ def _forward(symbol: str, takes_state: bool, flat_params, batch, run, ws, out, s
     b = batch.cstruct()
     r = run.cstruct(with_prologue=True)
     tail = (state.data_ptr() if return_state else None,) if takes_state else ()
-    head = (gates.data_ptr(),) if gates is not None else ()
     st = getattr(_lib.lib(), symbol)(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
                                      *head, out.data_ptr(), *tail, _stream(batch.device))
     ws.stored(batch, run, st == 0, return_state, gates)
@@ -422,7 +478,8 @@ def _forward(symbol: str, takes_state: bool, flat_params, batch, run, ws, out, s
 
 def forward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace,
             logits: Optional[torch.Tensor] = None, return_state: bool = False,
-            state: Optional[torch.Tensor] = None, gates: Optional[torch.Tensor] = None):
+            state: Optional[torch.Tensor] = None, gates: Optional[torch.Tensor] = None,
+            step_gates: Optional[torch.Tensor] = None):
     """Logits (n_nodes,). With ``return_state`` also the final propagation state P_S, (n_nodes, 100) fp32
     in the plan's node order (spwgnn_forward_state) — what the next call takes as its ``prop`` — as
     ``(logits, state)``; the logits are the same bits either way. ``state``: the buffer to write it to
@@ -432,7 +489,14 @@ def forward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Wo
     gates[k] in the receiver sum of Networks.py:88 alone, padding slots are never read. A gated call takes
     the ungated call's launches in their gated forms (`fused_path(gated=True)`; the results are the wide gated
     kernels' bit for bit), in x6, x3 and h3 (`gates_supported`); its backward must be given the same tensor,
-    unchanged."""
+    unchanged.
+    ``step_gates`` (spwgnn_forward_step_gated; exclusive with ``gates``): one gate per edge slot AND propagation
+    step, (mp_steps, 32·n_eblocks) contiguous fp32 (`TowerBatch.edge_step_gates` builds it): step s scales edge k's
+    message by step_gates[s, k]. Equal rows give the ``gates=`` call's bits; the same launches, maths and backward
+    contract."""
+    if step_gates is not None:
+        return _forward("spwgnn_forward_step_gated", True, flat_params, batch, run, ws, logits, (batch.n_nodes,),
+                        "logits", return_state, state, gates, step_gates)
     if gates is not None:
         return _forward("spwgnn_forward_gated", True, flat_params, batch, run, ws, logits, (batch.n_nodes,), "logits",
                         return_state, state, gates)
@@ -452,12 +516,11 @@ def forward_steps(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, 
 
 
 def _backward(symbol: str, takes_dstate: bool, flat_params, batch, run, ws, dlogits, rows, grads, want_dprop, dstate,
-              dprop, gates=None):
+              dprop, gates=None, step_gates=None):
     """`backward` / `backward_steps` through the library's `symbol`, whose argument list has a state
-    cotangent when `takes_dstate` (and a gate pointer in front of ``dlogits`` with ``gates``). `rows`: the
-    (mp_steps, n_nodes) shape ``dlogits`` must have, or None."""
-    if gates is not None:
-        gates = _check_gates(batch, run, gates)
+    cotangent when `takes_dstate` (and a gate pointer in front of ``dlogits`` with ``gates``, or a gate pointer
+    and its row stride with ``step_gates``). `rows`: the (mp_steps, n_nodes) shape ``dlogits`` must have, or None."""
+    gates, head = _gate_args(batch, run, gates, step_gates)
     dstate = _training_forward(ws, batch, run, dstate)
     if ws.gate_key != _gate_key(gates):
         # the library's contract (spwgnn_backward_gated): the backward's gates hold what the forward's held
@@ -475,7 +538,6 @@ def _backward(symbol: str, takes_dstate: bool, flat_params, batch, run, ws, dlog
     r = run.cstruct()
     buf = ws.buf
     mid = (dstate.data_ptr() if dstate is not None else None,) if takes_dstate else ()
-    head = (gates.data_ptr(),) if gates is not None else ()
     st = getattr(_lib.lib(), symbol)(flat_params.data_ptr(), C.byref(b), C.byref(r), buf.data_ptr(), buf.numel(),
                                      *head, dlogits.data_ptr(), *mid, grads.data_ptr(),
                                      dprop.data_ptr() if dprop is not None else None, _stream(batch.device))
@@ -486,7 +548,8 @@ def _backward(symbol: str, takes_dstate: bool, flat_params, batch, run, ws, dlog
 
 def backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: Workspace, dlogits: torch.Tensor,
              grads: Optional[torch.Tensor] = None, want_dprop: bool = False, dstate: Optional[torch.Tensor] = None,
-             dprop: Optional[torch.Tensor] = None, gates: Optional[torch.Tensor] = None):
+             dprop: Optional[torch.Tensor] = None, gates: Optional[torch.Tensor] = None,
+             step_gates: Optional[torch.Tensor] = None):
     """Gradients of Σ dlogits·z — and, with ``dstate`` ((n_nodes, 100) fp32 on the batch's device, plan node
     order), of Σ dlogits·z + Σ dstate·P_S in the same single pass (spwgnn_backward_state); the forward on
     this workspace must then have been ``forward(..., return_state=True)``. A caller with a loss on the
@@ -494,7 +557,12 @@ def backward(flat_params: torch.Tensor, batch: TowerBatch, run: RunConfig, ws: W
     (it implies ``want_dprop``). Returns (grads, dprop).
     ``gates`` (spwgnn_backward_gated): the gate tensor the forward on this workspace ran with — the same
     tensor, not written since; other gates, or none after a gated forward (or gates after an ungated one),
-    raise ValueError. `backward_relations` then returns the gradient with respect to these gates."""
+    raise ValueError. `backward_relations` then returns the gradient with respect to these gates.
+    ``step_gates`` (spwgnn_backward_step_gated): likewise the forward's per-step gate tensor; `backward_relations`'
+    ``drel_steps`` is then its gradient, entry by entry."""
+    if step_gates is not None:
+        return _backward("spwgnn_backward_step_gated", True, flat_params, batch, run, ws, dlogits, None, grads,
+                         want_dprop, dstate, dprop, gates, step_gates)
     if gates is not None:
         return _backward("spwgnn_backward_gated", True, flat_params, batch, run, ws, dlogits, None, grads, want_dprop,
                          dstate, dprop, gates)

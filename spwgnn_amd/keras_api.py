@@ -112,7 +112,8 @@ class KerasModel:
     def __init__(self, net: GraphNetwork, n_objects: int, object_dim: int = 3, lr: float = 5e-4,
                  l2: float = 0.0, clipnorm: float = 0.0, clipvalue: float = 0.0, decay: float = 0.0,
                  skip_nonfinite: bool = False, step_loss_weights=None, tower_loss: float = 0.0, node_loss: float = 1.0,
-                 dropedge: float = 0.0, dropedge_symmetric: bool = True, dropedge_rescale: bool = False):
+                 dropedge: float = 0.0, dropedge_symmetric: bool = True, dropedge_rescale: bool = False,
+                 dropedge_per_step: bool = False):
         if object_dim != 3:
             # Networks.py:70-73 + main.py:28-31/59-63: the object_dim=2 path of the reference is
             # broken (om gets 1 feature, boxes[...,2] is out of range); only the Jenga layout runs.
@@ -142,6 +143,8 @@ class KerasModel:
         # relations, drawn from the step's dropout key; predict and evaluate draw nothing. 0 = off, the calls of before
         self.dropedge = E.check_dropedge(dropedge)
         self.dropedge_symmetric, self.dropedge_rescale = bool(dropedge_symmetric), bool(dropedge_rescale)
+        # layer-wise DropEdge (§3zzc; active only with dropedge > 0): a fresh subset at every propagation step
+        self.dropedge_per_step = bool(dropedge_per_step)
         if self.dropedge > 0:
             if not E.gates_supported(net.math):
                 raise ValueError(f"dropedge needs a math that takes relation gates (x6, x3, h3), not {net.math}")
@@ -167,15 +170,18 @@ class KerasModel:
     step_out3 = property(lambda self: self._path.out3s)   # the last loss's (S, 3) per-step rows (step_loss_weights)
 
     def _dropedge_options(self):
-        """(rate, symmetric, rescale) of a DropEdge model, None without it (replay.step_body's argument)."""
-        return (self.dropedge, self.dropedge_symmetric, self.dropedge_rescale) if self.dropedge > 0 else None
+        """(rate, symmetric, rescale) of a DropEdge model — with a fourth entry True when the mask is drawn per
+        propagation step — None without it (replay.step_body's argument)."""
+        if not self.dropedge > 0:
+            return None
+        return (self.dropedge, self.dropedge_symmetric, self.dropedge_rescale) + ((True,) if self.dropedge_per_step else ())
 
     def _dropedge_gates(self, batch, run):
         """A training step's DropEdge mask as relation gates, {} without DropEdge (the calls of before)."""
         if not self.dropedge > 0:
             return {}
         return {"gates": E.dropedge_gates(batch, run, self.dropedge, symmetric=self.dropedge_symmetric,
-                                          rescale=self.dropedge_rescale)}
+                                          rescale=self.dropedge_rescale, per_step=self.dropedge_per_step)}
 
     def _every_step(self) -> DeepLossPath:
         """A path over every step's rows whatever the model trains on: λ = e_{S−1} gives the plain loss's bits."""
@@ -697,7 +703,8 @@ class PropagationNetwork:
     def __init__(self, device="cuda", seed: int = 0, mp_steps: int = E.REF_MP_STEPS, dropout: float = E.REF_DROPOUT,
                  math: str = "x6", clipnorm: float = 0.0, clipvalue: float = 0.0, decay: float = 0.0,
                  skip_nonfinite: bool = False, step_loss_weights=None, tower_loss: float = 0.0, node_loss: float = 1.0,
-                 dropedge: float = 0.0, dropedge_symmetric: bool = True, dropedge_rescale: bool = False):
+                 dropedge: float = 0.0, dropedge_symmetric: bool = True, dropedge_rescale: bool = False,
+                 dropedge_per_step: bool = False):
         # Networks.py:101 Adam(lr=0.0005, decay=0.0); clipnorm / clipvalue are Keras 2.x Optimizer kwargs
         E.check_clip_options(clipnorm, clipvalue, decay)
         if step_loss_weights is not None:   # deep supervision (KerasModel): one weight per propagation step
@@ -708,7 +715,7 @@ class PropagationNetwork:
         self._opt = dict(clipnorm=clipnorm, clipvalue=clipvalue, decay=decay, skip_nonfinite=skip_nonfinite,
                          step_loss_weights=step_loss_weights, tower_loss=tower_loss, node_loss=node_loss,
                          dropedge=E.check_dropedge(dropedge), dropedge_symmetric=dropedge_symmetric,
-                         dropedge_rescale=dropedge_rescale)
+                         dropedge_rescale=dropedge_rescale, dropedge_per_step=bool(dropedge_per_step))
         if math not in E.MATH_MODES:
             raise ValueError(f"math must be one of {sorted(E.MATH_MODES)}")
         if self._opt["dropedge"] > 0:   # DropEdge (KerasModel): refused here, at construction, where it cannot run

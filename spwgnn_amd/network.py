@@ -25,7 +25,9 @@ class _PropagationFn(torch.autograd.Function):
     after the gated backward. With ``want_state`` a second
     output, the final state (n_nodes, 100), whose gradient enters the same backward pass as ``dstate``.
     With ``want_steps`` the first output is every step's logits (mp_steps, n_nodes) (`engine.forward_steps`)
-    and its gradient goes back through `engine.backward_steps`, still one pass over the step loop."""
+    and its gradient goes back through `engine.backward_steps`, still one pass over the step loop.
+    A 2-D ``gates`` ((mp_steps, slots), `engine.forward`'s ``step_gates``) holds one gate per edge slot and step;
+    its gradient is `engine.backward_relations`' ``drel_steps``."""
 
     @staticmethod
     def forward(ctx, flat, prop_dummy, obj_dummy, batch: TowerBatch, run: E.RunConfig, ws: E.Workspace,
@@ -38,8 +40,9 @@ class _PropagationFn(torch.autograd.Function):
         ctx.want_state = want_state
         ctx.want_steps = want_steps
         ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None, not as zeros
+        ctx.gate_kw = "step_gates" if ctx.gated and gates.dim() == 2 else "gates"
         if ctx.gated:   # forward_batch refuses gates with want_steps
-            return E.forward(flat, batch, run, ws, return_state=want_state, gates=gates)
+            return E.forward(flat, batch, run, ws, return_state=want_state, **{ctx.gate_kw: gates})
         return (E.forward_steps if want_steps else E.forward)(flat, batch, run, ws, return_state=want_state)
 
     @staticmethod
@@ -52,13 +55,17 @@ class _PropagationFn(torch.autograd.Function):
             dlogits = torch.zeros(shape, dtype=torch.float32, device=flat.device)
         if ctx.gated:
             grads, dprop = E.backward(flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop, dstate=dstate,
-                                      gates=gates)
+                                      **{ctx.gate_kw: gates})
         else:
             grads, dprop = (E.backward_steps if ctx.want_steps else E.backward)(
                 flat, ctx.batch, ctx.run, ctx.ws, dlogits, want_dprop=ctx.want_prop, dstate=dstate)
         dobj = E.backward_inputs(flat, ctx.batch, ctx.run, ctx.ws) if ctx.want_obj else None
         # d loss / d gate at the run's gates, 0 in padding slots (one more launch that only reads the workspace)
-        dgates = E.backward_relations(flat, ctx.batch, ctx.run, ctx.ws) if ctx.gated and ctx.needs_input_grad[8] else None
+        dgates = None
+        if ctx.gated and ctx.needs_input_grad[8]:
+            dgates = E.backward_relations(flat, ctx.batch, ctx.run, ctx.ws, per_step=ctx.gate_kw == "step_gates")
+            if ctx.gate_kw == "step_gates":   # (drel, drel_steps): the per-step gates' gradient is drel_steps
+                dgates = dgates[1]
         return grads, dprop, dobj, None, None, None, None, None, dgates
 
 
@@ -108,17 +115,20 @@ class GraphNetwork(nn.Module):
     subset of the relations — `engine.dropedge_gates` with the step's dropout key, multiplied into the call's
     ``relation_weights`` in torch, so the chain rule to a weights leaf stays autograd's. ``dropedge_symmetric``:
     both directions of a contact share the draw; ``dropedge_rescale``: kept relations weigh 1/(1 − rate).
-    `eval()` and no-grad calls draw nothing. 0 = off.
+    `eval()` and no-grad calls draw nothing. 0 = off. ``dropedge_per_step`` (layer-wise DropEdge, §3zzc; active
+    only with ``dropedge`` > 0): a fresh subset at every propagation step instead of one for all of them.
     """
 
     def __init__(self, mp_steps: int = E.REF_MP_STEPS, dropout: float = E.REF_DROPOUT, seed: int = 0,
                  device="cuda", params: Optional[Dict[str, np.ndarray]] = None, math: str = "x6",
-                 dropedge: float = 0.0, dropedge_symmetric: bool = True, dropedge_rescale: bool = False):
+                 dropedge: float = 0.0, dropedge_symmetric: bool = True, dropedge_rescale: bool = False,
+                 dropedge_per_step: bool = False):
         super().__init__()
         if math not in E.MATH_MODES:
             raise ValueError(f"math must be one of {sorted(E.MATH_MODES)}")
         self.dropedge = E.check_dropedge(dropedge)
         self.dropedge_symmetric, self.dropedge_rescale = bool(dropedge_symmetric), bool(dropedge_rescale)
+        self.dropedge_per_step = bool(dropedge_per_step)
         if self.dropedge > 0 and not E.gates_supported(math):
             raise ValueError(f'dropedge is not supported in math "{math}" (x6, x3 and h3 take relation gates)')
         self.math = math          # the matrix-product arithmetic of every run this network builds (engine.RunConfig.math)
@@ -155,8 +165,14 @@ class GraphNetwork(nn.Module):
 
     def forward_batch(self, batch: TowerBatch, prop: Optional[torch.Tensor] = None,
                       objects: Optional[torch.Tensor] = None, return_state: bool = False, return_steps: bool = False,
-                      relation_weights: Optional[torch.Tensor] = None):
+                      relation_weights: Optional[torch.Tensor] = None,
+                      relation_step_weights: Optional[torch.Tensor] = None):
         """Logits (n_nodes,) for a compact batch (the reference returns sigmoid of these).
+
+        ``relation_step_weights`` (exclusive with ``relation_weights``): one gate per active
+        relation AND propagation step, as `TowerBatch.edge_step_gates` takes them — (S, B, N, N) indexed [step,
+        tower, sender, receiver], or (S, E) in the input's edge order. Step s scales relation k's message by its
+        step-s gate; everything else as ``relation_weights``, the gradient of a leaf included.
 
         ``relation_weights``: soft relations — one gate per active relation, as
         `TowerBatch.edge_gates` takes them: a dense (B, N, N) tensor indexed [tower, sender, receiver] for towers
@@ -187,6 +203,18 @@ class GraphNetwork(nn.Module):
         # a carried state that has a gradient path needs this call's backward even under frozen weights
         want_prop = return_state and prop is not None and torch.is_grad_enabled() and prop.requires_grad
         gates = None
+        if relation_step_weights is not None:
+            if relation_weights is not None:
+                raise ValueError("relation_weights and relation_step_weights are mutually exclusive")
+            if return_steps:
+                raise ValueError("relation_step_weights do not combine with return_steps (per-step logits are not gated)")
+            if not E.gates_supported(self.math):
+                raise ValueError(f'relation_step_weights are not supported in math "{self.math}" (x6, x3 and h3 take '
+                                 "them)")
+            if int(relation_step_weights.shape[0]) != int(self.mp_steps):
+                raise ValueError(f"relation_step_weights needs one leading row per propagation step ({self.mp_steps}), "
+                                 f"got {tuple(relation_step_weights.shape)}")
+            gates = batch.edge_step_gates(relation_step_weights)   # torch indexing: autograd reaches the leaf
         if relation_weights is not None:
             if return_steps:
                 raise ValueError("relation_weights do not combine with return_steps (per-step logits are not gated)")
@@ -199,8 +227,10 @@ class GraphNetwork(nn.Module):
             if return_steps:
                 raise ValueError("dropedge does not combine with return_steps (per-step logits are not gated)")
             mask = E.dropedge_gates(batch, run, self.dropedge, symmetric=self.dropedge_symmetric,
-                                    rescale=self.dropedge_rescale)
-            gates = mask if gates is None else gates * mask   # in torch: autograd carries the mask to the weights leaf
+                                    rescale=self.dropedge_rescale, per_step=self.dropedge_per_step)
+            # in torch: autograd carries the mask to the weights leaf (a shared weight row under a per-step mask
+            # broadcasts over the steps; per-step weights under a shared mask likewise)
+            gates = mask if gates is None else (gates * mask).contiguous()
         ws = E.Workspace(self.device)
         if prop is not None:
             batch = batch.with_prop(prop)
@@ -218,7 +248,8 @@ class GraphNetwork(nn.Module):
         if not run.training:
             with torch.no_grad():
                 if gates is not None:
-                    out = E.forward(self.flat.detach(), batch, run, ws, return_state=return_state, gates=gates)
+                    out = E.forward(self.flat.detach(), batch, run, ws, return_state=return_state,
+                                    **{"step_gates" if gates.dim() == 2 else "gates": gates})
                 else:
                     out = (E.forward_steps if return_steps else E.forward)(self.flat.detach(), batch, run, ws,
                                                                            return_state=return_state)
@@ -260,9 +291,11 @@ class GraphNetwork(nn.Module):
 
     def forward_logits(self, objects, sender_relations, receiver_relations, propagation=None,
                        plan: str = "host", return_state: bool = False, return_steps: bool = False,
-                       relation_weights: Optional[torch.Tensor] = None):
+                       relation_weights: Optional[torch.Tensor] = None,
+                       relation_step_weights: Optional[torch.Tensor] = None):
         """``relation_weights``: a (B, N, N) [tower, sender, receiver] tensor of relation gates (soft relations:
         see `forward_batch`); entries without a relation are not read. Autograd reaches it.
+        ``relation_step_weights``: (S, B, N, N), one such tensor per propagation step (see `forward_batch`).
         ``return_steps``: (S, B, N) — every step's logits (see `forward_batch`) in place of the last step's.
         (B, N) logits; with ``return_state`` ``(logits, state)``, state (B, N, 100) (see `forward_batch`). A torch ``objects`` that requires grad receives d/d objects (B, N, 3) on
         backward (see `forward_batch`; the relations are constants).
@@ -276,7 +309,8 @@ class GraphNetwork(nn.Module):
         if propagation is not None:
             prop = torch.as_tensor(propagation, dtype=torch.float32, device=self.device).reshape(batch.n_nodes, 100)
         z = self.forward_batch(batch, prop, objects if isinstance(objects, torch.Tensor) else None,
-                               return_state=return_state, return_steps=return_steps, relation_weights=relation_weights)
+                               return_state=return_state, return_steps=return_steps, relation_weights=relation_weights,
+                               relation_step_weights=relation_step_weights)
         shape = (self.mp_steps, *batch.node_shape) if return_steps else batch.node_shape
         if return_state:
             z, state = z
@@ -285,13 +319,15 @@ class GraphNetwork(nn.Module):
 
     def forward(self, objects, sender_relations, receiver_relations, propagation=None, plan: str = "host",
                 return_state: bool = False, return_steps: bool = False,
-                relation_weights: Optional[torch.Tensor] = None):
+                relation_weights: Optional[torch.Tensor] = None,
+                relation_step_weights: Optional[torch.Tensor] = None):
         """(B, N, 1) probabilities: sigmoid(x[:, :, :1]) of the last step (Networks.py:93-96);
-        differentiable in a torch ``objects`` like `forward_logits` (``plan`` and ``relation_weights`` as there). With
+        differentiable in a torch ``objects`` like `forward_logits` (``plan``, ``relation_weights`` and
+        ``relation_step_weights`` as there). With
         ``return_state`` ``(probabilities, state)``, state (B, N, 100). With ``return_steps`` the
         probabilities of every step, (S, B, N, 1): how the predicted stabilities settle over the steps."""
         z = self.forward_logits(objects, sender_relations, receiver_relations, propagation, plan, return_state,
-                                return_steps, relation_weights)
+                                return_steps, relation_weights, relation_step_weights)
         if return_state:
             return torch.sigmoid(z[0])[..., None], z[1]
         return torch.sigmoid(z)[..., None]

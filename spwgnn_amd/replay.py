@@ -329,7 +329,7 @@ def step_body(params, grads, m, v, path, adam, counters: DeviceCounters, make_ru
     step.AdamUpdate; `make_run(seed_dev=, prologue=)` builds the training RunConfig. `sums`: the epoch
     sums (total3, total3s or None, {towers of the batch: weights3}) the loss launch adds to. The buffers
     are bound here, as a captured graph binds their addresses.
-    `dropedge` ((rate, symmetric, rescale), or None): a DropEdge step. The mask kernel reads the uploaded plan and
+    `dropedge` ((rate, symmetric, rescale) or, per step, (rate, symmetric, rescale, True); or None): a DropEdge step. The mask kernel reads the uploaded plan and
     the advanced key, so this body does not fold the prologue: the upload (ReplayStep's copy_in) and
     spwgnn_step_advance run as launches of their own, then the mask into a static gates buffer of the geometry,
     then the gated forward / loss / backward on the device key — two launches more than the folded step."""
@@ -367,16 +367,18 @@ def _dropedge_body(params, grads, m, v, path, adam, counters, make_run, key_mode
     """`step_body` with DropEdge: no `pre` parameter, so ReplayStep issues the upload as its own launch."""
     tot, tot_s, w3s = sums if sums is not None else (None, None, None)
     tower_kw = bool(getattr(path, "needs_towers", False))
-    rate, symmetric, rescale = dropedge
+    rate, symmetric, rescale, *rest = dropedge
+    per_step = bool(rest and rest[0])   # layer-wise DropEdge: a mask row per propagation step (§3zzc)
     static = {}   # the geometry's gates buffer: a captured graph binds its address
 
     def body(batch, target, ws, bce, z, dz, weights=None, norm=None, norm_t=None):
         E.step_advance(counters.key, counters.step, key_mode, seed, rank)
         run = make_run(seed_dev=counters.key, prologue=None)
+        shape = (int(run.mp_steps), 32 * batch.n_eblocks) if per_step else (32 * batch.n_eblocks,)
         buf = static.get("gates")
-        if buf is None or buf.numel() != 32 * batch.n_eblocks:
-            buf = static["gates"] = torch.empty(32 * batch.n_eblocks, dtype=torch.float32, device=z.device)
-        gates = E.dropedge_gates(batch, run, rate, symmetric=symmetric, rescale=rescale, out=buf)
+        if buf is None or tuple(buf.shape) != shape:
+            buf = static["gates"] = torch.empty(shape, dtype=torch.float32, device=z.device)
+        gates = E.dropedge_gates(batch, run, rate, symmetric=symmetric, rescale=rescale, out=buf, per_step=per_step)
         logits = path.forward(params, batch, run, ws, z, gates=gates)
         path.loss_backward(params, batch, run, ws, logits, target, bce, dz, grads, tot,
                            w3s[batch.n_towers] if w3s is not None else None, tot_s, weights, norm, gates,

@@ -27,7 +27,10 @@ Optional (asked for only by the feature that needs it):
       (None with want_dlogits False: evaluate, which passes the micro-batch's own tower count as norm_t)
   dropedge_gates(batch, run, rate, symmetric=True, rescale=False, base=None) -> gates
       Trainer(dropedge=): one relation gate per edge slot of the plan ((32·n_eblocks,), 0 = dropped), drawn from
-      run.seed as engine.dropedge_gates draws it, `base` (a slot tensor or None) multiplied in
+      run.seed as engine.dropedge_gates draws it, `base` (a slot tensor or None) multiplied in; with
+      Trainer(dropedge_per_step=True) the call carries per_step=True and returns (mp_steps, 32·n_eblocks), a row per
+      propagation step, which the gated calls below then receive as their ``gates=`` (a 2-D tensor: the loss paths
+      hand it to the engine's ``step_gates=``)
   forward(params, batch, run, gates=gates) / backward(params, batch, run, dlogits, gates=gates)
       Trainer(dropedge=) and step(relation_weights=): the gated calls (engine.forward / backward's ``gates=``); the
       backward receives the tensor the forward of the same micro-batch ran with. Without DropEdge and without
@@ -44,6 +47,12 @@ from typing import Optional
 import torch
 
 from . import engine as E
+
+
+def gate_kw(gates) -> dict:
+    """The keyword `engine.forward` / `backward` take a gate tensor under: a 2-D one, (mp_steps, slots), holds one
+    gate per edge slot and step (``step_gates=``, layer-wise DropEdge); a 1-D one is shared by the steps."""
+    return {"step_gates" if gates.dim() == 2 else "gates": gates}
 
 
 class LossPath:
@@ -65,7 +74,7 @@ class LossPath:
     def forward(self, params, batch, run, ws, out=None, gates=None):
         """The logits the loss takes; ``out``: a replayed step's static (n,) logits buffer."""
         if gates is not None:
-            return E.forward(params, batch, run, ws, logits=out, gates=gates)
+            return E.forward(params, batch, run, ws, logits=out, **gate_kw(gates))
         return E.forward(params, batch, run, ws, logits=out)
 
     def loss(self, logits, target, total3=None, weights3=None, total3s=None, node_weights=None, norm=None):
@@ -75,7 +84,7 @@ class LossPath:
 
     def backward(self, params, batch, run, ws, dlogits, grads, gates=None):
         if gates is not None:
-            return E.backward(params, batch, run, ws, dlogits, grads=grads, gates=gates)[0]
+            return E.backward(params, batch, run, ws, dlogits, grads=grads, **gate_kw(gates))[0]
         return E.backward(params, batch, run, ws, dlogits, grads=grads)[0]
 
     def loss_backward(self, params, batch, run, ws, logits, target, scratch, dlogits, grads, total3=None,
@@ -86,7 +95,7 @@ class LossPath:
         if gates is not None:
             _, dz = E.bce(logits, target, scratch, dlogits=dlogits, total3=total3, weights3=weights3,
                           node_weights=node_weights, norm=norm)
-            E.backward(params, batch, run, ws, dz, grads=grads, gates=gates)
+            E.backward(params, batch, run, ws, dz, grads=grads, **gate_kw(gates))
             return
         E.bce_backward(params, batch, run, ws, logits, target, scratch, dlogits=dlogits, total3=total3,
                        weights3=weights3, grads=grads, node_weights=node_weights, norm=norm)
@@ -185,7 +194,7 @@ class TowerLossPath(LossPath):
         _, dz = self.loss(logits, target, node_weights=node_weights, norm=norm, batch=batch,
                           tower_targets=tower_targets, norm_t=norm_t, node_loss=node_loss, dlogits=dlogits)
         if gates is not None:
-            E.backward(params, batch, run, ws, dz, grads=grads, gates=gates)
+            E.backward(params, batch, run, ws, dz, grads=grads, **gate_kw(gates))
         else:
             E.backward(params, batch, run, ws, dz, grads=grads)
 

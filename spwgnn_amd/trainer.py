@@ -93,9 +93,10 @@ class HipEngine:
     def forward(self, params, batch: TowerBatch, run: E.RunConfig, gates=None):
         return self.path.forward(params, batch, run, self.ws, gates=gates)
 
-    def dropedge_gates(self, batch: TowerBatch, run: E.RunConfig, rate, symmetric=True, rescale=False, base=None):
+    def dropedge_gates(self, batch: TowerBatch, run: E.RunConfig, rate, symmetric=True, rescale=False, base=None,
+                       per_step=False):
         """The step's DropEdge mask as relation gates (engine.dropedge_gates), drawn from the run's key."""
-        return E.dropedge_gates(batch, run, rate, symmetric=symmetric, rescale=rescale, base=base)
+        return E.dropedge_gates(batch, run, rate, symmetric=symmetric, rescale=rescale, base=base, per_step=per_step)
 
     def loss(self, logits, target):
         return self.path.loss(logits, target)
@@ -163,7 +164,9 @@ class Trainer:
                  buckets: int = 1, overlap: bool = True, clipnorm: float = 0.0, clipvalue: float = 0.0,
                  decay: float = 0.0, skip_nonfinite: bool = False, step_loss_weights=None, tower_loss: float = 0.0,
                  node_loss: float = 1.0, dropedge: float = 0.0, dropedge_symmetric: bool = True,
-                 dropedge_rescale: bool = False):
+                 dropedge_rescale: bool = False, dropedge_per_step: bool = False):
+        # dropedge_per_step (layer-wise DropEdge; active only with dropedge > 0): a fresh subset at
+        # every propagation step — the step's gates are (mp_steps, slots) and go to the engine as step_gates.
         # dropedge (a rate in [0, 1)): every training step drops a random subset of the relations —
         # gate 0 in the receiver sum, or 1/(1 − rate) on a kept one with dropedge_rescale — drawn from the step's
         # dropout key with a kind of its own; dropedge_symmetric: both directions of a contact share the draw.
@@ -205,6 +208,7 @@ class Trainer:
                 self.engine.set_tower_loss(self.tower_loss, self.node_loss, mp_steps)
         self.dropedge = E.check_dropedge(dropedge)
         self.dropedge_symmetric, self.dropedge_rescale = bool(dropedge_symmetric), bool(dropedge_rescale)
+        self.dropedge_per_step = bool(dropedge_per_step)
         if self.dropedge > 0:
             if not E.gates_supported(math):
                 raise ValueError(f"dropedge needs a math that takes relation gates (spwgnn_gates_supported: x6, x3 and "
@@ -511,8 +515,11 @@ class Trainer:
         return out
 
     def _dropedge_options(self):
-        """(rate, symmetric, rescale) of a DropEdge trainer, None without it."""
-        return (self.dropedge, self.dropedge_symmetric, self.dropedge_rescale) if self.dropedge > 0 else None
+        """(rate, symmetric, rescale) of a DropEdge trainer — with a fourth entry True when the mask is drawn per
+        propagation step — None without it."""
+        if not self.dropedge > 0:
+            return None
+        return (self.dropedge, self.dropedge_symmetric, self.dropedge_rescale) + ((True,) if self.dropedge_per_step else ())
 
     def _gates(self, i: int, b, run):
         """Micro-batch i's relation gates: its relation weights (a slot tensor, or what `TowerBatch.edge_gates`
@@ -521,8 +528,9 @@ class Trainer:
         if base is not None and not (isinstance(base, torch.Tensor) and tuple(base.shape) == (32 * b.n_eblocks,)):
             base = b.edge_gates(base)
         if self.dropedge > 0:
+            kw = {"per_step": True} if self.dropedge_per_step else {}   # the shared mask: the call of before
             return self.engine.dropedge_gates(b, run, self.dropedge, symmetric=self.dropedge_symmetric,
-                                              rescale=self.dropedge_rescale, base=base)
+                                              rescale=self.dropedge_rescale, base=base, **kw)
         return base
 
     def _accumulate_and_update(self, batches, loss_of):

@@ -18,7 +18,14 @@ one JSON line; `--out` also writes it to a file.
 and of whole optimizer steps (forward, loss, backward, Adam) of a `Trainer`
   * without and with DropEdge, issued eagerly (`Trainer.step`) and replayed as a hipGraph (`Trainer.replay_step`).
 
+`step_gates` (`--step-gates`, which runs this section alone): at the headline shape and at batch
+32, alternating rounds of the forward + backward pair ungated, with one shared gate row (``gates=``) and with a row
+per propagation step (``step_gates=``, mp_steps distinct rows) — the cost of the per-step gate loads over the
+shared-gate step. `--shared-only` times the ungated and shared-gate pairs alone through the calls every earlier
+library has (a same-box A/B of the shared-gate step against another build, SPWGNN_LIB).
+
     python tools/relation_gates_bench.py --out profiles/relation_gates_bench.json
+    python tools/relation_gates_bench.py --step-gates --out profiles/step_gates_bench.json
 """
 import argparse
 import json
@@ -148,6 +155,44 @@ def steps32(args, math="x6"):
     return out
 
 
+def step_gates_cost(args, towers, calls, math="x6", shared_only=False):
+    dev, S = "cuda:0", args.mp_steps
+    raw = D.synthetic_towers_fast(towers, args.nodes, seed=1000 + 97 * args.nodes)
+    batch = TowerBatch.fully_connected((raw / D.RELATION_THRESHOLD).astype(np.float32), device=dev, nw_max=16)
+    flat = P.to_flat(P.glorot_uniform(0), device=dev)
+    rows = torch.as_tensor(np.random.default_rng(5).uniform(0.25, 1.5, (S, batch.n_edges)).astype(np.float32), device=dev)
+    shared = batch.edge_gates(rows[0])
+    run = E.RunConfig(S, training=True, dropout=0.1, seed=1, math=math)
+    dz = torch.as_tensor(np.random.default_rng(17).normal(0, 1e-3, batch.n_nodes).astype(np.float32), device=dev)
+    z, grads = torch.empty(batch.n_nodes, dtype=torch.float32, device=dev), torch.empty_like(flat)
+    wss = [E.Workspace(dev) for _ in range(3)]
+
+    def pair(ws, **kw):
+        E.forward(flat, batch, run, ws, logits=z, **kw)
+        E.backward(flat, batch, run, ws, dz, grads=grads, **kw)
+
+    variants = {"ungated": lambda: pair(wss[0]), "shared": lambda: pair(wss[1], gates=shared)}
+    if not shared_only:
+        per_step = batch.edge_step_gates(rows)
+        variants["per_step"] = lambda: pair(wss[2], step_gates=per_step)
+    t = _rounds(args, variants, calls)
+    assert bool(torch.isfinite(grads).all())
+    rnd = lambda xs: [round(x, 4) for x in xs]
+    out = {"towers": towers, "n_nodes": batch.n_nodes, "n_eblocks": batch.n_eblocks, "math": math, "calls_per_round": calls,
+           "fused_path_gated": E.fused_path(batch, run, gated=True)}
+    for k, v in t.items():
+        out[k + "_ms"] = rnd(v)
+        out[k + "_min_max"] = rnd([min(v), max(v)])
+    out["shared_over_ungated"] = round(min(t["shared"]) / min(t["ungated"]), 4)
+    if not shared_only:
+        out["per_step_over_shared"] = round(min(t["per_step"]) / min(t["shared"]), 4)
+        out["per_step_over_ungated"] = round(min(t["per_step"]) / min(t["ungated"]), 4)
+        # the extra gate loads of a per-step call: (S − 1) more rows of 4 bytes per slot, read by the edge forward, the
+        # edge backward (or the dA rebuild) and the W2 gradient's staging
+        out["extra_gate_bytes_per_reader"] = int((S - 1) * 4 * 32 * batch.n_eblocks)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--towers", type=int, default=65536)
@@ -160,8 +205,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dropedge", type=float, default=0.25)
     ap.add_argument("--only-steps32", action="store_true", help="the batch-32 step comparison alone")
+    ap.add_argument("--step-gates", action="store_true", help="the per-step gate comparison alone (DESIGN.md §3zzc)")
+    ap.add_argument("--shared-only", action="store_true", help="with --step-gates: ungated and shared-gate pairs alone")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.step_gates:
+        res = {"tool": "relation_gates_bench --step-gates", "device": torch.cuda.get_device_name(0),
+               "nodes_per_tower": args.nodes, "mp_steps": args.mp_steps, "rounds": args.rounds,
+               "step_gates": [step_gates_cost(args, args.towers, args.calls, shared_only=args.shared_only),
+                              step_gates_cost(args, args.small_towers, args.small_calls, shared_only=args.shared_only)]}
+        line = json.dumps(res)
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     res = {"tool": "relation_gates_bench", "device": torch.cuda.get_device_name(0), "nodes_per_tower": args.nodes,
            "mp_steps": args.mp_steps, "rounds": args.rounds,
            "runs": [] if args.only_steps32 else [one_shape(args, args.towers, args.calls),
